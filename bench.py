@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """bench.py -- MSM points/s on MI355X (BASELINE.json metric), one process per GPU, everything through the C ABI.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload bn254_g1] [--log-n 20] [--scaling weak|strong]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload bn254_g1] [--log-n 20] [--scaling weak|strong] [--full]
+                    [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...
 
 A "step" = one pass of the hot path over one batch: one Pippenger MSM (the reference's `msm_unchecked` call: uniform scalars
@@ -13,10 +14,15 @@ in Montgomery form, bases and scalars already resident in HBM).
           plane: rendezvous, barriers, max-over-ranks timing).
           --scaling weak (default): 2^log_n points per rank;  --scaling strong: 2^log_n points in total (BASELINE config 5 is
           `--workload bls12_381_g1|bls12_381_g2 --log-n 24 --scaling strong`).
-`value` = points of the whole job per second. The timed result is checked against the closed form (sum s_i k_i) G at every N.
+`value` = points of the whole job per second, `ms_per_step` = wall ms of one timed step.
 
-Extra objects on the JSON line: "roofline" (dominant kernel k_msm_accum, HIP-event timed on the launch stream; constants
-and PMC traffic read from profiles/roofline_inputs.json), "cpu_baseline" (oracle/c `oc_msm_fast` on this box's host cores on
+A plain run sets up, spins up (untimed steps until the clocks settle), runs W warm-up steps, times exactly K steps and prints the line.
+--dump-outputs DIR writes the last timed step's MSM result as DIR/msm_result.npy (see dump_outputs); inputs are seeded, so the same
+arguments give the same inputs on every run.
+
+--full adds everything else, as before: the first 20 steps after setup (`value_first_20_steps`), the closed-form check of the timed
+result against (sum s_i k_i) G at every N (`result_check`), and the extra objects on the JSON line: "roofline" (dominant kernel
+k_msm_accum, HIP-event timed on the launch stream; constants and PMC traffic read from profiles/roofline_inputs.json), "cpu_baseline" (oracle/c `oc_msm_fast` on this box's host cores on
 the step's own inputs; rank 0, N = 1 only) and "secondary" (MSM 2^24, NTT 2^22, Rep3 local_mul_vec, Groth16 prove ms, and the
 config-5 workloads at this N).
 """
@@ -105,6 +111,27 @@ def load_roofline_inputs():
         return json.load(open(os.path.join(ROOT, "profiles", "roofline_inputs.json")))
     except Exception:
         return {}
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, results: dict):
+    """--dump-outputs: every MSM result as <out_dir>/<name>.npy, float64 of shape (3, words): rows X, Y, Z of the Jacobian point the
+    C ABI hands back (the library's Montgomery limbs, Z in {0, 1}), every u64 limb split into its low and high 32-bit halves, least
+    significant first, so the float64 values are exact and two builds can be compared word for word."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    conv = {}
+    for name, words in results.items():
+        w = np.asarray(words, dtype=np.uint64).reshape(3, -1)
+        halves = np.stack([w & np.uint64(0xFFFFFFFF), w >> np.uint64(32)], axis=-1).reshape(3, -1)
+        conv[name] = np.ascontiguousarray(halves, dtype=np.float64)
+    total = sum(a.nbytes for a in conv.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError("--dump-outputs: %d bytes exceed the %d byte limit" % (total, DUMP_LIMIT_BYTES))
+    for name, a in conv.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 class Ctx:
@@ -758,7 +785,7 @@ def run_groth16_prove(cx: Ctx, args):
     dt = cx.max_over_ranks(time.perf_counter() - t0)
     if rank == 0:
         ok = None
-        if err is None and not args.no_check:
+        if err is None and args.full and not args.no_check:
             ok = circ.check()
         ms = dt / args.steps * 1e3
         med = lambda k: sorted(p[k] for p in phases)[len(phases) // 2] if phases else None
@@ -769,7 +796,7 @@ def run_groth16_prove(cx: Ctx, args):
                                        "one prover, its five query MSMs placed on the GPUs", "devices": devices,
                            "placement": {0: "auto (whole queries per GPU up to 2 GPUs, ranges of every query from 3 on)", 1: "whole queries per GPU (LPT, G2 = 2.5 x G1)",
                                          2: "the k-th range of every query per GPU"}[args.placement] + "; csh_bases_clone + csh_memcpy_peer, one host thread per GPU"},
-                "phases_ms_median": {k: med(k) for k in ("witness_upload_and_map", "msm_groups", "finish")}, "result_check": ok, "error": err,
+                "phases_ms_median": {k: med(k) for k in ("witness_upload_and_map", "msm_groups", "finish")}, "result_check": ok, "error": err, "full": args.full,
                 "roofline": None, "cpu_baseline": None}
         print(json.dumps(line))
         if circ is not None:
@@ -812,7 +839,16 @@ def main():
     ap.add_argument("--no-extras", action="store_true", help="skip the secondary metrics")
     ap.add_argument("--quick", action="store_true", help="shrink the secondary workloads (schema tests of the N > 1 line on a small box): "
                                                          "split MSM 2^18, NTT 2^16, prove 2^14")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline: the cold first-20-step figure, the roofline, the "
+                                                        "closed-form check, the secondary workloads and the CPU baseline (off: the plain run "
+                                                        "sets up, warms up, times the K steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller as DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.workload == "groth16_prove":
+        ap.error("--dump-outputs: the groth16_prove workload returns no arrays to its caller (the proof stays inside the library handle)")
     args.split_log_n, args.ntt_log_n, args.prove_log_n = (18, 16, 14) if args.quick else (24, 22, 20)
 
     if args.workload == "groth16_prove":
@@ -833,27 +869,33 @@ def main():
         n_local = per if rank < world - 1 else total - start
 
     job = MsmJob(cx, args.workload, start, n_local, 1234 + rank)
-    want_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload == "bn254_g1"
+    want_cpu = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload == "bn254_g1"
     pts_host = job.points_to_host() if want_cpu else None
     job.drop_point_copy()
-    # the first 20 steps after setup (what rounds 1-4 recorded under the driver's `--steps 20 --warmup 5`: inside the clock ramp of an idle GPU),
-    # kept beside `value`; then the spin-up (untimed, >= 0.3 s, until two consecutive 10-step medians agree within 2 %), then W warm-up
-    # steps and EXACTLY K timed steps between barriers
-    cold_dt, _ = job.timed(20, 3)
-    value_first_20 = total * 20 / cold_dt
+    # --full: the first 20 steps after setup (what rounds 1-4 recorded under the driver's `--steps 20 --warmup 5`: inside the clock ramp of an
+    # idle GPU), kept beside `value`. Every run: the spin-up (untimed, >= 0.3 s, until two consecutive 10-step medians agree within 2 %), then
+    # W warm-up steps and EXACTLY K timed steps between barriers
+    value_first_20, cold_ms_per_step = None, None
+    if args.full:
+        cold_dt, _ = job.timed(20, 3)
+        value_first_20, cold_ms_per_step = total * 20 / cold_dt, cold_dt / 20 * 1e3
     for _ in range(args.spinup):
         job.step()
     spin_steps, spin_ms, spin_last_ms = job.spin_up(min_s=args.spinup_s) if args.spinup_s > 0 else (0, 0.0, None)
     dt, res = job.timed(args.steps, args.warmup)
     ms_per_step = dt / args.steps * 1e3
     value = total * args.steps / dt
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"msm_result": res})
 
-    log_local = max(0, n_local.bit_length() - 1)
-    roofline = msm_roofline(job, rin, log_local)          # every rank runs the same untimed passes (keeps the ranks in step)
-    check = None if args.no_check else job.check(res)
+    roofline, check = None, None
+    if args.full:
+        log_local = max(0, n_local.bit_length() - 1)
+        roofline = msm_roofline(job, rin, log_local)          # every rank runs the same untimed passes (keeps the ranks in step)
+        check = None if args.no_check else job.check(res)
 
     extras, cpu_inputs24 = None, None
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         try:
             if world == 1:
                 extras, cpu_inputs24 = secondary_single_gpu(cx, rin, args)
@@ -917,7 +959,7 @@ def main():
                        "spinup_steps": args.spinup + spin_steps,
                        "spinup_ms": round(spin_ms, 1), "spinup_last_batch_median_ms": spin_last_ms,
                        "spinup_rule": "untimed steps before the W warm-up steps: batches of 10 for >= %.1f s until two consecutive batch medians agree within 2 %% (cap 3 s)" % args.spinup_s},
-            "value_first_20_steps": value_first_20, "ms_per_step_first_20_steps": cold_dt / 20 * 1e3,
+            "full": args.full, "value_first_20_steps": value_first_20, "ms_per_step_first_20_steps": cold_ms_per_step,
             # the same workload on a handle that carries the library's fixed-base tables (round 6: what a prover gets at key load through
             # csh_bases_table_policy; `value` itself stays the plain handle) -- top-level scalars, copied from `secondary`
             "value_fixed_base_tables": ((extras or {}).get(f"msm_{args.workload}_2p{args.log_n}_fixed_base_tables") or {}).get("points_per_s"),

@@ -43,3 +43,18 @@ def test_uniform_scalars_are_below_the_modulus_and_use_the_full_range():
     vals = [sum(((int(x) + (1 << 64)) % (1 << 64)) << (64 * i) for i, x in enumerate(row)) for row in sc.tolist()]
     assert all(0 <= v < m for v in vals) and max(vals) > (m * 15) // 16 and len(set(vals)) == len(vals)
     assert any(((v >> 63) & 1) for v in vals) and any((v >> 252) & 1 for v in vals)        # bit 63 of the lower limbs is random too
+
+
+def test_dump_outputs_writes_the_result_words_exactly_as_float64(tmp_path):
+    """--dump-outputs: the MSM result's u64 limbs go out as exact float64 32-bit halves, rows X, Y, Z, least significant first."""
+    import numpy as np
+    r = random.Random(11)
+    for limbs in (4, 6, 8, 12):                  # u64 words per coordinate: BN254 G1, BLS12 G1, BN254 G2, BLS12 G2
+        words = np.array([r.getrandbits(64) for _ in range(3 * limbs)], dtype=np.uint64)
+        d = tmp_path / str(limbs)
+        bench.dump_outputs(str(d), {"msm_result": words})
+        a = np.load(d / "msm_result.npy")
+        assert a.dtype == np.float64 and a.shape == (3, 2 * limbs)
+        h = a.astype(np.uint64).reshape(3, limbs, 2)
+        assert (a == np.floor(a)).all() and (a < 2.0**32).all()
+        assert ((h[..., 0] | (h[..., 1] << np.uint64(32))).reshape(-1) == words).all()

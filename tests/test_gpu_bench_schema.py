@@ -7,6 +7,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -24,7 +25,7 @@ def _run(cmd, env_extra, timeout=900):
 
 def test_two_rank_line_folded_on_one_gpu(gpu):
     line = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", "29533",
-                 "bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1", "--log-n", "16", "--quick"], {"BENCH_FOLD_RANKS": "1"})
+                 "bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1", "--log-n", "16", "--quick", "--full"], {"BENCH_FOLD_RANKS": "1"})
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config",
               "roofline", "cpu_baseline", "result_check", "secondary"):
         assert k in line, k
@@ -60,7 +61,7 @@ def test_two_rank_line_folded_on_one_gpu(gpu):
 
 
 def test_single_gpu_line_quick(gpu):
-    line = _run([sys.executable, "bench.py", "--steps", "5", "--warmup", "2", "--log-n", "16", "--quick", "--no-cpu-baseline"], {})
+    line = _run([sys.executable, "bench.py", "--steps", "5", "--warmup", "2", "--log-n", "16", "--quick", "--no-cpu-baseline", "--full"], {})
     assert line["n_gpus"] == 1 and line["result_check"] is True and line["cpu_baseline"] is None
     sec = line["secondary"]
     assert "error" not in sec, sec
@@ -78,3 +79,21 @@ def test_single_gpu_line_quick(gpu):
     assert pr["rep3_trait_path"]["seeded_device_masks"]["party0_phases_ms"]["mask_draw"] < pr["rep3_trait_path"]["host_masks"]["party0_phases_ms"]["mask_draw"]
     assert pr["prove_ms"] >= pr["prove_ms_min"] and pr["trait_path_ms"] >= pr["trait_path_ms_min"]   # medians, the minimum beside them
     assert pr["closed_form_check"] is True and pr["trait_path_closed_form_check"] is True and pr["trait_path_ms"] > 0 and pr["rep3_proofs_equal_plain"] is True
+
+
+def test_plain_line_times_k_steps_and_dumps_the_checked_result(gpu, tmp_path):
+    """The plain run (no --full): the headline keys and nothing measured beyond them; --dump-outputs writes the last timed step's MSM
+    result, and a --full run with the same arguments (closed-form checked) dumps the same words."""
+    plain, full = tmp_path / "plain", tmp_path / "full"
+    line = _run([sys.executable, "bench.py", "--steps", "7", "--warmup", "2", "--log-n", "16", "--dump-outputs", str(plain)], {})
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in line, k
+    assert line["steps"] == 7 and line["warmup"] == 2 and line["full"] is False and line["ms_per_step"] > 0
+    assert line["value"] == pytest.approx(line["config"]["points_total"] * 1e3 / line["ms_per_step"], rel=1e-9)
+    assert line["roofline"] is None and line["secondary"] is None and line["cpu_baseline"] is None and line["value_first_20_steps"] is None
+    a = np.load(plain / "msm_result.npy")
+    assert a.dtype == np.float64 and a.shape == (3, 8)
+    line = _run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--log-n", "16", "--full", "--no-extras", "--no-cpu-baseline",
+                 "--dump-outputs", str(full)], {})
+    assert line["full"] is True and line["result_check"] is True and line["roofline"]["c"] > 0 and line["value_first_20_steps"] > 0
+    assert np.array_equal(a, np.load(full / "msm_result.npy"))

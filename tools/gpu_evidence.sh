@@ -24,7 +24,7 @@ python -c "import os, cosnarks_amd as h; print('devices', h.device_count(), h.li
 if has tests; then (timeout -s KILL 1500 python -m pytest tests -m gpu -q -p no:cacheprovider --durations=10 2>&1 | tail -30) > ${S}_pytest_gpu.log; fi
 if has long; then (timeout -s KILL 1500 python -m pytest tests -m gpu_long -q -p no:cacheprovider --durations=10 2>&1 | tail -25) > ${S}_pytest_gpu_long.log; fi
 if has bench; then
-  (timeout -s KILL 1200 python bench.py --steps 20 --warmup 5 2>${S}_bench.err | tail -1) > ${S}_bench.log          # the driver's own command
+  (timeout -s KILL 1200 python bench.py --steps 20 --warmup 5 --full 2>${S}_bench.err | tail -1) > ${S}_bench.log   # the driver's command, with everything --full adds
   (timeout -s KILL 600 python bench.py --no-extras --no-cpu-baseline 2>/dev/null | tail -1) > ${S}_bench_default_flags.log
   (timeout -s KILL 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2) > ${S}_smoke.log
   (timeout -s KILL 300 python bench.py --workload groth16_prove --log-n 20 --steps 10 --warmup 3 2>/dev/null | tail -1) > ${S}_bench_prove_n1.log
