@@ -10,7 +10,10 @@
  *
  * Data conventions (identical to arkworks' in-memory layout, so Rust slices can be passed as-is):
  *  - field element  = N64 little-endian u64 limbs of x*R mod p (Montgomery, R = 2^(64*N64));
- *                     Fr: 4 limbs (32 B) on both curves; Fq: 4 limbs (BN254) / 6 limbs (BLS12-381).
+ *                     Fr: 4 limbs (32 B) on every curve; Fq: 4 limbs (BN254) / 6 limbs (BLS12-381, BLS12-377).
+ *                     Every field element the library returns (vectors, transforms, shares, masks, point
+ *                     coordinates) is canonical arkworks Montgomery form: x*R mod p < p, never a lazy
+ *                     representative such as x*R mod p + p, even where kernels compute in lazy form inside.
  *  - affine point   = x || y (G2: x.c0 || x.c1 || y.c0 || y.c1), Montgomery; infinity = all-zero bytes
  *                     (the zkey convention).  `stride_bytes` lets the caller pass arkworks `Affine`
  *                     (x, y, infinity flag, padding) without repacking -- the flag byte is ignored.

@@ -287,7 +287,7 @@ int oc_hash_points_bn254_g1(uint64_t seed, size_t n, int nthreads, uint64_t* out
   return 0;
 }
 
-/* ---- NTT / vector ops over Fr (both scalar fields are 4 limbs) ------------------------------------------- */
+/* ---- NTT / vector ops over Fr (every scalar field is 4 limbs) ------------------------------------------- */
 typedef struct { uint64_t l[4]; } fr_t;
 typedef void (*fr_bin)(fr_t*, const fr_t*, const fr_t*);
 static void bnr_mul_w(fr_t* r, const fr_t* a, const fr_t* b) { bnr_mul((bnr_t*)r, (const bnr_t*)a, (const bnr_t*)b); }
@@ -296,19 +296,27 @@ static void bnr_sub_w(fr_t* r, const fr_t* a, const fr_t* b) { bnr_sub((bnr_t*)r
 static void blr_mul_w(fr_t* r, const fr_t* a, const fr_t* b) { blr_mul((blr_t*)r, (const blr_t*)a, (const blr_t*)b); }
 static void blr_add_w(fr_t* r, const fr_t* a, const fr_t* b) { blr_add((blr_t*)r, (const blr_t*)a, (const blr_t*)b); }
 static void blr_sub_w(fr_t* r, const fr_t* a, const fr_t* b) { blr_sub((blr_t*)r, (const blr_t*)a, (const blr_t*)b); }
+static void b7r_mul_w(fr_t* r, const fr_t* a, const fr_t* b) { b7r_mul((b7r_t*)r, (const b7r_t*)a, (const b7r_t*)b); }
+static void b7r_add_w(fr_t* r, const fr_t* a, const fr_t* b) { b7r_add((b7r_t*)r, (const b7r_t*)a, (const b7r_t*)b); }
+static void b7r_sub_w(fr_t* r, const fr_t* a, const fr_t* b) { b7r_sub((b7r_t*)r, (const b7r_t*)a, (const b7r_t*)b); }
 
 typedef struct { fr_bin mul, add, sub; fr_t one; } fr_ops;
-static fr_ops ops_for(int curve) {
-  fr_ops o;
-  if (curve == 0) { o.mul = bnr_mul_w; o.add = bnr_add_w; o.sub = bnr_sub_w; memcpy(&o.one, BN254_FR_R, 32); }
-  else { o.mul = blr_mul_w; o.add = blr_add_w; o.sub = blr_sub_w; memcpy(&o.one, BLS381_FR_R, 32); }
-  return o;
+/* curve: 0 BN254, 1 BLS12-381, 3 BLS12-377 (csh_curve_t). Any other id is refused: the Fr entry points return nonzero. */
+static int ops_for(int curve, fr_ops* o) {
+  if (curve == 0) { o->mul = bnr_mul_w; o->add = bnr_add_w; o->sub = bnr_sub_w; memcpy(&o->one, BN254_FR_R, 32); return 0; }
+  if (curve == 1) { o->mul = blr_mul_w; o->add = blr_add_w; o->sub = blr_sub_w; memcpy(&o->one, BLS381_FR_R, 32); return 0; }
+  if (curve == 3) { o->mul = b7r_mul_w; o->add = b7r_add_w; o->sub = b7r_sub_w; memcpy(&o->one, BLS377_FR_R, 32); return 0; }
+  return -1;
 }
 static void fr_inv(int curve, fr_t* r, const fr_t* a) {
-  if (curve == 0) bnr_inv((bnr_t*)r, (const bnr_t*)a); else blr_inv((blr_t*)r, (const blr_t*)a);
+  if (curve == 0) bnr_inv((bnr_t*)r, (const bnr_t*)a);
+  else if (curve == 1) blr_inv((blr_t*)r, (const blr_t*)a);
+  else if (curve == 3) b7r_inv((b7r_t*)r, (const b7r_t*)a);
 }
 static void fr_from_u64(int curve, fr_t* r, uint64_t v) {
-  if (curve == 0) bnr_from_u64((bnr_t*)r, v); else blr_from_u64((blr_t*)r, v);
+  if (curve == 0) bnr_from_u64((bnr_t*)r, v);
+  else if (curve == 1) blr_from_u64((blr_t*)r, v);
+  else if (curve == 3) b7r_from_u64((b7r_t*)r, v);
 }
 
 static size_t bitrev(size_t i, int logn) {
@@ -331,7 +339,8 @@ int oc_bit_reverse(uint64_t* data, int logn, int ncomp) {
  * bit-reversed out, scaled by 1/n; decimation in frequency with the inverse root). gen: Montgomery. */
 int oc_ntt(int curve, uint64_t* data, int logn, const uint64_t* gen, int ncomp, int dif, int nthreads) {
   nthreads = threads_or_default(nthreads);
-  fr_ops o = ops_for(curve);
+  fr_ops o;
+  if (ops_for(curve, &o)) return -1;
   size_t n = (size_t)1 << logn;
   fr_t* v = (fr_t*)data;
   if (logn == 0) return 0;
@@ -377,7 +386,8 @@ int oc_ntt(int curve, uint64_t* data, int logn, const uint64_t* gen, int ncomp, 
 
 int oc_vec_mul(int curve, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n, int nthreads) {
   nthreads = threads_or_default(nthreads);
-  fr_ops o = ops_for(curve);
+  fr_ops o;
+  if (ops_for(curve, &o)) return -1;
 #pragma omp parallel for schedule(static) num_threads(nthreads)
   for (size_t i = 0; i < n; i++) o.mul((fr_t*)out + i, (const fr_t*)a + i, (const fr_t*)b + i);
   return 0;
@@ -385,7 +395,8 @@ int oc_vec_mul(int curve, const uint64_t* a, const uint64_t* b, uint64_t* out, s
 
 int oc_rep3_local_mul_vec(int curve, const uint64_t* lhs, const uint64_t* rhs, const uint64_t* mask, uint64_t* out, size_t n, int nthreads) {
   nthreads = threads_or_default(nthreads);
-  fr_ops o = ops_for(curve);
+  fr_ops o;
+  if (ops_for(curve, &o)) return -1;
   const fr_t *l = (const fr_t*)lhs, *r = (const fr_t*)rhs, *m = (const fr_t*)mask;
 #pragma omp parallel for schedule(static) num_threads(nthreads)
   for (size_t i = 0; i < n; i++) {
@@ -402,7 +413,8 @@ int oc_rep3_local_mul_vec(int curve, const uint64_t* lhs, const uint64_t* rhs, c
 
 int oc_vec_mul_table(int curve, uint64_t* v, const uint64_t* table, size_t n, int ncomp, int nthreads) {
   nthreads = threads_or_default(nthreads);
-  fr_ops o = ops_for(curve);
+  fr_ops o;
+  if (ops_for(curve, &o)) return -1;
 #pragma omp parallel for schedule(static) num_threads(nthreads)
   for (size_t i = 0; i < n; i++)
     for (int c = 0; c < ncomp; c++) o.mul((fr_t*)v + i * ncomp + c, (fr_t*)v + i * ncomp + c, (const fr_t*)table + i);
@@ -411,7 +423,8 @@ int oc_vec_mul_table(int curve, uint64_t* v, const uint64_t* table, size_t n, in
 
 int oc_vec_sub(int curve, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n_elems, int nthreads) {
   nthreads = threads_or_default(nthreads);
-  fr_ops o = ops_for(curve);
+  fr_ops o;
+  if (ops_for(curve, &o)) return -1;
 #pragma omp parallel for schedule(static) num_threads(nthreads)
   for (size_t i = 0; i < n_elems; i++) o.sub((fr_t*)out + i, (const fr_t*)a + i, (const fr_t*)b + i);
   return 0;
@@ -419,7 +432,8 @@ int oc_vec_sub(int curve, const uint64_t* a, const uint64_t* b, uint64_t* out, s
 
 /* Horner: out = sum_i coeffs[i * stride] * x^i (i < n), no NTT code involved (spot checks of full-size transforms) */
 int oc_eval_poly(int curve, const uint64_t* coeffs, size_t n, size_t stride, const uint64_t* x, uint64_t* out) {
-  fr_ops o = ops_for(curve);
+  fr_ops o;
+  if (ops_for(curve, &o)) return -1;
   fr_t acc; memset(&acc, 0, sizeof acc);
   for (size_t i = n; i-- > 0;) { o.mul(&acc, &acc, (const fr_t*)x); o.add(&acc, &acc, (const fr_t*)coeffs + i * stride); }
   *(fr_t*)out = acc;
@@ -428,7 +442,8 @@ int oc_eval_poly(int curve, const uint64_t* coeffs, size_t n, size_t stride, con
 
 int oc_vec_add(int curve, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n_elems, int nthreads) {
   nthreads = threads_or_default(nthreads);
-  fr_ops o = ops_for(curve);
+  fr_ops o;
+  if (ops_for(curve, &o)) return -1;
 #pragma omp parallel for schedule(static) num_threads(nthreads)
   for (size_t i = 0; i < n_elems; i++) o.add((fr_t*)out + i, (const fr_t*)a + i, (const fr_t*)b + i);
   return 0;
@@ -437,7 +452,8 @@ int oc_vec_add(int curve, const uint64_t* a, const uint64_t* b, uint64_t* out, s
 /* out[i] = sum_k coeffs[k] * shares[k][i] (Shamir reconstruct / open_vec, shamir.rs:483-491; Rep3 combine with coeffs = 1) */
 int oc_lincomb(int curve, const uint64_t* const* shares, const uint64_t* coeffs, size_t k, uint64_t* out, size_t n, int nthreads) {
   nthreads = threads_or_default(nthreads);
-  fr_ops o = ops_for(curve);
+  fr_ops o;
+  if (ops_for(curve, &o)) return -1;
 #pragma omp parallel for schedule(static) num_threads(nthreads)
   for (size_t i = 0; i < n; i++) {
     fr_t acc, t; memset(&acc, 0, sizeof acc);
@@ -449,7 +465,8 @@ int oc_lincomb(int curve, const uint64_t* const* shares, const uint64_t* coeffs,
 
 int oc_rep3_to_shamir_vec(int curve, const uint64_t* in, const uint64_t* x, const uint64_t* y, uint64_t* out, size_t n, int nthreads) {
   nthreads = threads_or_default(nthreads);
-  fr_ops o = ops_for(curve);
+  fr_ops o;
+  if (ops_for(curve, &o)) return -1;
   const fr_t* s = (const fr_t*)in;
 #pragma omp parallel for schedule(static) num_threads(nthreads)
   for (size_t i = 0; i < n; i++) {
@@ -463,7 +480,8 @@ int oc_rep3_to_shamir_vec(int curve, const uint64_t* in, const uint64_t* x, cons
 
 /* out[bitrev(i)] = shift^i (reduction.rs:45-60) */
 int oc_coset_table(int curve, const uint64_t* shift, int logn, uint64_t* out) {
-  fr_ops o = ops_for(curve);
+  fr_ops o;
+  if (ops_for(curve, &o)) return -1;
   size_t n = (size_t)1 << logn;
   fr_t cur = o.one;
   for (size_t i = 0; i < n; i++) {

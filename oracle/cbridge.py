@@ -16,13 +16,23 @@ _LIB = None
 
 
 def lib():
+    """Loads oracle/c/liboracle.so, running `make -s` first on every first load: the Makefile tracks oracle.c and its headers, so an
+    edited restatement is never shadowed by a stale library (a no-op when it is up to date)."""
     global _LIB
     if _LIB is None:
-        p = os.path.join(_HERE, "c", "liboracle.so")
-        if not os.path.exists(p):
-            subprocess.run(["make", "-s", "-C", os.path.join(_HERE, "c")], check=True)
-        _LIB = C.CDLL(p)
+        subprocess.run(["make", "-s", "-C", os.path.join(_HERE, "c")], check=True)
+        _LIB = C.CDLL(os.path.join(_HERE, "c", "liboracle.so"))
     return _LIB
+
+
+class OracleError(RuntimeError):
+    pass
+
+
+def _fr_check(rc, what, curve):
+    """The Fr entry points return nonzero for a curve id without a scalar field here (only 0 BN254, 1 BLS12-381, 3 BLS12-377)."""
+    if rc != 0:
+        raise OracleError("oracle/c %s: curve id %r refused (rc %d)" % (what, curve, rc))
 
 
 def _p(a):
@@ -122,14 +132,14 @@ def eval_poly(curve, coeffs, x, stride=1, offset=0):
     xx = np.ascontiguousarray(x, dtype=np.uint64)
     out = np.zeros(4, dtype=np.uint64)
     n = (c.shape[0] - offset + stride - 1) // stride
-    lib().oc_eval_poly(curve, C.c_void_p(c.ctypes.data + 32 * offset), C.c_size_t(n), C.c_size_t(stride), _p(xx), _p(out))
+    _fr_check(lib().oc_eval_poly(curve, C.c_void_p(c.ctypes.data + 32 * offset), C.c_size_t(n), C.c_size_t(stride), _p(xx), _p(out)), "eval_poly", curve)
     return out
 
 
 def vec_add(curve, a, b, threads=0):
     a, b = np.ascontiguousarray(a, dtype=np.uint64), np.ascontiguousarray(b, dtype=np.uint64)
     out = np.empty_like(a)
-    lib().oc_vec_add(curve, _p(a), _p(b), _p(out), C.c_size_t(a.size // 4), _t(threads))
+    _fr_check(lib().oc_vec_add(curve, _p(a), _p(b), _p(out), C.c_size_t(a.size // 4), _t(threads)), "vec_add", curve)
     return out
 
 
@@ -139,14 +149,14 @@ def lincomb(curve, shares, coeffs, threads=0):
     arr = (C.c_void_p * k)(*[s.ctypes.data for s in sh])
     co = np.ascontiguousarray(coeffs, dtype=np.uint64)
     out = np.empty(n * 4, dtype=np.uint64)
-    lib().oc_lincomb(curve, arr, _p(co), C.c_size_t(k), _p(out), C.c_size_t(n), _t(threads))
+    _fr_check(lib().oc_lincomb(curve, arr, _p(co), C.c_size_t(k), _p(out), C.c_size_t(n), _t(threads)), "lincomb", curve)
     return out
 
 
 def ntt(curve: int, data, logn: int, gen, ncomp=1, dif=False, threads=0):
     d = np.ascontiguousarray(data, dtype=np.uint64).copy()
     g = np.ascontiguousarray(gen, dtype=np.uint64)
-    assert lib().oc_ntt(curve, _p(d), logn, _p(g), ncomp, int(dif), _t(threads)) == 0
+    _fr_check(lib().oc_ntt(curve, _p(d), logn, _p(g), ncomp, int(dif), _t(threads)), "ntt", curve)
     return d
 
 
@@ -159,14 +169,14 @@ def bit_reverse(data, logn: int, ncomp=1):
 def coset_table(curve: int, shift, logn: int):
     out = np.zeros((1 << logn) * 4, dtype=np.uint64)
     s = np.ascontiguousarray(shift, dtype=np.uint64)
-    lib().oc_coset_table(curve, _p(s), logn, _p(out))
+    _fr_check(lib().oc_coset_table(curve, _p(s), logn, _p(out)), "coset_table", curve)
     return out
 
 
 def vec_mul(curve, a, b, threads=0):
     a, b = np.ascontiguousarray(a, dtype=np.uint64), np.ascontiguousarray(b, dtype=np.uint64)
     out = np.empty_like(a)
-    lib().oc_vec_mul(curve, _p(a), _p(b), _p(out), C.c_size_t(a.size // 4), _t(threads))
+    _fr_check(lib().oc_vec_mul(curve, _p(a), _p(b), _p(out), C.c_size_t(a.size // 4), _t(threads)), "vec_mul", curve)
     return out
 
 
@@ -175,21 +185,21 @@ def rep3_local_mul_vec(curve, l, r, mask=None, threads=0):
     m = np.ascontiguousarray(mask, dtype=np.uint64) if mask is not None else None
     n = l.size // 8
     out = np.empty(n * 4, dtype=np.uint64)
-    lib().oc_rep3_local_mul_vec(curve, _p(l), _p(r), _p(m), _p(out), C.c_size_t(n), _t(threads))
+    _fr_check(lib().oc_rep3_local_mul_vec(curve, _p(l), _p(r), _p(m), _p(out), C.c_size_t(n), _t(threads)), "rep3_local_mul_vec", curve)
     return out
 
 
 def vec_mul_table(curve, v, table, ncomp=1, threads=0):
     v = np.ascontiguousarray(v, dtype=np.uint64).copy()
     t = np.ascontiguousarray(table, dtype=np.uint64)
-    lib().oc_vec_mul_table(curve, _p(v), _p(t), C.c_size_t(t.size // 4), ncomp, _t(threads))
+    _fr_check(lib().oc_vec_mul_table(curve, _p(v), _p(t), C.c_size_t(t.size // 4), ncomp, _t(threads)), "vec_mul_table", curve)
     return v
 
 
 def vec_sub(curve, a, b, threads=0):
     a, b = np.ascontiguousarray(a, dtype=np.uint64), np.ascontiguousarray(b, dtype=np.uint64)
     out = np.empty_like(a)
-    lib().oc_vec_sub(curve, _p(a), _p(b), _p(out), C.c_size_t(a.size // 4), _t(threads))
+    _fr_check(lib().oc_vec_sub(curve, _p(a), _p(b), _p(out), C.c_size_t(a.size // 4), _t(threads)), "vec_sub", curve)
     return out
 
 
@@ -197,8 +207,8 @@ def rep3_to_shamir_vec(curve, in_ab, x, y, threads=0):
     a = np.ascontiguousarray(in_ab, dtype=np.uint64)
     n = a.size // 8
     out = np.empty(n * 4, dtype=np.uint64)
-    lib().oc_rep3_to_shamir_vec(curve, _p(a), _p(np.ascontiguousarray(x, dtype=np.uint64)), _p(np.ascontiguousarray(y, dtype=np.uint64)),
-                                _p(out), C.c_size_t(n), _t(threads))
+    _fr_check(lib().oc_rep3_to_shamir_vec(curve, _p(a), _p(np.ascontiguousarray(x, dtype=np.uint64)), _p(np.ascontiguousarray(y, dtype=np.uint64)),
+                                          _p(out), C.c_size_t(n), _t(threads)), "rep3_to_shamir_vec", curve)
     return out
 
 

@@ -267,8 +267,9 @@ def pack_points(curve: Curve, pts) -> np.ndarray:
     return np.frombuffer(bytes(out), dtype="<u8").reshape(len(pts), 2 * k * base.nlimbs).copy()
 
 
-def unpack_points(curve: Curve, arr, ncoords: int = 2):
-    """Inverse of pack_points; ncoords=3 decodes Jacobian (X,Y,Z) triples (not normalised)."""
+def unpack_points(curve: Curve, arr, ncoords: int = 2, strict: bool = False):
+    """Inverse of pack_points; ncoords=3 decodes Jacobian (X,Y,Z) triples (not normalised). strict: every coordinate component's raw
+    word value must be < q (canonical Montgomery form), else AssertionError naming the point, coordinate and value."""
     F = curve.F
     base = F.base if isinstance(F, fl.Fp2) else F
     k = F.ncoeff()
@@ -283,7 +284,11 @@ def unpack_points(curve: Curve, arr, ncoords: int = 2):
             cs = []
             for j in range(k):
                 off = i * stride + (cidx * k + j) * nb
-                cs.append(base.from_mont(int.from_bytes(raw[off:off + nb], "little")))
+                v = int.from_bytes(raw[off:off + nb], "little")
+                if strict and v >= base.p:
+                    raise AssertionError("non-canonical coordinate: point %d, coordinate %d, component %d: raw word value %#x >= q (%#x)"
+                                         % (i, cidx, j, v, base.p))
+                cs.append(base.from_mont(v))
             coords.append(F.from_coeffs(cs))
         if ncoords == 2:
             if F.is_zero(coords[0]) and F.is_zero(coords[1]):

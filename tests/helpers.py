@@ -28,8 +28,55 @@ def pack(F, xs, mont=True):
     return fl.pack(F, xs, mont).reshape(-1)
 
 
-def unpack(F, arr, mont=True):
+def uniform_limbs(F, rs, n):
+    """n field elements of F uniform in [0, p) as (n, 4) u64 limbs (used raw: any value < p is a valid Montgomery encoding). Seeded by
+    the numpy RandomState `rs` and vectorised: p.bit_length() random bits per value, values >= p redrawn -- the whole field, including
+    its top (on BLS12-381 Fr three quarters of the values are >= 2^253)."""
+    assert F.nlimbs == 4
+    bits = F.p.bit_length()
+    top = np.uint64((1 << (bits - 192)) - 1)
+    pl = [np.uint64((F.p >> (64 * i)) & (2**64 - 1)) for i in range(4)]
+    out = np.empty((n, 4), dtype=np.uint64)
+    todo = np.arange(n)
+    while todo.size:
+        v = rs.randint(0, 2**64, size=(todo.size, 4), dtype=np.uint64)
+        v[:, 3] &= top
+        lt, eq = np.zeros(todo.size, dtype=bool), np.ones(todo.size, dtype=bool)
+        for i in (3, 2, 1, 0):                      # v < p, most significant limb first
+            lt |= eq & (v[:, i] < pl[i])
+            eq &= v[:, i] == pl[i]
+        out[todo[lt]] = v[lt]
+        todo = todo[~lt]
+    return out
+
+
+def unpack(F, arr, mont=True, lenient=False):
+    """C-ABI limbs -> ints. Strict by default: every raw word value must be < p (the library's contract: canonical arkworks
+    Montgomery form, or canonical integers with mont=False); a lazy value x + p would otherwise decode to the right residue.
+    lenient=True only for a documented non-canonical value, with a comment saying why."""
+    if not lenient:
+        assert_canonical(F, arr)
     return fl.unpack(F, arr, mont)
+
+
+def assert_canonical(F, arr):
+    """Vectorised strict check without decoding (large vectors compared byte for byte elsewhere): every raw word value < p."""
+    a = np.ascontiguousarray(arr, dtype="<u8").reshape(-1, F.nlimbs)
+    bad = _noncanonical_rows(F, a)
+    if bad.size:
+        i = int(bad[0])
+        raise AssertionError("non-canonical field element at index %d: raw word value %#x >= p (%#x); %d of %d values non-canonical"
+                             % (i, int.from_bytes(a[i].tobytes(), "little"), F.p, bad.size, a.shape[0]))
+
+
+def _noncanonical_rows(F, a):
+    """Row indices of a (n, nlimbs) u64 array whose value is >= F.p (vectorised, most significant limb first)."""
+    ge, eq = np.zeros(a.shape[0], dtype=bool), np.ones(a.shape[0], dtype=bool)
+    for i in reversed(range(F.nlimbs)):
+        pi = np.uint64((F.p >> (64 * i)) & (2**64 - 1))
+        ge |= eq & (a[:, i] > pi)
+        eq &= a[:, i] == pi
+    return np.nonzero(ge | eq)[0]
 
 
 def pack_shares(F, shares):
@@ -40,8 +87,8 @@ def pack_shares(F, shares):
     return pack(F, flat)
 
 
-def unpack_shares(F, arr):
-    v = unpack(F, arr)
+def unpack_shares(F, arr, lenient=False):
+    v = unpack(F, arr, lenient=lenient)
     return list(zip(v[0::2], v[1::2]))
 
 
@@ -61,8 +108,8 @@ def rand_points(curve: cv.Curve, n, r, with_inf=False):
 
 
 def jac_to_affine(curve: cv.Curve, limbs):
-    """C-ABI Jacobian output -> oracle affine point."""
-    (X, Y, Z), = cv.unpack_points(curve, np.asarray(limbs), ncoords=3)
+    """C-ABI Jacobian output -> oracle affine point. Strict: every coordinate component must be < q (canonical Montgomery form)."""
+    (X, Y, Z), = cv.unpack_points(curve, np.asarray(limbs), ncoords=3, strict=True)
     return curve.to_affine((X, Y, Z))
 
 

@@ -3,6 +3,7 @@ NTT 2^20 / 2^22 (config 3) full-vector equality + 16 Horner indices, MSM 2^20 (c
 three groups, the share-vector kernels at 2^24 + 5 elements (the grid-stride branch), and the reference's BN254 Fr products
 (tests/tests/mpc/rep3.rs:286-345) through the device kernels. Everything through the C ABI; bit-exact."""
 import ctypes as C
+import hashlib
 
 import numpy as np
 import pytest
@@ -14,13 +15,6 @@ from oracle import mpc
 from tests import helpers as H
 
 pytestmark = pytest.mark.gpu
-
-
-def _uniform_limbs(rs, n):
-    """n canonical values < 2^253 (< r on every curve here), used as Montgomery encodings of uniform field elements."""
-    v = rs.randint(0, 1 << 63, size=(n, 4), dtype=np.uint64)
-    v[:, 3] >>= np.uint64(3)
-    return v
 
 
 G2_FULL_RANGE_DEFAULT = [("bn254", 20), ("bls12_381", 19)]
@@ -35,7 +29,7 @@ def test_msm_g2_full_range_points_equals_cpu_restatement(gpu, curve, logn):
     cid = H.CURVE_IDS[curve]
     n = 1 << logn
     pts = cbridge.generate_bases_progression(cid, 1, 0xD1CE + logn, n)
-    sc = _uniform_limbs(np.random.RandomState(31 + logn), n)
+    sc = H.uniform_limbs(H.FR[curve], np.random.RandomState(31 + logn), n)
     sc[:16] = 0
     bases = gpu.Bases(cid, 1, pts)
     got = bases.msm(sc, montgomery=True)
@@ -56,7 +50,7 @@ def test_msm_2p20_witness_like_scalars_equals_cpu_restatement(gpu, variant):
     n = 1 << 20
     pts = cbridge.hash_points_bn254_g1(0xFEED, n)
     rs = np.random.RandomState(99)
-    sc = _uniform_limbs(rs, n)
+    sc = H.uniform_limbs(H.FR["bn254"], rs, n)
     kind = rs.randint(0, 4, size=n)
     sc[kind == 0] = 0
     sc[kind == 1] = np.array([1, 0, 0, 0], dtype=np.uint64)
@@ -81,10 +75,10 @@ def test_msm_sliced_giant_buckets_equal_cpu_restatement(gpu, curve, group, case)
     rs = np.random.RandomState(5 + group)
     if case == "one_value":
         n, knobs = 3000, {"msm_l": 1, "msm_c": 12}
-        sc = np.repeat(_uniform_limbs(rs, 1), n, axis=0)
+        sc = np.repeat(H.uniform_limbs(H.FR[curve], rs, 1), n, axis=0)
     else:
         n, knobs = 120000, {"msm_l": 1, "msm_c": 11}
-        sc = np.repeat(_uniform_limbs(rs, 400), 300, axis=0)
+        sc = np.repeat(H.uniform_limbs(H.FR[curve], rs, 400), 300, axis=0)
     pts = cbridge.generate_bases_progression(cid, group, 0xC0DE + group, n)
     bases = gpu.Bases(cid, group, pts)
     with gpu.tuned(**knobs):
@@ -97,6 +91,8 @@ def test_msm_sliced_giant_buckets_equal_cpu_restatement(gpu, curve, group, case)
 
 NTT_FULL_DEFAULT = [(20, 1), (20, 2), (21, 1), (21, 2), (22, 1)]
 NTT_FULL_LONG = [(22, 2), (23, 1)]                          # tests/test_gpu_long.py (-m gpu_long)
+NTT_FULL_377 = [(20, 1), (20, 2), (22, 1)]                  # BLS12-377 Fr: radix-4 passes, two and three sweeps, share pairs
+NTT_FULL_377_LONG = [(21, 1), (21, 2), (22, 2)]             # tests/test_gpu_long.py (-m gpu_long)
 
 
 @pytest.mark.parametrize("curve", ["bn254", "bls12_381"])
@@ -113,7 +109,7 @@ def test_ntt_full_size_equals_cpu_restatement(gpu, curve, logn, ncomp):
     gen = ntt.roots_of_unity(F)[1][logn]                      # snarkjs root (reduction.rs:38-43 via groth16 roots)
     pg = H.pack(F, [gen])
     dom = gpu.Domain(cid, logn, pg)
-    x = _uniform_limbs(np.random.RandomState(1000 + logn + ncomp), n * ncomp)
+    x = H.uniform_limbs(F, np.random.RandomState(1000 + logn + ncomp), n * ncomp)
     coeffs = dom.ifft_in_to_out(x, ncomp=ncomp)
     want = cbridge.ntt(cid, x, logn, pg, ncomp=ncomp, dif=True)
     assert np.array_equal(coeffs.reshape(-1), want.reshape(-1))
@@ -129,6 +125,12 @@ def test_ntt_full_size_equals_cpu_restatement(gpu, curve, logn, ncomp):
         got = cbridge.eval_poly(cid, nat, wk, stride=ncomp, offset=comp)
         assert np.array_equal(got, x.reshape(n, ncomp, 4)[k, comp]), (k, comp)
     dom.free()
+
+
+@pytest.mark.parametrize("logn,ncomp", NTT_FULL_377)
+def test_ntt_full_size_bls12_377(gpu, logn, ncomp):
+    """The full-size comparison on BLS12-377 Fr: both directions bit-identical to oracle/c, the round trip and Horner spot checks."""
+    test_ntt_full_size_equals_cpu_restatement(gpu, "bls12_377", logn, ncomp)
 
 
 NTT_BEYOND_DEFAULT = [(24, 1)]
@@ -147,7 +149,7 @@ def test_ntt_beyond_2p23_equals_cpu_restatement(gpu, logn, ncomp):
     gen = ntt.roots_of_unity(F)[1][logn]
     pg = H.pack(F, [gen])
     dom = gpu.Domain(cid, logn, pg)
-    x = _uniform_limbs(np.random.RandomState(2000 + logn + ncomp), n * ncomp)
+    x = H.uniform_limbs(F, np.random.RandomState(2000 + logn + ncomp), n * ncomp)
     coeffs = dom.ifft_in_to_out(x, ncomp=ncomp)
     want = cbridge.ntt(cid, x, logn, pg, ncomp=ncomp, dif=True)
     assert np.array_equal(coeffs.reshape(-1), want.reshape(-1))
@@ -187,7 +189,7 @@ def test_msm_2p20_random_points_equals_cpu_restatement(gpu, curve, group, family
         logn, family = (20 if group == 0 else 18), "wide"
     n = 1 << logn
     pts = cbridge.hash_points_bn254_g1(0xA11CE, n) if family == "hashed" else cbridge.generate_bases_wide(cid, group, 0xB0B + group, n)
-    sc = _uniform_limbs(np.random.RandomState(7 + group), n)
+    sc = H.uniform_limbs(H.FR[curve], np.random.RandomState(7 + group), n)
     sc[:64] = 0                                                # zero scalars
     sc[64:128] = sc[128:192]                                   # repeated scalars
     bases = gpu.Bases(cid, group, pts)
@@ -208,7 +210,7 @@ def test_msm_2p20_random_points_equals_cpu_restatement(gpu, curve, group, family
     bases.free()
 
 
-SHARE_VECTOR_CURVES_LONG = ["bls12_381"]          # tests/test_gpu_long.py (-m gpu_long)
+SHARE_VECTOR_CURVES_LONG = ["bls12_381", "bls12_377"]          # tests/test_gpu_long.py (-m gpu_long)
 
 
 @pytest.mark.parametrize("curve", ["bn254"])
@@ -219,8 +221,8 @@ def test_share_vector_kernels_beyond_one_launch_width(gpu, curve):
     cid = H.CURVE_IDS[curve]
     n = (1 << 24) + 5
     rs = np.random.RandomState(99)
-    a2, b2 = _uniform_limbs(rs, 2 * n), _uniform_limbs(rs, 2 * n)
-    m = _uniform_limbs(rs, n)
+    a2, b2 = H.uniform_limbs(F, rs, 2 * n), H.uniform_limbs(F, rs, 2 * n)
+    m = H.uniform_limbs(F, rs, n)
     eq = lambda x, y: np.array_equal(np.asarray(x).reshape(-1), np.asarray(y).reshape(-1))
     assert eq(gpu.rep3_local_mul_vec(cid, a2, b2, m), cbridge.rep3_local_mul_vec(cid, a2, b2, m))
     a1, b1 = a2[:n], b2[:n]
@@ -293,7 +295,7 @@ def test_msm_fuzz_sizes_and_plans_vs_cpu_restatement(gpu, curve, group, rounds):
     for it in range(rounds):
         n = r.choice([1, 2, 63, 64, 65, 255, 256, 257, 1023, 1025, 4095, 4097, r.randrange(1, nmax), r.randrange(1, nmax)])
         off = r.randrange(0, nmax - n + 1)
-        sc = _uniform_limbs(rs, n)
+        sc = H.uniform_limbs(F, rs, n)
         k = r.randrange(0, 4)
         if k == 0 and n > 8:
             sc[: n // 3] = sc[0]                          # one giant bucket per window
@@ -327,6 +329,8 @@ def test_msm_fuzz_sizes_and_plans_vs_cpu_restatement(gpu, curve, group, rounds):
 
 NTT_VARIANTS_DEFAULT = [0, 2, 1, 0x102, 0x401, 0x100801]
 NTT_VARIANTS_LONG = [0x101, 0x201, 0x302, 0x402]   # tests/test_gpu_long.py (-m gpu_long): the other forced tile sizes
+NTT_VARIANTS_377 = [0, 2, 1]                       # BLS12-377 Fr: the default plan, radix-2 and radix-4 passes forced
+NTT_VARIANTS_377_LONG = [0x102, 0x401, 0x100801] + NTT_VARIANTS_LONG   # tests/test_gpu_long.py: the forced tile sizes on BLS12-377
 
 
 @pytest.mark.parametrize("variant", NTT_VARIANTS_DEFAULT)
@@ -336,11 +340,35 @@ def test_ntt_every_size_up_to_2p19_vs_cpu_restatement(gpu, curve, variant):
     directions, ncomp 1 and 2, against oracle/c's radix-2 NTT over the whole vector. variant 0: the default (tile size by transform
     size, radix-2 passes below 2^20 points); 2: the radix-2 pass everywhere, 1: the radix-4 pass everywhere; bits 8-10 = v force
     2^(12-v)-element tiles (tune ntt_variant), each with either pass form; 0x100801: the radix-4 pass with the unit-twiddle rounds and the
-    LDS bank swizzle switched off (the plain form both are measured against)."""
+    LDS bank swizzle switched off (the plain form both are measured against). Inputs uniform over the whole field plus the structured
+    vectors of _structured."""
     if curve == "bls12_381" and variant in (0x101, 0x302):
         pytest.skip("the forced tile sizes run on both fields with one pass form each")
     with gpu.tuned(ntt_variant=variant):
         _ntt_every_size(gpu, curve)
+
+
+@pytest.mark.parametrize("variant", NTT_VARIANTS_377)
+def test_ntt_every_size_up_to_2p19_bls12_377(gpu, variant):
+    """The every-size sweep on BLS12-377 Fr (Bls377Fr29s: two-adicity 47, the only field here whose domains' trace shift is not a
+    multiple of 32 bits)."""
+    with gpu.tuned(ntt_variant=variant):
+        _ntt_every_size(gpu, "bls12_377")
+
+
+# sha256 of oracle/c's output per (curve, logn, ncomp, input, direction): the inputs are seeded and identical for every variant, so the
+# restatement runs once per process and each variant is compared byte for byte against the digest (on a mismatch the oracle's vector is
+# recomputed for the message)
+_NTT_DIGESTS = {}
+
+
+def _structured(F, n):
+    """Raw Montgomery words of the structured inputs: all zeros, all p - 1, alternating 0 / p - 1, a constant c."""
+    pm1 = np.array([((F.p - 1) >> (64 * i)) & (2**64 - 1) for i in range(4)], dtype=np.uint64)
+    c = np.array([((F.p // 3 + 12345) >> (64 * i)) & (2**64 - 1) for i in range(4)], dtype=np.uint64)
+    alt = np.zeros((n, 4), dtype=np.uint64)
+    alt[1::2] = pm1
+    return {"zeros": np.zeros((n, 4), dtype=np.uint64), "p-1": np.tile(pm1, (n, 1)), "alt": alt, "const": np.tile(c, (n, 1))}
 
 
 def _ntt_every_size(gpu, curve):
@@ -348,13 +376,33 @@ def _ntt_every_size(gpu, curve):
     cid = H.CURVE_IDS[curve]
     rs = np.random.RandomState(77)
     roots = ntt.roots_of_unity(F)[1]
+    digest = lambda a: hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
+
+    def check(got, x, logn, pg, ncomp, dif, key):
+        k = (curve, logn, ncomp, key, dif)
+        if k not in _NTT_DIGESTS:
+            _NTT_DIGESTS[k] = digest(cbridge.ntt(cid, x, logn, pg, ncomp=ncomp, dif=dif))
+        if digest(got) != _NTT_DIGESTS[k]:
+            want = cbridge.ntt(cid, x, logn, pg, ncomp=ncomp, dif=dif).reshape(-1, 4)
+            bad = np.nonzero((np.asarray(got).reshape(-1, 4) != want).any(axis=1))[0]
+            raise AssertionError("%s 2^%d ncomp %d %s: %d words differ from oracle/c, first at %d: got %s want %s"
+                                 % (curve, logn, ncomp, "ifft" if dif else "fft", bad.size, bad[0], got.reshape(-1, 4)[bad[0]], want[bad[0]]))
+
     for logn in range(1, 20):
         n = 1 << logn
         gen = roots[logn]
         pg = H.pack(F, [gen])
         dom = gpu.Domain(cid, logn, pg)
         for ncomp in ((1, 2) if logn % 3 == 0 or logn >= 14 else (1,)):
-            x = _uniform_limbs(rs, n * ncomp)
-            assert np.array_equal(dom.ifft_in_to_out(x, ncomp=ncomp).reshape(-1), cbridge.ntt(cid, x, logn, pg, ncomp=ncomp, dif=True, threads=8).reshape(-1)), (logn, ncomp, "ifft")
-            assert np.array_equal(dom.fft_out_to_in(x, ncomp=ncomp).reshape(-1), cbridge.ntt(cid, x, logn, pg, ncomp=ncomp, dif=False, threads=8).reshape(-1)), (logn, ncomp, "fft")
+            x = H.uniform_limbs(F, rs, n * ncomp)
+            check(dom.ifft_in_to_out(x, ncomp=ncomp), x, logn, pg, ncomp, True, "uniform")
+            check(dom.fft_out_to_in(x, ncomp=ncomp), x, logn, pg, ncomp, False, "uniform")
+        for key, x in _structured(F, n).items():
+            inv = dom.ifft_in_to_out(x)
+            check(inv, x, logn, pg, 1, True, key)
+            check(dom.fft_out_to_in(x), x, logn, pg, 1, False, key)
+            if key in ("zeros", "p-1", "const"):   # closed form, independent of the output order: c at index 0, zero elsewhere
+                want = np.zeros((n, 4), dtype=np.uint64)
+                want[0] = x[0]
+                assert np.array_equal(np.asarray(inv).reshape(n, 4), want), (curve, logn, key)
         dom.free()

@@ -342,7 +342,7 @@ def test_bases_clone_and_peer_copy(gpu):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("curve,generator", [("bn254", 5), ("bls12_381", 7)])
+@pytest.mark.parametrize("curve,generator", [("bn254", 5), ("bls12_381", 7), ("bls12_377", 22)])
 @pytest.mark.parametrize("n_public,n_constraints", [(1, 2), (3, 29), (2, 3000)])
 def test_libsnark_reduction_device_matches_oracle(gpu, curve, generator, n_public, n_constraints):
     """LibSnarkReduction::witness_map_from_matrices on the device (csh_groth16_witness_map_libsnark through the host
@@ -425,17 +425,22 @@ def test_h_with_fused_tile_passes_equals_two_launch_and_unfused_forms(gpu, logn)
     the same contiguous tiles and run as ONE launch (k_ntt_pass_r4<.., PAIR>, default from 2^20 points; forced here at every size). h of
     random a, b (plain: one component; Rep3: two components + both masks) is bit-identical in the three forms: fused pair, two launches
     (tune ntt_pair = 0), and the reference's step-by-step sequence (tune h_unfused = 1) -- one-pass plans (2^2 .. 2^11), two passes, three."""
-    F = H.FR["bn254"]
+    _h_three_forms(gpu, "bn254", logn)
+
+
+@pytest.mark.parametrize("logn", [12, 16, 20])
+def test_h_with_fused_tile_passes_bls12_377(gpu, logn):
+    """The same three forms of h on BLS12-377 Fr (the field of the Penumbra proofs): one, two and three sweeps."""
+    _h_three_forms(gpu, "bls12_377", logn)
+
+
+def _h_three_forms(gpu, curve, logn):
+    F = H.FR[curve]
     n = 1 << logn
     gen = ntt.roots_of_unity(F)[1][logn]
-    dom = gpu.Domain(0, logn, H.pack(F, [gen]))
+    dom = gpu.Domain(H.CURVE_IDS[curve], logn, H.pack(F, [gen]))
     rs = np.random.RandomState(600 + logn)
-
-    def limbs(k):
-        v = rs.randint(0, 1 << 63, size=(k, 4), dtype=np.uint64)
-        v[:, 3] >>= np.uint64(3)
-        return v
-
+    limbs = lambda k: H.uniform_limbs(F, rs, k)
     shift = H.pack(F, [ntt.roots_of_unity(F)[1][logn + 1]])
     for protocol, comp in ((0, 1), (1, 2)):
         a, b = limbs(n * comp), limbs(n * comp)
@@ -444,8 +449,9 @@ def test_h_with_fused_tile_passes_equals_two_launch_and_unfused_forms(gpu, logn)
         for name, knobs in (("pair", {"ntt_pair": 1, "ntt_pair_min_log": 0}), ("two_launches", {"ntt_pair": 0}), ("unfused", {"h_unfused": 1})):
             with gpu.tuned(**knobs):
                 outs[name] = gpu.bindings.groth16_h(dom, shift, protocol, a, b, mc, mab)
-        assert np.array_equal(outs["pair"], outs["two_launches"]), (logn, protocol)
-        assert np.array_equal(outs["pair"], outs["unfused"]), (logn, protocol)
+        assert np.array_equal(outs["pair"], outs["two_launches"]), (curve, logn, protocol)
+        assert np.array_equal(outs["pair"], outs["unfused"]), (curve, logn, protocol)
+        H.assert_canonical(F, outs["pair"])
     dom.free()
 
 

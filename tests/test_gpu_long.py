@@ -42,6 +42,16 @@ def test_ntt_every_size_long(gpu, curve, variant):
     T.test_ntt_every_size_up_to_2p19_vs_cpu_restatement(gpu, curve, variant)
 
 
+@pytest.mark.parametrize("logn,ncomp", T.NTT_FULL_377_LONG)
+def test_ntt_full_size_bls12_377_long(gpu, logn, ncomp):
+    T.test_ntt_full_size_equals_cpu_restatement(gpu, "bls12_377", logn, ncomp)
+
+
+@pytest.mark.parametrize("variant", T.NTT_VARIANTS_377_LONG)
+def test_ntt_every_size_bls12_377_long(gpu, variant):
+    T.test_ntt_every_size_up_to_2p19_bls12_377(gpu, variant)
+
+
 @pytest.mark.parametrize("curve,group", M.GROUPS)
 def test_msm_fixed_base_table_layouts_long(gpu, curve, group):
     M.test_msm_fixed_base_tables(gpu, curve, group, M.TABLE_LAYOUTS_LONG)

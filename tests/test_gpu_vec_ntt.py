@@ -7,7 +7,7 @@ from oracle import mpc, ntt
 from tests import helpers as H
 
 pytestmark = pytest.mark.gpu
-CURVES = ["bn254", "bls12_381"]
+CURVES = ["bn254", "bls12_381", "bls12_377"]
 
 
 @pytest.mark.parametrize("curve", CURVES)
@@ -35,6 +35,10 @@ def test_rep3_ops(gpu, curve, n):
     lhs = [(r.randrange(F.p), r.randrange(F.p)) for _ in range(n)]
     rhs = [(r.randrange(F.p), r.randrange(F.p)) for _ in range(n)]
     masks = H.rand_elems(F, n, r)
+    top = [(F.p - 1, F.p - 1), (F.p - 2, F.p - 1), (F.p - 1, F.p - 2), (F.p - 2, 0), (0, F.p - 1)]   # the top of the field in both components
+    lhs[:len(top)] = top[:n]
+    rhs[:len(top)] = top[::-1][:n]
+    masks[:3] = [F.p - 1, F.p - 2, F.p - 1][:n]
     pl, pr, pm = H.pack_shares(F, lhs), H.pack_shares(F, rhs), H.pack(F, masks)
     assert H.unpack(F, gpu.rep3_local_mul_vec(cid, pl, pr, pm)) == mpc.rep3_local_mul_vec(F, lhs, rhs, masks)
     if n:   # an unmasked Rep3 product is refused (it leaks cross terms once opened); the product build has no override (round 6)
@@ -114,7 +118,7 @@ def test_ntt_matches_oracle(gpu, curve, logn):
 def test_ntt_default_root_is_arkworks(gpu):
     """Domain::new (reduction.rs:249): arkworks 2-adic root = GENERATOR^TRACE squared down; on BN254 it equals
     the snarkjs root (both derive from 5), on BLS12-381 (generator 7) it does not."""
-    for curve, g in [("bn254", 5), ("bls12_381", 7)]:
+    for curve, g in [("bn254", 5), ("bls12_381", 7), ("bls12_377", 22)]:
         F = H.FR[curve]
         logn = 6
         root = pow(ntt.arkworks_two_adic_root(F, g), 1 << (F.two_adicity - logn), F.p)
@@ -128,6 +132,9 @@ def test_ntt_default_root_is_arkworks(gpu):
 def test_ntt_degree_too_large(gpu):
     with pytest.raises(gpu.CoSnarksHipError, match="Polynomial Degree too large"):
         gpu.Domain(H.CURVE_IDS["bn254"], 29, None)
+    # BLS12-377 Fr: two-adicity 47, so 2^48 is refused before any allocation (by the C ABI's log_n <= 31 guard, which comes first)
+    with pytest.raises(gpu.CoSnarksHipError, match="too large"):
+        gpu.Domain(H.CURVE_IDS["bls12_377"], 48, None)
 
 
 @pytest.mark.parametrize("logn", [16, 22])

@@ -168,7 +168,7 @@ def test_c_progression_bases_match_python(curve, group):
         assert G.eq(pts[i], G.mul(G.gen, s_b + j * d_b)), i
 
 
-@pytest.mark.parametrize("curve", ["bn254", "bls12_381"])
+@pytest.mark.parametrize("curve", ["bn254", "bls12_381", "bls12_377"])
 def test_c_ntt_and_vec_ops_match_python(curve):
     F = H.FR[curve]
     cid = H.CURVE_IDS[curve]
@@ -190,6 +190,70 @@ def test_c_ntt_and_vec_ops_match_python(curve):
     assert H.unpack(F, cbridge.rep3_local_mul_vec(cid, H.pack_shares(F, a), H.pack_shares(F, b), H.pack(F, m))) == mpc.rep3_local_mul_vec(F, a, b, m)
     x, y = mpc.rep3_to_shamir_points(F, 1)
     assert H.unpack(F, cbridge.rep3_to_shamir_vec(cid, H.pack_shares(F, a), H.pack(F, [x]), H.pack(F, [y]))) == mpc.rep3_to_shamir_vec(F, a, 1)
+    # the plain vector ops, the table product (one and two components), the linear combination and Horner, edge values included
+    u = (H.edge_elems(F) + H.rand_elems(F, n, r))[:n]
+    u = [e % F.p for e in u]
+    v = H.rand_elems(F, n, r)[::-1]
+    v[:3] = [F.p - 1, F.p - 2, 0]
+    pu, pv = H.pack(F, u), H.pack(F, v)
+    assert H.unpack(F, cbridge.vec_mul(cid, pu, pv)) == [s * t % F.p for s, t in zip(u, v)]
+    assert H.unpack(F, cbridge.vec_add(cid, pu, pv)) == [(s + t) % F.p for s, t in zip(u, v)]
+    assert H.unpack(F, cbridge.vec_sub(cid, pu, pv)) == [(s - t) % F.p for s, t in zip(u, v)]
+    assert H.unpack(F, cbridge.vec_mul_table(cid, pu, pv)) == [s * t % F.p for s, t in zip(u, v)]
+    assert H.unpack_shares(F, cbridge.vec_mul_table(cid, H.pack_shares(F, a), pv, ncomp=2)) == [(s * t % F.p, w * t % F.p) for (s, w), t in zip(a, v)]
+    co = [3, F.p - 2, r.randrange(F.p)]
+    assert H.unpack(F, cbridge.lincomb(cid, [pu, pv, H.pack(F, m)], H.pack(F, co))) == \
+        [(co[0] * s + co[1] * t + co[2] * k) % F.p for s, t, k in zip(u, v, m)]
+    z = r.randrange(F.p)
+    assert H.unpack(F, cbridge.eval_poly(cid, pu, H.pack(F, [z]))) == [ntt.eval_poly_at(F, u, z)]
+
+
+@pytest.mark.parametrize("cid", [2, 7, -1])
+def test_c_fr_ops_refuse_unknown_curve_ids(cid):
+    """Only 0 BN254, 1 BLS12-381 and 3 BLS12-377 have a scalar field in oracle/c; any other id (2 is Grumpkin, whose Fr is BN254's Fq)
+    is refused by every Fr entry point instead of silently computing in some other field."""
+    F = fl.BN254_FR
+    one, two = H.pack(F, [1] * 4), H.pack(F, [2] * 4)
+    calls = [lambda: cbridge.ntt(cid, one, 2, H.pack(F, [1])), lambda: cbridge.vec_mul(cid, one, two), lambda: cbridge.vec_add(cid, one, two),
+             lambda: cbridge.vec_sub(cid, one, two), lambda: cbridge.vec_mul_table(cid, one, two), lambda: cbridge.eval_poly(cid, one, one[:4]),
+             lambda: cbridge.lincomb(cid, [one, two], H.pack(F, [1, 1])), lambda: cbridge.coset_table(cid, one[:4], 2),
+             lambda: cbridge.rep3_local_mul_vec(cid, two, two, one[:8]), lambda: cbridge.rep3_to_shamir_vec(cid, two, one[:4], one[:4])]
+    for f in calls:
+        with pytest.raises(cbridge.OracleError, match="refused"):
+            f()
+
+
+@pytest.mark.parametrize("curve", ["bn254", "bls12_381", "bls12_377"])
+def test_strict_decode_rejects_non_canonical_words(curve):
+    """tests/helpers.py decodes strictly: a raw word value >= p (e.g. a lazy x + p a kernel forgot to reduce) is an error naming the
+    index and the value, in Montgomery and canonical mode, for single values and share pairs; p - 1 is accepted. The Jacobian decode
+    refuses a coordinate component >= q the same way."""
+    F = H.FR[curve]
+    raw = lambda vals: fl.pack(F, vals, mont=False).reshape(-1)        # the words exactly as given (values < 2^256, no reduction)
+    words = lambda vals: np.array([[(v >> (64 * i)) & (2**64 - 1) for i in range(4)] for v in vals], dtype=np.uint64).reshape(-1)
+    for mont in (True, False):
+        assert H.unpack(F, raw([F.p - 1]), mont=mont) == [F.from_mont(F.p - 1) if mont else F.p - 1]
+        for bad in (F.p, F.p + 5):
+            with pytest.raises(AssertionError, match="index 2: raw word value %#x" % bad):
+                H.unpack(F, words([0, F.p - 1, bad, 1]), mont=mont)
+            assert H.unpack(F, words([bad]), mont=mont, lenient=True) == [F.from_mont(bad) if mont else bad]   # decoded as is
+    with pytest.raises(AssertionError, match="index 3"):
+        H.unpack_shares(F, words([1, 2, F.p - 1, F.p + 5]))
+    assert H.unpack_shares(F, words([1, 2, F.p - 1, F.p - 2])) == [(F.from_mont(1), F.from_mont(2)), (F.from_mont(F.p - 1), F.from_mont(F.p - 2))]
+    G = cv.CURVES[curve][0]
+    q = G.F.p
+    good = cv.pack_points(G, [G.gen]).reshape(-1)
+    jac = np.concatenate([good, fl.pack(G.F, [1]).reshape(-1)])
+    assert G.eq(H.jac_to_affine(G, jac), G.gen)
+    for coord in range(3):
+        bad = jac.copy()
+        nl = G.F.nlimbs
+        v = int.from_bytes(bad[coord * nl:(coord + 1) * nl].tobytes(), "little") + q
+        if v >= 1 << (64 * nl):
+            continue
+        bad[coord * nl:(coord + 1) * nl] = np.frombuffer(v.to_bytes(8 * nl, "little"), dtype="<u8")
+        with pytest.raises(AssertionError, match="coordinate %d" % coord):
+            H.jac_to_affine(G, bad)
 
 
 def test_c_generated_bases_closed_form():
