@@ -61,22 +61,36 @@ struct Fp2Pair {
     for (int i = 0; i < NL; ++i) r.l[i] *= sgn;
     return r;
   }
+  // Products whose first operand is a hi_signed() value. With NR = 5 that operand is five times a normalised one BY DESIGN, so the
+  // limb-bound contract is stated by the routines Fp2S uses for its scaled() operand (LIM_SCALED = 5 LIM1; same multiply-adds as
+  // col_mul / mac_wide). Column sums, 14 x 28-bit limbs, every operand normalised: mul / sqr / sqr_sub (1 + 5) 14 2^56 of products
+  // + 14 2^56 of the reduction = 98 2^56 < 2^63; mul_sub: the first pair (<= 84 2^56) goes through compress_wide (columns back below
+  // 2^28), then 84 2^56 of the second pair + 14 2^56 of the reduction. hi_signed() of an un-normalised two-term sum (which col_mul
+  // accepts as a first operand) does NOT fit and is reported as such.
+  __device__ __forceinline__ static int64_t col_mul_hi(const LF& ahi, const LF& b, int k, int64_t acc) {
+    if constexpr (NR == 1) return LF::col_mul(ahi, b, k, acc);
+    else return LF::col_mul_scaled(ahi, b, k, acc);
+  }
+  __device__ __forceinline__ static void mac_wide_hi(typename LF::Wide& w, const LF& ahi, const LF& b, bool negate) {
+    if constexpr (NR == 1) LF::mac_wide(w, ahi, b, negate);
+    else LF::mac_wide_scaled(w, negate ? LF::neg(ahi) : ahi, b);
+  }
   // role 0: a0 b0 - a1 b1, role 1: a0 b1 + a1 b0 (unreduced)
   __device__ __forceinline__ static typename LF::Wide mul_wide(const Fp2Pair& a, const Fp2Pair& b) {
     typename LF::Wide w = LF::mul_wide(quad_perm<PairLo::value>(a.v), b.v);
-    LF::mac_wide(w, hi_signed(a.v), quad_perm<PairSwap::value>(b.v), false);
+    mac_wide_hi(w, hi_signed(a.v), quad_perm<PairSwap::value>(b.v), false);
     return w;
   }
 #if CSH_REDUCE_SCAN
   __device__ __forceinline__ static Fp2Pair mul(const Fp2Pair& a, const Fp2Pair& b) {
     const LF alo = quad_perm<PairLo::value>(a.v), ahi = hi_signed(a.v), bsw = quad_perm<PairSwap::value>(b.v);
-    return {LF::reduce_scan([&](int k, int64_t acc) CSH_LAMBDA_INLINE { return LF::col_mul(ahi, bsw, k, LF::col_mul(alo, b.v, k, acc)); })};
+    return {LF::reduce_scan([&](int k, int64_t acc) CSH_LAMBDA_INLINE { return col_mul_hi(ahi, bsw, k, LF::col_mul(alo, b.v, k, acc)); })};
   }
   __device__ __forceinline__ static Fp2Pair sqr(const Fp2Pair& a) { return mul(a, a); }
   __device__ __forceinline__ static Fp2Pair sqr_sub(const Fp2Pair& a, const Fp2Pair& s) {
     const LF alo = quad_perm<PairLo::value>(a.v), ahi = hi_signed(a.v), bsw = quad_perm<PairSwap::value>(a.v);
     const int32_t m1 = LF::opaque_minus_one();
-    return {LF::reduce_scan([&](int k, int64_t acc) CSH_LAMBDA_INLINE { return LF::col_sub_hi(s.v, m1, k, LF::col_mul(ahi, bsw, k, LF::col_mul(alo, a.v, k, acc))); })};
+    return {LF::reduce_scan([&](int k, int64_t acc) CSH_LAMBDA_INLINE { return LF::col_sub_hi(s.v, m1, k, col_mul_hi(ahi, bsw, k, LF::col_mul(alo, a.v, k, acc))); })};
   }
 #else
   __device__ __forceinline__ static Fp2Pair mul(const Fp2Pair& a, const Fp2Pair& b) { return {LF::reduce(mul_wide(a, b))}; }
@@ -90,18 +104,18 @@ struct Fp2Pair {
       const LF alo = quad_perm<PairLo::value>(a.v), ahi = hi_signed(a.v), bsw = quad_perm<PairSwap::value>(b.v);
       const LF nclo = LF::neg(quad_perm<PairLo::value>(c.v)), nchi = LF::neg(hi_signed(c.v)), dsw = quad_perm<PairSwap::value>(d.v);
       return {LF::reduce_scan([&](int k, int64_t acc) CSH_LAMBDA_INLINE {
-        return LF::col_mul(nchi, dsw, k, LF::col_mul(nclo, d.v, k, LF::col_mul(ahi, bsw, k, LF::col_mul(alo, b.v, k, acc))));
+        return col_mul_hi(nchi, dsw, k, LF::col_mul(nclo, d.v, k, col_mul_hi(ahi, bsw, k, LF::col_mul(alo, b.v, k, acc))));
       })};
 #endif
       typename LF::Wide w = mul_wide(a, b);
       LF::mac_wide(w, quad_perm<PairLo::value>(c.v), d.v, true);
-      LF::mac_wide(w, hi_signed(c.v), quad_perm<PairSwap::value>(d.v), true);
+      mac_wide_hi(w, hi_signed(c.v), quad_perm<PairSwap::value>(d.v), true);
       return {LF::reduce(w)};
     } else {
       typename LF::Wide w = mul_wide(a, b);  // two products, then a carry sweep so that the next two fit the same columns
       LF::compress_wide(w);
       typename LF::Wide v = LF::mul_wide(LF::neg(quad_perm<PairLo::value>(c.v)), d.v);
-      LF::mac_wide(v, hi_signed(c.v), quad_perm<PairSwap::value>(d.v), true);
+      mac_wide_hi(v, hi_signed(c.v), quad_perm<PairSwap::value>(d.v), true);
       LF::add_wide(w, v);
       return {LF::reduce(w)};
     }

@@ -165,10 +165,31 @@ using Fq29 = FpLazy<Bn254Fq29Params, Bn254Fq>;
 // (-p/32, p + p/32) whose limbs 0..NL-2 are in [0, 2^B) and whose top limb carries the sign.
 // Contract: |limb| of mul operands <= 2^B + 2 for both, or <= 2^(B+1) for one of them; operand values within
 // (-8p, 8p). `normalized()` (one parallel signed carry step) restores |limb| <= 2^B + 1 after 2-3 term sums.
-// Host-only contract checks (enabled by the self-test translation unit): every product routine verifies the
+// Contract checks (enabled by the self-test translation units only): every product routine verifies the
 // limb magnitudes its 63-bit column bound was derived for, so a caller that forgets a normalized() fails loudly
 // in `pytest -m "not gpu"` instead of producing a one-in-10^5 wrong bucket on the device.
-#if defined(CSH_CHECK_BOUNDS) && !defined(__HIP_DEVICE_COMPILE__)
+//   CSH_CHECK_BOUNDS (selftest.hip): host code aborts with a message.
+//   CSH_CHECK_BOUNDS_DEVICE (selftest_dev.hip): device code RECORDS and goes on -- the lane-distributed arithmetic
+//   (curve_quad.hpp, curve_pair.hpp) exists on the device only. g_bound_record[0] counts the violating limbs, [1] keeps the
+//   largest offender as |limb| << 16 | site (site = the line of this file that states the violated bound); plain vector
+//   atomics, no trap, no print. The entry points of selftest_dev.hip copy the record back and clear it.
+// Everywhere else the macro is empty.
+#if defined(CSH_CHECK_BOUNDS_DEVICE)
+__device__ unsigned long long g_bound_record[2];
+#endif
+#if defined(CSH_CHECK_BOUNDS_DEVICE) && defined(__HIP_DEVICE_COMPILE__)
+#define CSH_LIMB_BOUND(x, bound, what)                                                        \
+  do {                                                                                        \
+    for (int i__ = 0; i__ < NL; ++i__) {                                                      \
+      const int64_t v__ = (x).l[i__];                                                         \
+      const int64_t a__ = v__ < 0 ? -v__ : v__;                                               \
+      if (a__ > (int64_t)(bound)) {                                                           \
+        atomicAdd(&g_bound_record[0], 1ull);                                                  \
+        atomicMax(&g_bound_record[1], ((unsigned long long)a__ << 16) | (unsigned long long)(__LINE__ & 0xffff)); \
+      }                                                                                       \
+    }                                                                                         \
+  } while (0)
+#elif defined(CSH_CHECK_BOUNDS) && !defined(__HIP_DEVICE_COMPILE__)
 #include <stdio.h>
 #include <stdlib.h>
 #define CSH_LIMB_BOUND(x, bound, what)                                                        \
@@ -184,6 +205,8 @@ using Fq29 = FpLazy<Bn254Fq29Params, Bn254Fq>;
 #else
 #define CSH_LIMB_BOUND(x, bound, what) do { } while (0)
 #endif
+// the same for the per-column routines of the product-scanning form: a product visits them 2 NL times with the same operands
+#define CSH_LIMB_BOUND_COL(k, x, bound, what) do { if ((k) == 0) CSH_LIMB_BOUND(x, bound, what); } while (0)
 
 // the column-term lambdas of reduce_scan must be inlined whatever their size (the column index has to be a constant)
 #define CSH_LAMBDA_INLINE __attribute__((always_inline))
@@ -570,8 +593,8 @@ struct FpS {
   static constexpr int64_t LIM_SCALED = 5 * LIM1;  // scaled() output
   // column products with a scaled() first operand (its bound is checked as such; the caller accounts for the column sum)
   CSH_HD static int64_t col_mul_scaled(const FpS& a, const FpS& b, int k, int64_t acc) {
-    CSH_LIMB_BOUND(a, LIM_SCALED, "col_mul_scaled(a)");
-    CSH_LIMB_BOUND(b, LIM1, "col_mul_scaled(b)");
+    CSH_LIMB_BOUND_COL(k, a, LIM_SCALED, "col_mul_scaled(a)");
+    CSH_LIMB_BOUND_COL(k, b, LIM1, "col_mul_scaled(b)");
 #pragma unroll
     for (int i = 0; i < NL; ++i)
       if (k - i >= 0 && k - i < NL) acc = mad_pinned(a.l[i], b.l[k - i], acc);
@@ -579,8 +602,8 @@ struct FpS {
   }
   // - s b^2 for bs = s b (scaled), nb = -b, nb2 = -2 b
   CSH_HD static int64_t col_nsqr_scaled(const FpS& bs, const FpS& nb, const FpS& nb2, int k, int64_t acc) {
-    CSH_LIMB_BOUND(bs, LIM_SCALED, "col_nsqr_scaled(bs)");
-    CSH_LIMB_BOUND(nb, LIM1, "col_nsqr_scaled(nb)");
+    CSH_LIMB_BOUND_COL(k, bs, LIM_SCALED, "col_nsqr_scaled(bs)");
+    CSH_LIMB_BOUND_COL(k, nb, LIM1, "col_nsqr_scaled(nb)");
 #pragma unroll
     for (int i = 0; i < NL; ++i) {
       const int j = k - i;
@@ -600,8 +623,8 @@ struct FpS {
   }
   // operand products of column k
   CSH_HD static int64_t col_mul(const FpS& a, const FpS& b, int k, int64_t acc) {
-    CSH_LIMB_BOUND(a, LIM2, "col_mul(a)");
-    CSH_LIMB_BOUND(b, LIM1, "col_mul(b)");
+    CSH_LIMB_BOUND_COL(k, a, LIM2, "col_mul(a)");
+    CSH_LIMB_BOUND_COL(k, b, LIM1, "col_mul(b)");
 #pragma unroll
     for (int i = 0; i < NL; ++i)
       if (k - i >= 0 && k - i < NL) acc = mad_pinned(a.l[i], b.l[k - i], acc);
@@ -609,7 +632,7 @@ struct FpS {
   }
   // a^2: squares + doubled cross terms (a2 = 2 a)
   CSH_HD static int64_t col_sqr(const FpS& a, const FpS& a2, int k, int64_t acc) {
-    CSH_LIMB_BOUND(a, LIM1, "col_sqr");
+    CSH_LIMB_BOUND_COL(k, a, LIM1, "col_sqr");
 #pragma unroll
     for (int i = 0; i < NL; ++i) {
       const int j = k - i;
@@ -620,7 +643,7 @@ struct FpS {
   }
   // - b^2 (nb = -b, nb2 = -2 b)
   CSH_HD static int64_t col_nsqr(const FpS& b, const FpS& nb, const FpS& nb2, int k, int64_t acc) {
-    CSH_LIMB_BOUND(b, LIM1, "col_nsqr");
+    CSH_LIMB_BOUND_COL(k, b, LIM1, "col_nsqr");
 #pragma unroll
     for (int i = 0; i < NL; ++i) {
       const int j = k - i;

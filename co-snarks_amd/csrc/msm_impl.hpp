@@ -1386,6 +1386,70 @@ int repack_bases_t(Bases* B, hipStream_t st) {
   return CSH_OK;
 }
 
+// Test hook (selftest_dev.hip): the window reduction and the fold tree as bucket_group launches them, on ONE window whose dense
+// bucket array (NB + 1 LazyPt slots, host memory) the caller built. form: 0 lane-serial, 1 quad, 2 pair (G2 only). Instantiated
+// with the kernels it launches (CSH_MSM_INSTANTIATE), so no k_msm_* kernel gets a second home. win_out_host: one XYZZ<Fq>.
+template <class Cfg>
+int msm_tail_selftest_t(const void* dense_host, uint32_t NB, uint32_t S, int form, void* win_out_host) {
+  using Fq = typename Cfg::Fq;
+  CSH_REQUIRE(dense_host && win_out_host && NB >= 1 && S >= 1 && NB <= (1u << 21) && S <= (1u << 16), "msm_tail_selftest: bad arguments");
+  CSH_REQUIRE(form == 0 || form == 1 || (form == 2 && Cfg::PAIR), "msm_tail_selftest: unknown form");
+  CSH_TRY(ensure_device());
+  MsmParams p{};
+  p.NB = NB;
+  p.S = S;
+  p.W = 1;
+  p.wide = 1;
+  const uint32_t fold_n1 = (S + 127) / 128;
+  struct Mem {
+    void* p = nullptr;
+    ~Mem() {
+      if (p) (void)hipFree(p);
+    }
+  } m_dense, m_seg, m_fa, m_fb, m_win;
+  CSH_HIP(hipMalloc(&m_dense.p, ((size_t)NB + 1) * sizeof(LazyPt<Cfg>)));
+  CSH_HIP(hipMalloc(&m_seg.p, (size_t)S * sizeof(LazyPt<Cfg>)));
+  CSH_HIP(hipMalloc(&m_fa.p, (size_t)fold_n1 * sizeof(LazyPt<Cfg>)));
+  CSH_HIP(hipMalloc(&m_fb.p, (size_t)fold_n1 * sizeof(LazyPt<Cfg>)));
+  CSH_HIP(hipMalloc(&m_win.p, sizeof(XYZZ<Fq>)));
+  CSH_HIP(hipMemcpy(m_dense.p, dense_host, ((size_t)NB + 1) * sizeof(LazyPt<Cfg>), hipMemcpyHostToDevice));
+  const LazyPt<Cfg>* dense = reinterpret_cast<const LazyPt<Cfg>*>(m_dense.p);
+  LazyPt<Cfg>* segres = reinterpret_cast<LazyPt<Cfg>*>(m_seg.p);
+  LazyPt<Cfg>* fold_a = reinterpret_cast<LazyPt<Cfg>*>(m_fa.p);
+  LazyPt<Cfg>* fold_b = reinterpret_cast<LazyPt<Cfg>*>(m_fb.p);
+  XYZZ<Fq>* win_out = reinterpret_cast<XYZZ<Fq>*>(m_win.p);
+  const hipStream_t st = nullptr;
+  const uint32_t* no_start = nullptr;
+  const LazyPt<Cfg>* no_partial = nullptr;
+  if (form == 1) {
+    hipLaunchKernelGGL((k_msm_reduce<Cfg, false>), dim3((S + 63) / 64, 1), dim3(256), 0, st, p, dense, segres, no_start, no_partial);
+  } else if (form == 2) {
+    if constexpr (Cfg::PAIR)
+      hipLaunchKernelGGL((k_msm_reduce_pair<Cfg, false>), dim3((S + RED_BLK / 2 - 1) / (RED_BLK / 2), 1), dim3(RED_BLK), 0, st, p, dense, segres, no_start, no_partial);
+  } else {
+    hipLaunchKernelGGL(k_msm_reduce_serial<Cfg>, dim3((S + RED_BLK - 1) / RED_BLK, 1), dim3(RED_BLK), 0, st, p, dense, segres);
+  }
+  CSH_HIP(hipGetLastError());
+  const LazyPt<Cfg>* cur = segres;
+  uint32_t cur_n = S, cur_stride = S;
+  LazyPt<Cfg>* nxt = fold_a;
+  bool exported = false;
+  while (cur_n > 1) {
+    const uint32_t out_n = (cur_n + 127) / 128;
+    exported = out_n == 1;
+    hipLaunchKernelGGL(k_msm_fold_tree<Cfg>, dim3(out_n, 1), dim3(256), 0, st, cur, cur_stride, cur_n, nxt, fold_n1, exported ? win_out : (XYZZ<Fq>*)nullptr);
+    cur = nxt;
+    cur_n = out_n;
+    cur_stride = fold_n1;
+    nxt = nxt == fold_a ? fold_b : fold_a;
+  }
+  if (!exported) hipLaunchKernelGGL(k_msm_gather_windows<Cfg>, dim3(1), dim3(MAX_WINDOWS), 0, st, cur, cur_stride, 1, win_out);
+  CSH_HIP(hipGetLastError());
+  CSH_HIP(hipDeviceSynchronize());
+  CSH_HIP(hipMemcpy(win_out_host, win_out, sizeof(XYZZ<Fq>), hipMemcpyDeviceToHost));
+  return CSH_OK;
+}
+
 // The accumulate kernels are instantiated in their own translation units (msm_accum_*.hip, which define CSH_PIN_MADS 3: the
 // product-scanning Montgomery multiplication with its multiply-add order pinned); the per-configuration units below see them
 // as explicit-instantiation declarations, so their own copy of the field code stays unpinned for the tail kernels.
@@ -1402,6 +1466,7 @@ int repack_bases_t(Bases* B, hipStream_t st) {
   KW template int msm_partial_t<CFG>(const Bases*, size_t, size_t, const uint64_t*, int, void*, hipStream_t, bool);                 \
   KW template int fold_partials_t<CFG>(const void*, size_t, void*);                                                             \
   KW template int repack_bases_t<CFG>(Bases*, hipStream_t);                                                                     \
+  KW template int msm_tail_selftest_t<CFG>(const void*, uint32_t, uint32_t, int, void*);                                        \
   KW template size_t msm_bucket_bytes<CFG>(const MsmParams*);                                                                   \
   KW template int msm_bucket_stage<CFG>(const void*, const MsmParams*, const SortOut*, hipStream_t, Arena*, void*, hipEvent_t*);          \
   KW template int precompute_table_t<CFG>(Bases*, int, int, hipStream_t);                                                            \

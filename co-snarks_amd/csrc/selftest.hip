@@ -264,7 +264,45 @@ static int fp2s_raw_t(int op, const int32_t* limbs, uint64_t* out) {
   memcpy(out, &f, sizeof f);
   return CSH_OK;
 }
+
+// The two halves of the lazy field's zero test, separately, on RAW signed limbs (n elements of NL int32 each; 2 NL for an Fp2S type):
+// flags[i] = maybe_zero() | is_zero_slow() << 1 | is_zero() << 2. maybe_zero() looks at limb 0 only; the slow test decides.
+template <class L>
+static void zero_flags_one(const int32_t* limbs, L& v) {
+  for (int i = 0; i < L::NL; ++i) v.l[i] = limbs[i];
+}
+template <class LF, class F2>
+static void zero_flags_one(const int32_t* limbs, Fp2S<LF, F2>& v) {
+  for (int i = 0; i < LF::NL; ++i) {
+    v.c0.l[i] = limbs[i];
+    v.c1.l[i] = limbs[LF::NL + i];
+  }
+}
+template <class L>
+static int zero_flags_t(const int32_t* limbs, size_t n, uint8_t* flags) {
+  constexpr size_t words = sizeof(L) / sizeof(int32_t);
+  for (size_t i = 0; i < n; ++i) {
+    L v;
+    zero_flags_one(limbs + i * words, v);
+    flags[i] = (uint8_t)((v.maybe_zero() ? 1 : 0) | (v.is_zero_slow() ? 2 : 0) | (v.is_zero() ? 4 : 0));
+  }
+  return CSH_OK;
+}
 extern "C" {
+
+// type: 0 Fq29s, 1 Fq28s, 2 Fr29s, 3 Fq28s377, 4 Fq29s2, 5 Fq28s2, 6 Fq28s377x2
+int csh_selftest_zero_flags(int type, const int32_t* limbs, size_t n, uint8_t* flags) {
+  switch (type) {
+    case 0: return zero_flags_t<Fq29s>(limbs, n, flags);
+    case 1: return zero_flags_t<Fq28s>(limbs, n, flags);
+    case 2: return zero_flags_t<Fr29s>(limbs, n, flags);
+    case 3: return zero_flags_t<Fq28s377>(limbs, n, flags);
+    case 4: return zero_flags_t<Fq29s2>(limbs, n, flags);
+    case 5: return zero_flags_t<Fq28s2>(limbs, n, flags);
+    case 6: return zero_flags_t<Fq28s377x2>(limbs, n, flags);
+    default: return CSH_ERR_INVALID;
+  }
+}
 
 int csh_selftest_lazy_chain_dev(int curve, int group, const void* affine_pts, size_t n, size_t len, size_t nthreads, size_t host_samples,
                                 int* mismatches) {

@@ -1,0 +1,418 @@
+// Device-executed self-test hooks for the arithmetic that exists on the device only: curve_quad.hpp (one XYZZ point over a DPP
+// quad) and curve_pair.hpp (one Fp2 value over a lane pair), plus a launcher of the real window-reduction and fold-tree kernels
+// on bucket arrays the caller chooses. The kernels here are compiled with the device form of the limb-bound contract
+// (field29.hpp, CSH_CHECK_BOUNDS_DEVICE): a violated operand bound is counted in g_bound_record, never trapped; every entry
+// point hands the record back and clears it. Test infrastructure; not declared in include/cosnarks_hip.h.
+#define CSH_CHECK_BOUNDS_DEVICE 1
+#include <string.h>
+
+#include <vector>
+
+#include "msm_impl.hpp"
+
+using namespace csh;
+
+namespace csh {
+// the tail launchers live with the kernels they launch (msm_inst_*.hip): no second instantiation of a k_msm_* kernel here
+#define CSH_ST_TAIL_DECL(CFG) extern template int msm_tail_selftest_t<CFG>(const void*, uint32_t, uint32_t, int, void*);
+CSH_ST_TAIL_DECL(Bn254G1Cfg)
+CSH_ST_TAIL_DECL(Bn254G2Cfg)
+CSH_ST_TAIL_DECL(Bls381G1Cfg)
+CSH_ST_TAIL_DECL(Bls381G2Cfg)
+CSH_ST_TAIL_DECL(GrumpkinG1Cfg)
+CSH_ST_TAIL_DECL(Bls377G1Cfg)
+CSH_ST_TAIL_DECL(Bls377G2Cfg)
+}  // namespace csh
+
+namespace {
+
+struct DevMem {
+  void* p = nullptr;
+  ~DevMem() {
+    if (p) (void)hipFree(p);
+  }
+  int alloc(size_t bytes) {
+    CSH_HIP(hipMalloc(&p, bytes ? bytes : 1));
+    return CSH_OK;
+  }
+  template <class T>
+  T* as() { return reinterpret_cast<T*>(p); }
+};
+
+int bound_record_clear() {
+  const unsigned long long z[2] = {0, 0};
+  CSH_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_bound_record), z, sizeof z));
+  return CSH_OK;
+}
+// rec[0] = violating limbs, rec[1] = largest |limb|, rec[2] = its site (line of field29.hpp); the device record is cleared
+int bound_record_take(uint64_t rec[3]) {
+  unsigned long long r[2];
+  CSH_HIP(hipDeviceSynchronize());
+  CSH_HIP(hipMemcpyFromSymbol(r, HIP_SYMBOL(g_bound_record), sizeof r));
+  rec[0] = r[0];
+  rec[1] = r[1] >> 16;
+  rec[2] = r[1] & 0xffff;
+  return bound_record_clear();
+}
+
+// ---- positive control of the recorder: a raw-limb product whose first operand has every limb at 2^(B+2) -------------------
+template <class LF>
+__global__ void k_st_bound_control(int64_t* sink) {
+  LF a, b;
+  for (int i = 0; i < LF::NL; ++i) {
+    a.l[i] = (int32_t)(1u << (LF::B + 2));
+    b.l[i] = 3;
+  }
+  const typename LF::Wide w = LF::mul_wide(a, b);  // integer arithmetic on chosen inputs: 3 * 2^(B+2) * NL per column at most
+  int64_t s = 0;
+  for (int k = 0; k < 2 * LF::NL; ++k) s += w.t[k];
+  sink[threadIdx.x] = s;
+}
+template <class LF>
+int bound_control_t(uint64_t rec[3]) {
+  DevMem sink;
+  CSH_TRY(sink.alloc(64 * sizeof(int64_t)));
+  CSH_TRY(bound_record_clear());
+  hipLaunchKernelGGL(k_st_bound_control<LF>, dim3(1), dim3(64), 0, 0, sink.as<int64_t>());
+  CSH_HIP(hipGetLastError());
+  return bound_record_take(rec);
+}
+
+// ---- Fp2Pair products on raw limbs ---------------------------------------------------------------------------------------
+// limbs: [npairs][4 elements][2 components][NL] int32; pair j = lanes 2j, 2j + 1. op 0: a b, 1: a^2, 2: a^2 - b, 3: a b - c d.
+template <class LP, class F32>
+__global__ __launch_bounds__(256) void k_st_fp2pair_raw(int op, const int32_t* __restrict__ limbs, uint32_t npairs, F32* out) {
+  constexpr int NL = LP::NL;
+  const uint32_t t = blockIdx.x * 256 + threadIdx.x, j = t >> 1;
+  const int role = pair_role();
+  if (j >= npairs) return;  // pair-uniform
+  LP v[4];
+  for (int e = 0; e < 4; ++e)
+    for (int i = 0; i < NL; ++i) v[e].v.l[i] = limbs[(((size_t)j * 4 + e) * 2 + role) * NL + i];
+  LP r;
+  if (op == 0) r = LP::mul(v[0], v[1]);
+  else if (op == 1) r = LP::sqr(v[0]);
+  else if (op == 2) r = LP::sqr_sub(v[0], v[1]);
+  else r = LP::mul_sub(v[0], v[1], v[2], v[3]);
+  out[2 * (size_t)j + role] = r.v.to_fp();
+}
+template <class LP, class F32>
+int fp2pair_raw_t(int op, const int32_t* limbs, size_t npairs, uint64_t* out, uint64_t rec[3]) {
+  const size_t in_bytes = npairs * 8 * LP::NL * sizeof(int32_t), out_bytes = npairs * 2 * sizeof(F32);
+  DevMem din, dout;
+  CSH_TRY(din.alloc(in_bytes));
+  CSH_TRY(dout.alloc(out_bytes));
+  CSH_HIP(hipMemcpy(din.p, limbs, in_bytes, hipMemcpyHostToDevice));
+  CSH_TRY(bound_record_clear());
+  hipLaunchKernelGGL((k_st_fp2pair_raw<LP, F32>), dim3((unsigned)((2 * npairs + 255) / 256)), dim3(256), 0, 0, op, din.as<int32_t>(), (uint32_t)npairs,
+                     dout.as<F32>());
+  CSH_HIP(hipGetLastError());
+  CSH_TRY(bound_record_take(rec));
+  CSH_HIP(hipMemcpy(out, dout.p, out_bytes, hipMemcpyDeviceToHost));
+  return CSH_OK;
+}
+
+// ---- the two zero tests of Fp2Pair on raw limbs --------------------------------------------------------------------------
+// limbs: [npairs][2 components][NL]; flags[j] = maybe_zero() | is_zero_slow() << 1 | is_zero() << 2
+template <class LP>
+__global__ __launch_bounds__(256) void k_st_fp2pair_zero(const int32_t* __restrict__ limbs, uint32_t npairs, uint8_t* flags) {
+  constexpr int NL = LP::NL;
+  const uint32_t t = blockIdx.x * 256 + threadIdx.x, j = t >> 1;
+  const int role = pair_role();
+  if (j >= npairs) return;
+  LP v;
+  for (int i = 0; i < NL; ++i) v.v.l[i] = limbs[((size_t)j * 2 + role) * NL + i];
+  const bool m = v.maybe_zero(), s = v.is_zero_slow(), z = v.is_zero();
+  if (role == 0) flags[j] = (uint8_t)((m ? 1 : 0) | (s ? 2 : 0) | (z ? 4 : 0));
+}
+template <class LP>
+int fp2pair_zero_t(const int32_t* limbs, size_t npairs, uint8_t* flags, uint64_t rec[3]) {
+  const size_t in_bytes = npairs * 2 * LP::NL * sizeof(int32_t);
+  DevMem din, dout;
+  CSH_TRY(din.alloc(in_bytes));
+  CSH_TRY(dout.alloc(npairs));
+  CSH_HIP(hipMemcpy(din.p, limbs, in_bytes, hipMemcpyHostToDevice));
+  CSH_TRY(bound_record_clear());
+  hipLaunchKernelGGL(k_st_fp2pair_zero<LP>, dim3((unsigned)((2 * npairs + 255) / 256)), dim3(256), 0, 0, din.as<int32_t>(), (uint32_t)npairs, dout.as<uint8_t>());
+  CSH_HIP(hipGetLastError());
+  CSH_TRY(bound_record_take(rec));
+  CSH_HIP(hipMemcpy(flags, dout.p, npairs, hipMemcpyDeviceToHost));
+  return CSH_OK;
+}
+
+// ---- stored points, built on the host with the lane-serial templates ------------------------------------------------------
+// slot s = the lazy_madd chain over pts[off[s] .. off[s + 1]) (negated where neg[i]): what the accumulate kernel leaves in a partial
+// slot -- non-trivial zz / zzz from the second point on, `empty` with stale limbs after a cancellation, inf() for an empty range.
+template <class L, class Fq>
+void build_slots(const Affine<Fq>* pts, const uint8_t* neg, const uint32_t* off, size_t nslots, XYZZLazy<L>* out) {
+  for (size_t s = 0; s < nslots; ++s) {
+    XYZZLazy<L> acc = XYZZLazy<L>::inf();
+    for (uint32_t i = off[s]; i < off[s + 1]; ++i) {
+      Affine<Fq> p;
+      memcpy(&p, pts + i, sizeof p);
+      if (p.is_inf()) continue;
+      L x = L::unpack(L::repack_for_storage(p.x)), y = L::unpack(L::repack_for_storage(p.y));
+      if (neg && neg[i]) y = y.neg_unpacked();
+      lazy_madd(acc, x, y);
+    }
+    memset(&out[s], 0, sizeof out[s]);  // the padding behind `empty` travels to the device too
+    out[s].x = acc.x;
+    out[s].y = acc.y;
+    out[s].zz = acc.zz;
+    out[s].zzz = acc.zzz;
+    out[s].empty = acc.empty;
+  }
+}
+
+// ---- scripted point operations: one script per quad / per pair -------------------------------------------------------------
+// Two registers per unit (r0, r1; both start empty), an operation names its destination d: the other register is the source of
+// ST_ADDR. A script is unit-uniform, so the lanes of a unit never diverge; adjacent units of one wave run different scripts.
+struct StOp {
+  uint32_t code, reg, arg, k;
+};
+enum : uint32_t {
+  ST_LOAD = 0,  // d = slot[arg]
+  ST_ADDP = 1,  // d += slot[arg]
+  ST_ADDR = 2,  // d += the other register
+  ST_ADDS = 3,  // d += d (the same words on both sides)
+  ST_DBL = 4,   // d = 2 d
+  ST_MULK = 5,  // d = k d
+  ST_MADD = 6,  // d += stored affine point arg, negated if k (pair form only)
+  ST_ADDK = 7,  // d += k * the other register (the window reduction's bridge over a gap)
+  ST_NOPS = 8
+};
+
+// Every primitive has ONE call site in a kernel (an operation sets its operands up and falls into the shared sites): six inlined
+// copies of the addition would take the compiler a quarter of an hour. The registers are plain variables, exchanged by value where an
+// operation names r1 -- no indexed register arrays, no pointers into private memory.
+template <class T>
+__device__ __forceinline__ void st_swap(T& a, T& b) {
+  const T t = a;
+  a = b;
+  b = t;
+}
+
+template <class L>
+__global__ __launch_bounds__(256) void k_st_quad_ops(const XYZZLazy<L>* __restrict__ slots, const StOp* __restrict__ ops, const uint32_t* __restrict__ unit_off,
+                                                     uint32_t nunits, XYZZLazy<L>* out) {
+  const int role = threadIdx.x & 3;
+  const uint32_t u = (blockIdx.x * 256 + threadIdx.x) >> 2;
+  if (u >= nunits) return;  // quad-uniform
+  QPt<L> d = qpt_inf<L>(), o = qpt_inf<L>();
+  for (uint32_t i = unit_off[u]; i < unit_off[u + 1]; ++i) {
+    const StOp op = ops[i];
+    if (op.reg & 1) st_swap(d, o);
+    QPt<L> p = qpt_inf<L>();
+    bool add = false;
+    if (op.code == ST_LOAD || op.code == ST_ADDP) {
+      p = qpt_load<L>(&slots[op.arg], role);
+      if (op.code == ST_LOAD) d = p;
+      else add = true;
+    } else if (op.code == ST_ADDR) {
+      p = o;
+      add = true;
+    } else if (op.code == ST_ADDS) {
+      p = d;
+      add = true;
+    } else if (op.code == ST_MULK || op.code == ST_ADDK) {
+      p = qmul_small<L>(op.code == ST_ADDK ? o : d, op.k, role);
+      if (op.code == ST_MULK) d = p;
+      else add = true;
+    }
+    if (add) qadd<L>(d, p, role);
+    if (op.code == ST_DBL) qdbl<L>(d, role);
+    if (op.reg & 1) st_swap(d, o);
+  }
+  qpt_store<L>(&out[2 * (size_t)u], role, d);
+  qpt_store<L>(&out[2 * (size_t)u + 1], role, o);
+}
+
+template <class LS, class LP, class Fq>  // LS: the whole-element type of the stored layout, LP: its lane-pair form
+__global__ __launch_bounds__(256) void k_st_pair_ops(const XYZZLazy<LS>* __restrict__ slots, const Affine<Fq>* __restrict__ aff, const StOp* __restrict__ ops,
+                                                     const uint32_t* __restrict__ unit_off, uint32_t nunits, XYZZLazy<LS>* out) {
+  const int role = pair_role();
+  const uint32_t u = (blockIdx.x * 256 + threadIdx.x) >> 1;
+  if (u >= nunits) return;  // pair-uniform
+  XYZZLazy<LP> d = XYZZLazy<LP>::inf(), o = XYZZLazy<LP>::inf();
+  for (uint32_t i = unit_off[u]; i < unit_off[u + 1]; ++i) {
+    const StOp op = ops[i];
+    if (op.reg & 1) st_swap(d, o);
+    XYZZLazy<LP> p = XYZZLazy<LP>::inf();
+    bool add = false;
+    if (op.code == ST_LOAD || op.code == ST_ADDP) {
+      p = pair_load(&slots[op.arg], role);
+      if (op.code == ST_LOAD) d = p;
+      else add = true;
+    } else if (op.code == ST_ADDR) {
+      p = o;
+      add = true;
+    } else if (op.code == ST_ADDS) {
+      p = d;
+      add = true;
+    } else if (op.code == ST_MULK || op.code == ST_ADDK) {
+      p = lazy_mul_small<LP, true>(op.code == ST_ADDK ? o : d, op.k);
+      if (op.code == ST_MULK) d = p;
+      else add = true;
+    } else if (op.code == ST_MADD) {  // as k_msm_accum_pair feeds lazy_madd
+      LP x, y;
+      pair_unpack_affine<LP, Affine<Fq>>(aff + op.arg, &x, &y);
+      y = y.cneg_unpacked(op.k & 1u);
+      lazy_madd<LP, Affine<Fq>>(d, x, y, aff + op.arg, op.k & 1u);
+    }
+    if (add) lazy_add_inl<LP>(d, p);
+    if (op.code == ST_DBL) d = lazy_dbl_inl<LP>(d);
+    if (op.reg & 1) st_swap(d, o);
+  }
+  pair_store(&out[2 * (size_t)u], role, d);
+  pair_store(&out[2 * (size_t)u + 1], role, o);
+}
+
+template <class L, class Fq>
+__global__ __launch_bounds__(128) void k_st_export(const XYZZLazy<L>* __restrict__ in, uint32_t n, XYZZ<Fq>* out) {
+  const uint32_t i = blockIdx.x * 128 + threadIdx.x;
+  if (i < n) out[i] = lazy_to_xyzz<L, Fq>(in[i]);
+}
+
+// form 1: four lanes per point (curve_quad.hpp), form 2: two lanes per Fp2 point (curve_pair.hpp; LP = void on the G1 groups)
+template <class L, class LP, class Fq>
+int point_ops_t(int form, const void* affine_pts, const uint8_t* neg, size_t npts, const uint32_t* slot_off, size_t nslots, const uint32_t* ops_words,
+                const uint32_t* unit_off, size_t nunits, void* out_xyzz, uint64_t rec[3]) {
+  constexpr bool HAS_PAIR = !std::is_void<LP>::value;
+  if (form != 1 && !(form == 2 && HAS_PAIR)) return CSH_ERR_INVALID;
+  if (!nunits || !nslots || nunits > (1u << 20) || nslots > (1u << 20)) return CSH_ERR_INVALID;
+  const Affine<Fq>* pts = reinterpret_cast<const Affine<Fq>*>(affine_pts);
+  for (size_t s = 0; s < nslots; ++s)
+    if (slot_off[s] > slot_off[s + 1] || slot_off[s + 1] > npts) return CSH_ERR_INVALID;
+  const size_t nops = unit_off[nunits];
+  const StOp* ops = reinterpret_cast<const StOp*>(ops_words);
+  for (size_t u = 0; u < nunits; ++u)
+    if (unit_off[u] > unit_off[u + 1]) return CSH_ERR_INVALID;
+  for (size_t i = 0; i < nops; ++i) {  // every index a kernel will use, checked here
+    const StOp& o = ops[i];
+    if (o.code >= ST_NOPS || o.reg > 1) return CSH_ERR_INVALID;
+    if ((o.code == ST_LOAD || o.code == ST_ADDP) && o.arg >= nslots) return CSH_ERR_INVALID;
+    if (o.code == ST_MADD) {
+      if (form != 2 || o.arg >= npts) return CSH_ERR_INVALID;
+      Affine<Fq> p;
+      memcpy(&p, pts + o.arg, sizeof p);
+      if (p.is_inf()) return CSH_ERR_INVALID;  // the accumulate kernel filters infinity before lazy_madd
+    }
+  }
+  std::vector<XYZZLazy<L>> slots(nslots);
+  build_slots<L, Fq>(pts, neg, slot_off, nslots, slots.data());
+  std::vector<Affine<Fq>> stored(npts ? npts : 1);
+  for (size_t i = 0; i < npts; ++i) {
+    memcpy(&stored[i], pts + i, sizeof(Affine<Fq>));
+    if (!stored[i].is_inf()) stored[i] = {L::repack_for_storage(stored[i].x), L::repack_for_storage(stored[i].y)};
+  }
+  DevMem dslots, daff, dops, doff, dout, dx;
+  CSH_TRY(dslots.alloc(nslots * sizeof(XYZZLazy<L>)));
+  CSH_TRY(daff.alloc(stored.size() * sizeof(Affine<Fq>)));
+  CSH_TRY(dops.alloc(nops * sizeof(StOp)));
+  CSH_TRY(doff.alloc((nunits + 1) * sizeof(uint32_t)));
+  CSH_TRY(dout.alloc(2 * nunits * sizeof(XYZZLazy<L>)));
+  CSH_TRY(dx.alloc(2 * nunits * sizeof(XYZZ<Fq>)));
+  CSH_HIP(hipMemcpy(dslots.p, slots.data(), nslots * sizeof(XYZZLazy<L>), hipMemcpyHostToDevice));
+  CSH_HIP(hipMemcpy(daff.p, stored.data(), stored.size() * sizeof(Affine<Fq>), hipMemcpyHostToDevice));
+  if (nops) CSH_HIP(hipMemcpy(dops.p, ops, nops * sizeof(StOp), hipMemcpyHostToDevice));
+  CSH_HIP(hipMemcpy(doff.p, unit_off, (nunits + 1) * sizeof(uint32_t), hipMemcpyHostToDevice));
+  CSH_HIP(hipMemset(dout.p, 0, 2 * nunits * sizeof(XYZZLazy<L>)));
+  CSH_TRY(bound_record_clear());
+  if (form == 1) {
+    hipLaunchKernelGGL(k_st_quad_ops<L>, dim3((unsigned)((4 * nunits + 255) / 256)), dim3(256), 0, 0, dslots.as<XYZZLazy<L>>(), dops.as<StOp>(),
+                       doff.as<uint32_t>(), (uint32_t)nunits, dout.as<XYZZLazy<L>>());
+  } else {
+    if constexpr (HAS_PAIR)
+      hipLaunchKernelGGL((k_st_pair_ops<L, LP, Fq>), dim3((unsigned)((2 * nunits + 255) / 256)), dim3(256), 0, 0, dslots.as<XYZZLazy<L>>(),
+                         daff.as<Affine<Fq>>(), dops.as<StOp>(), doff.as<uint32_t>(), (uint32_t)nunits, dout.as<XYZZLazy<L>>());
+  }
+  CSH_HIP(hipGetLastError());
+  hipLaunchKernelGGL((k_st_export<L, Fq>), dim3((unsigned)((2 * nunits + 127) / 128)), dim3(128), 0, 0, dout.as<XYZZLazy<L>>(), (uint32_t)(2 * nunits),
+                     dx.as<XYZZ<Fq>>());
+  CSH_HIP(hipGetLastError());
+  CSH_TRY(bound_record_take(rec));
+  CSH_HIP(hipMemcpy(out_xyzz, dx.p, 2 * nunits * sizeof(XYZZ<Fq>), hipMemcpyDeviceToHost));
+  return CSH_OK;
+}
+
+// ---- the tail stages on chosen buckets --------------------------------------------------------------------------------------
+// bucket ids[i] (1 .. NB, each at most once) = the chain over pts[off[i] .. off[i + 1]); every other bucket is empty
+template <class Cfg>
+int msm_tail_t(int form, const void* affine_pts, const uint8_t* neg, size_t npts, const uint32_t* ids, const uint32_t* off, size_t nocc, uint32_t NB, uint32_t S,
+               void* out_xyzz) {
+  using L = typename Cfg::L;
+  using Fq = typename Cfg::Fq;
+  if (NB < 1 || NB > (1u << 16) || S < 1 || S > (1u << 16) || nocc > NB) return CSH_ERR_INVALID;
+  for (size_t i = 0; i < nocc; ++i)
+    if (ids[i] < 1 || ids[i] > NB || off[i] > off[i + 1] || off[i + 1] > npts) return CSH_ERR_INVALID;
+  std::vector<XYZZLazy<L>> occ(nocc ? nocc : 1);
+  build_slots<L, Fq>(reinterpret_cast<const Affine<Fq>*>(affine_pts), neg, off, nocc, occ.data());
+  std::vector<XYZZLazy<L>> dense((size_t)NB + 1);
+  memset((void*)dense.data(), 0, dense.size() * sizeof(XYZZLazy<L>));
+  for (auto& d : dense) d.empty = true;
+  for (size_t i = 0; i < nocc; ++i) dense[ids[i]] = occ[i];
+  return msm_tail_selftest_t<Cfg>(dense.data(), NB, S, form, out_xyzz);
+}
+
+}  // namespace
+
+#define ST_GROUP_DISPATCH(curve, group, CALL)                                                                                                   \
+  do {                                                                                                                                          \
+    if ((curve) == CSH_BN254 && (group) == CSH_G1) { using Cfg = Bn254G1Cfg; using L = Fq29s; using LP = void; using Fq = Bn254Fq; return CALL; }           \
+    if ((curve) == CSH_BN254 && (group) == CSH_G2) { using Cfg = Bn254G2Cfg; using L = Fq29s2; using LP = Bn254G2Cfg::LP; using Fq = Bn254Fq2; return CALL; } \
+    if ((curve) == CSH_BLS12_381 && (group) == CSH_G1) { using Cfg = Bls381G1Cfg; using L = Fq28s; using LP = void; using Fq = Bls381Fq; return CALL; }     \
+    if ((curve) == CSH_BLS12_381 && (group) == CSH_G2) { using Cfg = Bls381G2Cfg; using L = Fq28s2; using LP = Bls381G2Cfg::LP; using Fq = Bls381Fq2; return CALL; } \
+    if ((curve) == CSH_GRUMPKIN && (group) == CSH_G1) { using Cfg = GrumpkinG1Cfg; using L = Fr29s; using LP = void; using Fq = Bn254Fr; return CALL; }      \
+    if ((curve) == CSH_BLS12_377 && (group) == CSH_G1) { using Cfg = Bls377G1Cfg; using L = Fq28s377; using LP = void; using Fq = Bls377Fq; return CALL; }  \
+    if ((curve) == CSH_BLS12_377 && (group) == CSH_G2) { using Cfg = Bls377G2Cfg; using L = Fq28s377x2; using LP = Bls377G2Cfg::LP; using Fq = Bls377Fq2; return CALL; } \
+    return CSH_ERR_INVALID;                                                                                                                     \
+  } while (0)
+
+extern "C" {
+
+// type: 0 Fq29s, 1 Fq28s, 2 Fr29s, 3 Fq28s377. rec: violations, largest |limb|, site (must come back non-zero: the operand is 2^(B+2))
+int csh_selftest_bound_control_dev(int type, uint64_t rec[3]) {
+  CSH_TRY(ensure_device());
+  switch (type) {
+    case 0: return bound_control_t<Fq29s>(rec);
+    case 1: return bound_control_t<Fq28s>(rec);
+    case 2: return bound_control_t<Fr29s>(rec);
+    case 3: return bound_control_t<Fq28s377>(rec);
+    default: return CSH_ERR_INVALID;
+  }
+}
+
+int csh_selftest_fp2pair_raw_dev(int curve, int op, const int32_t* limbs, size_t npairs, uint64_t* out, uint64_t rec[3]) {
+  CSH_TRY(ensure_device());
+  if (op < 0 || op > 3 || !npairs || npairs > (1u << 20)) return CSH_ERR_INVALID;
+  if (curve == CSH_BN254) return fp2pair_raw_t<Bn254G2Cfg::LP, Bn254Fq>(op, limbs, npairs, out, rec);
+  if (curve == CSH_BLS12_381) return fp2pair_raw_t<Bls381G2Cfg::LP, Bls381Fq>(op, limbs, npairs, out, rec);
+  if (curve == CSH_BLS12_377) return fp2pair_raw_t<Bls377G2Cfg::LP, Bls377Fq>(op, limbs, npairs, out, rec);
+  return CSH_ERR_INVALID;
+}
+
+int csh_selftest_fp2pair_zero_dev(int curve, const int32_t* limbs, size_t npairs, uint8_t* flags, uint64_t rec[3]) {
+  CSH_TRY(ensure_device());
+  if (!npairs || npairs > (1u << 20)) return CSH_ERR_INVALID;
+  if (curve == CSH_BN254) return fp2pair_zero_t<Bn254G2Cfg::LP>(limbs, npairs, flags, rec);
+  if (curve == CSH_BLS12_381) return fp2pair_zero_t<Bls381G2Cfg::LP>(limbs, npairs, flags, rec);
+  if (curve == CSH_BLS12_377) return fp2pair_zero_t<Bls377G2Cfg::LP>(limbs, npairs, flags, rec);
+  return CSH_ERR_INVALID;
+}
+
+// Scripted point operations (see StOp): out_xyzz = 2 * nunits XYZZ points (r0, r1 of every unit) in arkworks words.
+int csh_selftest_point_ops_dev(int curve, int group, int form, const void* affine_pts, const uint8_t* neg, size_t npts, const uint32_t* slot_off, size_t nslots,
+                               const uint32_t* ops, const uint32_t* unit_off, size_t nunits, void* out_xyzz, uint64_t rec[3]) {
+  CSH_TRY(ensure_device());
+  ST_GROUP_DISPATCH(curve, group, (point_ops_t<L, LP, Fq>(form, affine_pts, neg, npts, slot_off, nslots, ops, unit_off, nunits, out_xyzz, rec)));
+}
+
+// The real window reduction (form 0: k_msm_reduce_serial, 1: k_msm_reduce<Cfg, false>, 2: k_msm_reduce_pair<Cfg, false>) and the real
+// k_msm_fold_tree levels on one window of NB buckets in S segments; out_xyzz = the window sum, one XYZZ point in arkworks words.
+int csh_selftest_msm_tail_dev(int curve, int group, int form, const void* affine_pts, const uint8_t* neg, size_t npts, const uint32_t* bucket_ids,
+                              const uint32_t* bucket_off, size_t nocc, uint32_t NB, uint32_t S, void* out_xyzz) {
+  CSH_TRY(ensure_device());
+  ST_GROUP_DISPATCH(curve, group, (msm_tail_t<Cfg>(form, affine_pts, neg, npts, bucket_ids, bucket_off, nocc, NB, S, out_xyzz)));
+}
+
+}  // extern "C"

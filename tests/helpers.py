@@ -157,3 +157,88 @@ def penumbra_libsnark_key(seed: int = 377):
     key = g16.libsnark_setup(F, exp["generator"], G1, G2, A, B, Cm, len(pub), len(wit), toxic, fixed_base)
     vk = {"alpha_g1": key["alpha_g1"], "beta_g2": key["beta_g2"], "gamma_g2": key["gamma_g2"], "delta_g2": key["delta_g2"], "ic": key["gamma_abc_g1"]}
     return fx, key, vk, arkfmt.ser_groth16_proving_key(key, G1.F.p, 48), msm
+
+
+# ---- raw limbs of the signed lazy field (field29.hpp FpS): B bits x NL limbs per base field ---------------------------------------
+LAZY_LIMBS = {"bn254": (29, 9), "bls12_381": (28, 14), "bls12_377": (28, 14), "grumpkin": (29, 9)}
+
+
+def fp2_raw_operands(curve, p, r, n):
+    """n operand sets (a, b, c, d) of Fp2 elements as raw signed limbs for the Fp2 product tests: limbs 0 .. NL-2 from the five patterns
+    all +lim, all -lim, alternating, random sign at lim, random in range (lim = 2^B + 8, the normalised-operand bound), the top limb
+    within the value contract |x| < 8p. The first five sets are the pure patterns. -> (list of 4 x (c0 limbs, c1 limbs), flat int32)"""
+    B, NL = LAZY_LIMBS[curve]
+    lim = (1 << B) + 8
+    top = 4 * (p >> (B * (NL - 1)))
+    tl = lambda: [r.randrange(-top, top + 1)]
+    patterns = [
+        lambda: [lim] * (NL - 1) + tl(), lambda: [-lim] * (NL - 1) + tl(), lambda: [lim if i % 2 else -lim for i in range(NL - 1)] + tl(),
+        lambda: [r.choice((lim, -lim)) for _ in range(NL - 1)] + tl(), lambda: [r.randrange(-lim, lim + 1) for _ in range(NL - 1)] + tl(),
+    ]
+    els = []
+    for j in range(n):
+        if j < 5:
+            els.append([(patterns[j](), patterns[j]()) for _ in range(4)])
+        else:
+            els.append([(patterns[r.randrange(5)](), patterns[r.randrange(5)]()) for _ in range(4)])
+    flat = np.array([x for e in els for el in e for comp in el for x in comp], dtype=np.int32)
+    return els, flat
+
+
+def _respell(limbs, B, r, moves):
+    """Random borrow moves l[i] -= 2^B, l[i+1] += 1 and the reverse: the same integer, limbs 0 .. NL-2 kept within |l| <= 2^B + 2 (the
+    class a difference of two reduction outputs belongs to); the top limb is free."""
+    l = list(limbs)
+    NL, lim = len(l), (1 << B) + 2
+    for _ in range(moves):
+        i = r.randrange(NL - 1)
+        s = r.choice((1, -1))
+        a, b = l[i] - s * (1 << B), l[i + 1] + s
+        if abs(a) <= lim and (i + 1 == NL - 1 or abs(b) <= lim):
+            l[i], l[i + 1] = a, b
+    return l
+
+
+def _digits(v, B, NL):
+    """canonical digits of a (possibly negative) integer: limbs 0 .. NL-2 in [0, 2^B), the signed top limb takes the rest"""
+    return [(v >> (B * i)) & ((1 << B) - 1) for i in range(NL - 1)] + [v >> (B * (NL - 1))]
+
+
+def zero_test_cases(p, B, NL, r, spellings=12):
+    """Inputs of the lazy field's zero tests as (limbs, kind):
+    'zero'     k p for every k in -7 .. 7, canonical digits and `spellings` random re-spellings each: maybe_zero() and is_zero_slow() true;
+    'limb0'    such a spelling +/- 2^B or +/- 2^(2B) (limb 0 unchanged): maybe_zero() true, is_zero_slow() false -- the slow test decides;
+    'nonzero'  such a spelling +/- 1, and random values in (-7p, 7p) that are no multiple of p: is_zero() and is_zero_slow() false."""
+    lim = (1 << B) + 2
+    val = lambda l: sum(x << (B * i) for i, x in enumerate(l))
+    cases = []
+    for k in range(-7, 8):
+        base = _digits(k * p, B, NL)
+        sp = [base] + [_respell(base, B, r, 4 * NL) for _ in range(spellings)]
+        for l in sp:
+            assert val(l) == k * p and all(abs(x) <= lim for x in l[:-1])
+            cases.append((l, "zero"))
+        for limb, kind in ((1, "limb0"), (2, "limb0"), (0, "nonzero")):
+            for sgn in (1, -1):
+                for l in sp[1:4]:
+                    if abs(l[limb] + sgn) <= lim:
+                        m = list(l)
+                        m[limb] += sgn
+                        cases.append((m, kind))
+    for _ in range(8 * spellings):
+        v = r.randrange(-7 * p, 7 * p)
+        if v % p:
+            cases.append((_respell(_digits(v, B, NL), B, r, 4 * NL), "nonzero"))
+    return cases
+
+
+def check_zero_flags(flags, comps, ctx):
+    """flags = maybe_zero() | is_zero_slow() << 1 | is_zero() << 2 of an element whose components are `comps` (zero_test_cases entries;
+    one for a base-field element, two for Fp2: every predicate is the conjunction over the components)."""
+    kinds = [k for _, k in comps]
+    zero = all(k == "zero" for k in kinds)
+    maybe, slow, both = bool(flags & 1), bool(flags & 2), bool(flags & 4)
+    assert slow == zero, ("is_zero_slow()", kinds, ctx)
+    assert both == zero, ("is_zero()", kinds, ctx)
+    if all(k in ("zero", "limb0") for k in kinds):
+        assert maybe, ("maybe_zero() misses a multiple of p in its window (or a value with the same limb 0)", kinds, ctx)

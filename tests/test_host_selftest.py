@@ -405,3 +405,28 @@ def test_lazy_fp2_products_at_the_edge_of_their_column_bound(hip, curve):
             out = np.zeros(2 * Fq.nlimbs, dtype=np.uint64)
             assert L.csh_selftest_fp2s_raw(H.CURVE_IDS[curve], op, flat.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)) == 0
             assert tuple(H.unpack(Fq, out)) == want[op], (trial, op)
+
+
+ZERO_TYPES = [("Fq29s", 0, fl.BN254_FQ, 29, 9, 1), ("Fq28s", 1, fl.BLS381_FQ, 28, 14, 1), ("Fr29s", 2, fl.BN254_FR, 29, 9, 1), ("Fq28s377", 3, fl.BLS377_FQ, 28, 14, 1),
+              ("Fq29s2", 4, fl.BN254_FQ, 29, 9, 2), ("Fq28s2", 5, fl.BLS381_FQ, 28, 14, 2), ("Fq28s377x2", 6, fl.BLS377_FQ, 28, 14, 2)]
+
+
+@pytest.mark.parametrize("name,typ,F,B,NL,ncomp", ZERO_TYPES, ids=[t[0] for t in ZERO_TYPES])
+def test_lazy_zero_tests_on_every_spelling_of_a_multiple_of_p(hip, name, typ, F, B, NL, ncomp):
+    """maybe_zero() (limb 0 only, specified for value = k p, |k| < 8, on signed limbs that are not normalised) and is_zero_slow(),
+    SEPARATELY, on raw limbs of every limb configuration the MSM uses: k p for k in -7 .. 7 in many spellings (both true); the same
+    +/- 2^B and +/- 2^(2B), where limb 0 is unchanged (maybe_zero() true, is_zero_slow() false: the slow path is the one that decides);
+    +/- 1 and random non-multiples (is_zero() false). Fp2S: each component zero / non-zero independently. A false negative here turns an
+    addition of equal points into zz3 = 0 garbage with no error."""
+    r = H.rng(5000 + typ)
+    cases = H.zero_test_cases(F.p, B, NL, r)
+    assert sum(1 for _, k in cases if k == "zero") >= 15 * 13 and sum(1 for _, k in cases if k == "limb0") >= 100
+    if ncomp == 1:
+        elems = [[c] for c in cases]
+    else:
+        elems = [[c0, c1] for c0 in cases for c1 in r.sample(cases, 4)]
+    flat = np.array([x for e in elems for limbs, _ in e for x in limbs], dtype=np.int32)
+    flags = np.zeros(len(elems), dtype=np.uint8)
+    assert hip.lib().csh_selftest_zero_flags(typ, flat.ctypes.data_as(C.c_void_p), C.c_size_t(len(elems)), flags.ctypes.data_as(C.c_void_p)) == 0
+    for j, e in enumerate(elems):
+        H.check_zero_flags(int(flags[j]), e, (name, j))
