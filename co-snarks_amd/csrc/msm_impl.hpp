@@ -858,19 +858,6 @@ constexpr int fr_id_of() {
   return std::is_same<Fr, Bls381Fr>::value ? 1 : (std::is_same<Fr, Bn254Fq>::value ? 2 : (std::is_same<Fr, Bls377Fr>::value ? 3 : 0));
 }
 
-inline size_t msm_sort_bytes(const MsmParams& p, const MsmParams& pdig) {
-  if (msm_sort_is_wide(p)) return msm_sort_wide_bytes(p, pdig);
-  const size_t len = (size_t)p.NB + 2, n = p.n;
-  size_t need = 0;
-  need += 2 * Arena::padded(sizeof(uint32_t) * len * p.W);       // hist/cursor, start
-  need += Arena::padded(sizeof(uint32_t) * MAX_WINDOWS);          // lanes per window
-  need += Arena::padded(sizeof(uint32_t) * n * p.W);              // sorted
-  need += Arena::padded(sizeof(uint16_t) * n * p.W);              // digit codes
-  need += Arena::padded(sizeof(uint32_t) * (size_t)p.NB * p.CH * p.W);  // per-chunk bucket counts / prefixes
-  need += msm_sort_extra_bytes(p);  // level-1 records + partition offsets (two-level scatter, large n)
-  return need;
-}
-
 // digits + counting sort; takes its buffers from `ar` (already reserved). ev (nullable): records ev[1..3].
 struct SortStageBufs {
   SortBuffers sb;
@@ -890,22 +877,32 @@ inline SortBuffers sort_group_view(const MsmParams& p, const SortBuffers& b, int
   if (g.part_cnt) g.part_cnt += (size_t)(p.NB / 256) * p.CH * w0;
   return g;
 }
+// Scratch of the plain sort stage, taken from `ar` in this order; msm_sort_bytes is the same list run on an arena without memory
+inline SortStageBufs sort_take(const MsmParams& p, Arena& ar) {
+  const size_t len = (size_t)p.NB + 2, n = p.n;
+  SortStageBufs s;
+  s.sb.hist = ar.take<uint32_t>(len * p.W);
+  s.sb.start = ar.take<uint32_t>(len * p.W);
+  s.sb.nlanes = ar.take<uint32_t>(MAX_WINDOWS);
+  s.sb.sorted = ar.take<uint32_t>(n * p.W);
+  s.sb.dig = ar.take<uint16_t>(n * p.W);
+  s.sb.blkcnt = ar.take<uint32_t>((size_t)p.NB * p.CH * p.W);
+  s.two_level = msm_sort_two_level(p);
+  s.sb.inter = s.two_level ? ar.take<uint64_t>(n * p.W) : nullptr;
+  s.sb.part_cnt = s.two_level ? ar.take<uint32_t>((size_t)(p.NB / 256) * p.CH * p.W) : nullptr;
+  return s;
+}
+inline size_t msm_sort_bytes(const MsmParams& p, const MsmParams& pdig) {
+  if (msm_sort_is_wide(p)) return msm_sort_wide_bytes(p, pdig);
+  Arena sizing;  // no memory behind it: take() only advances off
+  sort_take(p, sizing);
+  return sizing.off;
+}
 template <class Fr>
 int msm_sort_prepare(const MsmParams& p, const MsmParams& pdig, const uint64_t* scalars_dev, hipStream_t st, Arena& ar, SortStageBufs* out) {
-  const size_t len = (size_t)p.NB + 2, n = p.n;
-  uint32_t* hist = ar.take<uint32_t>(len * p.W);
-  uint32_t* start = ar.take<uint32_t>(len * p.W);
-  uint32_t* nlanes = ar.take<uint32_t>(MAX_WINDOWS);
-  uint32_t* sorted = ar.take<uint32_t>(n * p.W);
-  uint16_t* dig = ar.take<uint16_t>(n * p.W);
-  uint32_t* blkcnt = ar.take<uint32_t>((size_t)p.NB * p.CH * p.W);
-  const bool two_level = msm_sort_two_level(p);
-  uint64_t* inter = two_level ? ar.take<uint64_t>(n * p.W) : nullptr;
-  uint32_t* part_cnt = two_level ? ar.take<uint32_t>((size_t)(p.NB / 256) * p.CH * p.W) : nullptr;
+  *out = sort_take(p, ar);
   const int g1 = grid_for(pdig.n, MSM_BLK, 65536);
-  hipLaunchKernelGGL(k_msm_digits<Fr>, dim3(g1), dim3(MSM_BLK), 0, st, reinterpret_cast<const Fr*>(scalars_dev), pdig, dig);  // dig[w * n + i]
-  out->sb = SortBuffers{hist, start, nlanes, sorted, dig, blkcnt, inter, part_cnt};
-  out->two_level = two_level;
+  hipLaunchKernelGGL(k_msm_digits<Fr>, dim3(g1), dim3(MSM_BLK), 0, st, reinterpret_cast<const Fr*>(scalars_dev), pdig, const_cast<uint16_t*>(out->sb.dig));  // dig[w * n + i]
   return CSH_OK;
 }
 template <class Fr>
@@ -916,23 +913,6 @@ int msm_sort_stage(const MsmParams& p, const MsmParams& pdig, const uint64_t* sc
   CSH_TRY(msm_sort_launch(p, ss.sb, st, ev));
   *out = SortOut{ss.sb.start, ss.sb.nlanes, ss.sb.sorted};
   return CSH_OK;
-}
-
-template <class Cfg>
-size_t msm_bucket_bytes(const MsmParams* pp) {
-  const MsmParams& p = *pp;
-  const uint32_t max_lanes = (uint32_t)(((size_t)p.n + p.L - 1) / p.L);
-  const uint32_t max_giant = (uint32_t)(((uint64_t)max_lanes * p.W) / MERGE_CAP + 1);
-  const uint32_t giant_blocks = max_giant < 1024 ? max_giant : 1024;
-  size_t need = 0;
-  need += Arena::padded(sizeof(LazyPt<Cfg>) * (size_t)p.tmax * p.W);       // partials
-  need += Arena::padded(sizeof(LazyPt<Cfg>) * (size_t)p.S * p.W);          // segment results
-  need += Arena::padded(sizeof(LazyPt<Cfg>) * (size_t)(p.NB + 1) * p.W);   // dense bucket sums
-  need += Arena::padded(sizeof(uint32_t) * (2 * (size_t)max_giant + 2) * 8 /* MAX_GROUPS */);
-  need += Arena::padded(sizeof(uint32_t) * 2 * GIANT_BIG_CAP * 8) + Arena::padded(sizeof(LazyPt<Cfg>) * (size_t)GIANT_BIG_CAP * GIANT_SLICES * 8);  // sliced giants
-  need += 2 * Arena::padded(sizeof(LazyPt<Cfg>) * (size_t)((p.S + 127) / 128) * p.W);  // fold-tree ping / pong
-  (void)giant_blocks;
-  return need;
 }
 
 // Scratch of the bucket stage, every array with a per-window stride (window groups run on offset views of it)
@@ -955,12 +935,18 @@ BucketBufs<Cfg> bucket_take(const MsmParams& p, Arena& ar) {
   b.segres = ar.take<LazyPt<Cfg>>((size_t)p.S * p.W);
   b.dense = ar.take<LazyPt<Cfg>>((size_t)(p.NB + 1) * p.W);
   b.giant = ar.take<uint32_t>((2 * (size_t)b.max_giant + 2) * MAX_GROUPS);
-  b.big = ar.take<uint32_t>((size_t)2 * GIANT_BIG_CAP * MAX_GROUPS);
+  b.big = ar.take<uint32_t>((size_t)2 * GIANT_BIG_CAP * MAX_GROUPS);  // sliced giants
   b.gscratch = ar.take<LazyPt<Cfg>>((size_t)GIANT_BIG_CAP * GIANT_SLICES * MAX_GROUPS);
   b.fold_n1 = (p.S + 127) / 128;
-  b.fold_a = ar.take<LazyPt<Cfg>>((size_t)b.fold_n1 * p.W);
+  b.fold_a = ar.take<LazyPt<Cfg>>((size_t)b.fold_n1 * p.W);  // fold-tree ping / pong
   b.fold_b = ar.take<LazyPt<Cfg>>((size_t)b.fold_n1 * p.W);
   return b;
+}
+template <class Cfg>
+size_t msm_bucket_bytes(const MsmParams* pp) {
+  Arena sizing;  // no memory behind it: take() only advances off
+  bucket_take<Cfg>(*pp, sizing);
+  return sizing.off;
 }
 
 // accumulate -> merge -> reduce -> fold tree -> window sums for windows [w0, w0 + nw) on `st`; `group` picks the giant queue.

@@ -1,13 +1,9 @@
 // Sort stage of the MSM: LDS counting sort of the signed-digit codes (see msm.hip for the pipeline).
 #include <stdlib.h>
 
-#include <type_traits>
-
 #include "msm_sort.hpp"
 
 namespace csh {
-
-constexpr int SORT_BLK = 1024;
 
 // index written into the sorted list for flat position i of the digit array (identity unless merged-window mode)
 __device__ __forceinline__ uint32_t entry_id(const MsmParams& p, size_t i) {
@@ -102,24 +98,9 @@ __global__ __launch_bounds__(1024) void k_msm_scan(MsmParams p, uint32_t* hist, 
     const uint32_t b = b0 + k;
     if (b < len) cnt += sc_lds[b];
   }
-  // inclusive scan of cnt over the block: within the wave by shuffles, across the 16 waves through LDS
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  uint32_t incl = cnt;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t up = (uint32_t)__shfl_up((int)incl, d);
-    if (lane >= d) incl += up;
-  }
-  if (lane == 63) wave_tot[wv] = incl;
-  __syncthreads();
-  uint32_t base = 0, total = 0;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) {
-    const uint32_t t = wave_tot[i];
-    if (i < wv) base += t;
-    total += t;
-  }
-  uint32_t run_c = base + incl - cnt;  // exclusive prefix of this thread's run
+  // exclusive scan of cnt over the block: within the wave by shuffles, across the 16 waves through LDS
+  uint32_t total;
+  uint32_t run_c = block_excl_scan<16>(cnt, wave_tot, &total);  // exclusive prefix of this thread's run
   for (uint32_t k = 0; k < per; ++k) {
     const uint32_t b = b0 + k;
     if (b < len) {
@@ -169,7 +150,8 @@ __global__ __launch_bounds__(SORT_BLK) void k_msm_scatter_lds(MsmParams p, const
 // streams of 8-byte records, consecutive positions -> full lines); level 2 sorts each partition by the low bucket
 // byte with 256 open streams inside one contiguous output slice. All offsets come from the histogram already built.
 constexpr uint32_t PART_BUCKETS = 256;
-constexpr int SORT_UNROLL = 4;
+constexpr uint32_t PART_LB = 8;  // the lb of the record format (msm_sort.hpp): level 2 sorts by the low bucket byte
+static_assert(PART_BUCKETS == 1u << PART_LB, "the record format's low key must hold a partition's bucket index");
 
 // in place: part_cnt[w][ch][p] -> first intermediate slot of (chunk ch, partition p) = start of the partition's first
 // bucket + entries of earlier chunks. (Folding this into k_msm_scan, 64 threads per window walking the chunks, was measured:
@@ -195,7 +177,7 @@ __global__ __launch_bounds__(256) void k_msm_part_offsets(MsmParams p, const uin
 // Level 1: block (chunk, window); tiles of L1_TILE digit codes are counting-sorted by partition inside LDS and
 // written out as 8-byte records (index | sign << 31 | low bucket byte << 32) in runs of neighbouring addresses.
 // REC = 1 (entry ids < 2^23, i.e. n <= 2^23 and no table remap): 4-byte records (index | sign << 23 | low bucket byte << 24)
-// -- 14 instead of 22 bytes of HBM traffic per entry over the two levels. REC = 0: the 8-byte records.
+// -- 14 instead of 22 bytes of HBM traffic per entry over the two levels. REC = 0: the 8-byte records. (rec_pack, msm_sort.hpp)
 #ifndef CSH_L1_WPE
 #define CSH_L1_WPE 8  // two 1024-lane blocks per CU (64 VGPRs instead of 75): one block's barriers and LDS phases under the other's loads;
                       // scatter stage 0.124 -> 0.110 ms at 2^20, 0.384 -> 0.351 at 2^22 (profiles/archive/r03_y_scatter_l1_occupancy.log)
@@ -207,11 +189,10 @@ __global__ __launch_bounds__(256) void k_msm_part_offsets(MsmParams p, const uin
 #endif
 constexpr int L1_EPT = 8;
 constexpr int L1_TILE = L1_EPT * SORT_BLK;
+constexpr uint32_t MAXP = 128;  // partitions per window: NB <= 2^15
 template <int REC>
 __global__ __launch_bounds__(SORT_BLK) CSH_L1_OCC void k_msm_scatter_l1(MsmParams p, const uint16_t* __restrict__ dig, const uint32_t* __restrict__ part_off,
                                                              void* __restrict__ inter) {
-  using Rec = typename std::conditional<REC != 0, uint32_t, uint64_t>::type;
-  constexpr uint32_t MAXP = 128;  // NB <= 2^15
   __shared__ uint32_t gcur[MAXP];
   __shared__ uint32_t cnt[MAXP];
   __shared__ uint32_t toff[MAXP];
@@ -230,7 +211,7 @@ __global__ __launch_bounds__(SORT_BLK) CSH_L1_OCC void k_msm_scatter_l1(MsmParam
   size_t hi = lo + p.chunk_len;
   if (hi > p.n) hi = p.n;
   const uint16_t* d = dig + (size_t)w * p.n;
-  Rec* out = reinterpret_cast<Rec*>(inter) + (size_t)w * p.n;
+  SortRec<REC>* out = reinterpret_cast<SortRec<REC>*>(inter) + (size_t)w * p.n;
   for (size_t t0 = lo; t0 < hi; t0 += L1_TILE) {
     uint32_t code[L1_EPT], rank[L1_EPT];
 #pragma unroll
@@ -241,22 +222,11 @@ __global__ __launch_bounds__(SORT_BLK) CSH_L1_OCC void k_msm_scatter_l1(MsmParam
 #pragma unroll
     for (int k = 0; k < L1_EPT; ++k) rank[k] = lds_slot(cnt, (code[k] & 0x7fffu) / PART_BUCKETS, code[k] != DIG_ZERO);
     __syncthreads();
-    uint32_t v = 0, incl = 0;
-    if (tid < MAXP) {
-      v = cnt[tid];
-      incl = v;
-      const int lane = tid & 63;
-#pragma unroll
-      for (int dd = 1; dd < 64; dd <<= 1) {
-        const uint32_t t = (uint32_t)__shfl_up((int)incl, dd);
-        if (lane >= dd) incl += t;
-      }
-      if (lane == 63) wsum[tid >> 6] = incl;
-    }
+    const uint32_t v = tid < MAXP ? cnt[tid] : 0;
+    uint32_t tile_n;  // non-zero digits in this tile
+    const uint32_t excl = block_excl_scan<MAXP / 64, SORT_BLK / 64>(v, wsum, &tile_n);
+    if (tid < MAXP) toff[tid] = excl;
     __syncthreads();
-    if (tid < MAXP) toff[tid] = (tid >= 64 ? wsum[0] : 0) + incl - v;
-    __syncthreads();
-    const uint32_t tile_n = wsum[0] + wsum[1];  // non-zero digits in this tile
 #pragma unroll
     for (int k = 0; k < L1_EPT; ++k) {
       if (code[k] != DIG_ZERO) {
@@ -273,12 +243,7 @@ __global__ __launch_bounds__(SORT_BLK) CSH_L1_OCC void k_msm_scatter_l1(MsmParam
       const uint32_t sl = k * SORT_BLK + tid;
       if (sl < tile_n) {
         const uint32_t bin = sbin[sl];
-        const uint32_t dst = gcur[bin] + (sl - toff[bin]);
-        if constexpr (REC == 1) {
-          out[dst] = (pay[sl] & 0x7fffffu) | ((pay[sl] >> 31) << 23) | ((uint32_t)slo[sl] << 24);
-        } else {
-          out[dst] = (uint64_t)pay[sl] | ((uint64_t)slo[sl] << 32);
-        }
+        out[gcur[bin] + (sl - toff[bin])] = rec_pack<REC>(pay[sl], slo[sl], PART_LB);
       }
     }
     __syncthreads();
@@ -290,71 +255,53 @@ __global__ __launch_bounds__(SORT_BLK) CSH_L1_OCC void k_msm_scatter_l1(MsmParam
   }
 }
 
-// Level 2: block (partition, window). The partition is processed in tiles of L2_TILE records: each tile is
+// Level 2. A block works through a slice [lo, hi) of one partition's records in tiles of L2_TILE: each tile is
 // counting-sorted by the low bucket byte inside LDS and then written out slot by slot, so neighbouring lanes write
 // neighbouring addresses (runs of ~L2_TILE/256 entries per bucket) instead of 64 unrelated 4-byte stores per wave.
-constexpr int L2_EPT = 8;
-constexpr int L2_TILE = L2_EPT * SORT_BLK;
-template <int REC>
-__global__ __launch_bounds__(SORT_BLK) void k_msm_scatter_l2(MsmParams p, const uint32_t* __restrict__ start, const void* __restrict__ inter,
-                                                             uint32_t* __restrict__ sorted) {
-  using Rec = typename std::conditional<REC != 0, uint32_t, uint64_t>::type;
-  constexpr int BIN_SHIFT = REC != 0 ? 24 : 32;
-  __shared__ uint32_t gcur[PART_BUCKETS];  // next free sorted slot per bucket
-  __shared__ uint32_t cnt[PART_BUCKETS];   // tile histogram
-  __shared__ uint32_t toff[PART_BUCKETS];  // tile-local exclusive offsets
-  __shared__ uint32_t wsum[4];
-  __shared__ uint32_t pay[L2_TILE];
-  __shared__ uint8_t sbin[L2_TILE];
-  const uint32_t part = blockIdx.x, w = blockIdx.y;
-  const uint32_t* st = start + (size_t)w * (p.NB + 2) + (size_t)part * PART_BUCKETS + 1;
+struct L2Lds {
+  uint32_t obase[PART_BUCKETS];  // where the tile's entries of every bucket go in the sorted list
+  uint32_t cnt[PART_BUCKETS];    // tile histogram
+  uint32_t toff[PART_BUCKETS];   // tile-local exclusive offsets
+  uint32_t wsum[4];
+  uint32_t pay[L2_TILE];
+  uint8_t sbin[L2_TILE];
+};
+// Where obase comes from -- the only difference between the two level-2 kernels. Both calls are made by thread b < PART_BUCKETS with
+// v = the tile's entries of bucket b: reserve() before the tile is written out, advance() after.
+struct L2OwnRuns {  // the block has the whole partition: obase (set to the buckets' starts by the kernel) is a running cursor
+  __device__ void reserve(uint32_t*, uint32_t, uint32_t) const {}
+  __device__ void advance(uint32_t* obase, uint32_t b, uint32_t v) const { obase[b] += v; }
+};
+struct L2SharedRuns {  // blocks share the partition: one atomicAdd per bucket and tile on the buckets' global cursors
+  uint32_t* cur;
+  __device__ void reserve(uint32_t* obase, uint32_t b, uint32_t v) const { obase[b] = v ? atomicAdd(&cur[b], v) : 0u; }
+  __device__ void advance(uint32_t*, uint32_t, uint32_t) const {}
+};
+// s.cnt is zero on entry (and again on return); a barrier lies between the caller's LDS writes and the call
+template <int REC, class Runs>
+__device__ __forceinline__ void l2_sort_slice(L2Lds& s, const Runs runs, const SortRec<REC>* __restrict__ in, uint32_t lo, uint32_t hi,
+                                              uint32_t* __restrict__ so) {
   const uint32_t tid = threadIdx.x;
-  if (tid < PART_BUCKETS) {
-    gcur[tid] = st[tid];
-    cnt[tid] = 0;
-  }
-  __syncthreads();
-  const uint32_t lo = st[0], hi = st[PART_BUCKETS];
-  const Rec* in = reinterpret_cast<const Rec*>(inter) + (size_t)w * p.n;
-  uint32_t* so = sorted + (size_t)w * p.n;
   for (uint32_t t0 = lo; t0 < hi; t0 += L2_TILE) {
-    Rec e[L2_EPT];
+    SortRec<REC> e[L2_EPT];
     uint32_t rank[L2_EPT];
-#pragma unroll
-    for (int k = 0; k < L2_EPT; ++k) {
-      const uint32_t i = t0 + k * SORT_BLK + tid;
-      e[k] = i < hi ? __builtin_nontemporal_load(in + i) : 0;
-    }
-#pragma unroll
-    for (int k = 0; k < L2_EPT; ++k) rank[k] = lds_slot(cnt, (uint32_t)(e[k] >> BIN_SHIFT), t0 + k * SORT_BLK + tid < hi);
+    l2_load_rank<REC>(in, t0, hi, PART_LB, s.cnt, e, rank);
     __syncthreads();
-    uint32_t v = 0, incl = 0;
-    if (tid < PART_BUCKETS) {  // waves 0..3, fully active: wave scan + 4 wave totals
-      v = cnt[tid];
-      incl = v;
-      const int lane = tid & 63;
-#pragma unroll
-      for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t t = (uint32_t)__shfl_up((int)incl, d);
-        if (lane >= d) incl += t;
-      }
-      if (lane == 63) wsum[tid >> 6] = incl;
-    }
-    __syncthreads();
+    uint32_t v = 0, total;
     if (tid < PART_BUCKETS) {
-      uint32_t base = 0;
-      for (uint32_t q = 0; q < (tid >> 6); ++q) base += wsum[q];
-      toff[tid] = base + incl - v;
+      v = s.cnt[tid];
+      runs.reserve(s.obase, tid, v);
     }
+    const uint32_t excl = block_excl_scan<PART_BUCKETS / 64, SORT_BLK / 64>(v, s.wsum, &total);  // waves 0..3, fully active: wave scan + 4 wave totals
+    if (tid < PART_BUCKETS) s.toff[tid] = excl;
     __syncthreads();
 #pragma unroll
     for (int k = 0; k < L2_EPT; ++k) {
       if (t0 + k * SORT_BLK + tid < hi) {
-        const uint32_t bin = (uint32_t)(e[k] >> BIN_SHIFT);
-        const uint32_t slot = toff[bin] + rank[k];
-        if constexpr (REC == 1) pay[slot] = ((uint32_t)e[k] & 0x7fffffu) | ((((uint32_t)e[k] >> 23) & 1u) << 31);
-        else pay[slot] = (uint32_t)e[k];
-        sbin[slot] = (uint8_t)bin;
+        const uint32_t bin = rec_low<REC>(e[k], PART_LB);
+        const uint32_t slot = s.toff[bin] + rank[k];
+        s.pay[slot] = rec_entry<REC>(e[k], PART_LB);
+        s.sbin[slot] = (uint8_t)bin;
       }
     }
     __syncthreads();
@@ -363,17 +310,33 @@ __global__ __launch_bounds__(SORT_BLK) void k_msm_scatter_l2(MsmParams p, const 
     for (int k = 0; k < L2_EPT; ++k) {
       const uint32_t sl = k * SORT_BLK + tid;
       if (sl < tile_n) {
-        const uint32_t bin = sbin[sl];
-        so[gcur[bin] + (sl - toff[bin])] = pay[sl];
+        const uint32_t bin = s.sbin[sl];
+        so[s.obase[bin] + (sl - s.toff[bin])] = s.pay[sl];
       }
     }
     __syncthreads();
     if (tid < PART_BUCKETS) {
-      gcur[tid] += v;
-      cnt[tid] = 0;
+      runs.advance(s.obase, tid, v);
+      s.cnt[tid] = 0;
     }
     __syncthreads();
   }
+}
+
+// Level 2, block (partition, window): no atomics, the order inside a bucket is deterministic (tune "msm_variant" bit 5).
+template <int REC>
+__global__ __launch_bounds__(SORT_BLK) void k_msm_scatter_l2(MsmParams p, const uint32_t* __restrict__ start, const void* __restrict__ inter,
+                                                             uint32_t* __restrict__ sorted) {
+  __shared__ L2Lds s;
+  const uint32_t part = blockIdx.x, w = blockIdx.y, tid = threadIdx.x;
+  const uint32_t* st = start + (size_t)w * (p.NB + 2) + (size_t)part * PART_BUCKETS + 1;
+  if (tid < PART_BUCKETS) {
+    s.obase[tid] = st[tid];
+    s.cnt[tid] = 0;
+  }
+  __syncthreads();
+  l2_sort_slice<REC>(s, L2OwnRuns{}, reinterpret_cast<const SortRec<REC>*>(inter) + (size_t)w * p.n, st[0], st[PART_BUCKETS],
+                     sorted + (size_t)w * p.n);
 }
 
 // Level 2, tile-parallel (the default since the end of round 3). The kernel above gives one block a whole partition, so a skewed
@@ -387,117 +350,39 @@ __global__ __launch_bounds__(SORT_BLK) void k_msm_scatter_l2(MsmParams p, const 
 template <int REC>
 __global__ __launch_bounds__(SORT_BLK) void k_msm_scatter_l2t(MsmParams p, const uint32_t* __restrict__ start, uint32_t* __restrict__ cursor,
                                                               const void* __restrict__ inter, uint32_t* __restrict__ sorted) {
-  using Rec = typename std::conditional<REC != 0, uint32_t, uint64_t>::type;
-  constexpr int BIN_SHIFT = REC != 0 ? 24 : 32;
-  constexpr uint32_t MAXP = 128;  // NB <= 2^15
-  __shared__ uint32_t gbase[PART_BUCKETS];  // reserved output run of every bucket for the current tile
-  __shared__ uint32_t cnt[PART_BUCKETS];    // tile histogram
-  __shared__ uint32_t toff[PART_BUCKETS];   // tile-local exclusive offsets
-  __shared__ uint32_t wsum[4];
-  __shared__ uint32_t job[3];               // partition, first and one-past-last intermediate slot of this block's slice
-  __shared__ uint32_t pay[L2_TILE];
-  __shared__ uint8_t sbin[L2_TILE];
+  __shared__ L2Lds s;
+  __shared__ uint32_t job[3];  // partition, first and one-past-last intermediate slot of this block's slice
   const uint32_t x = blockIdx.x, w = blockIdx.y, tid = threadIdx.x;
   const uint32_t P = p.NB / PART_BUCKETS;
   const uint32_t* stw = start + (size_t)w * (p.NB + 2);
   {  // which slice of which partition is block x: partitions get max(1, round(entries / tile)) blocks each (none when empty)
-    uint32_t lo_p = 0, hi_p = 0, nb = 0, incl = 0;
-    if (tid < MAXP) {
-      if (tid < P) {
-        lo_p = stw[(size_t)tid * PART_BUCKETS + 1];
-        hi_p = stw[(size_t)(tid + 1) * PART_BUCKETS + 1];
-        const uint32_t c = hi_p - lo_p;
-        nb = c ? (c + L2_TILE / 2) / L2_TILE : 0;
-        if (c && nb == 0) nb = 1;
-      }
-      incl = nb;
-      const int lane = tid & 63;
-#pragma unroll
-      for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t t = (uint32_t)__shfl_up((int)incl, d);
-        if (lane >= d) incl += t;
-      }
-      if (lane == 63) wsum[tid >> 6] = incl;
+    uint32_t lo_p = 0, hi_p = 0, nb = 0, total;
+    if (tid < P) {
+      lo_p = stw[(size_t)tid * PART_BUCKETS + 1];
+      hi_p = stw[(size_t)(tid + 1) * PART_BUCKETS + 1];
+      const uint32_t c = hi_p - lo_p;
+      nb = c ? (c + L2_TILE / 2) / L2_TILE : 0;
+      if (c && nb == 0) nb = 1;
     }
     if (tid == 0) job[0] = 0xffffffffu;
-    __syncthreads();
-    if (tid < MAXP) {
-      const uint32_t pre = (tid >= 64 ? wsum[0] : 0) + incl - nb;  // blocks of earlier partitions
-      if (nb && x >= pre && x < pre + nb) {
-        const uint32_t c = hi_p - lo_p, slice = (c + nb - 1) / nb, j = x - pre;
-        uint32_t a = lo_p + j * slice, b = a + slice;
-        if (b > hi_p) b = hi_p;
-        if (a > hi_p) a = hi_p;
-        job[0] = tid;
-        job[1] = a;
-        job[2] = b;
-      }
+    const uint32_t pre = block_excl_scan<MAXP / 64, SORT_BLK / 64>(nb, s.wsum, &total);  // blocks of earlier partitions
+    if (nb && x >= pre && x < pre + nb) {
+      const uint32_t c = hi_p - lo_p, slice = (c + nb - 1) / nb, j = x - pre;
+      uint32_t a = lo_p + j * slice, b = a + slice;
+      if (b > hi_p) b = hi_p;
+      if (a > hi_p) a = hi_p;
+      job[0] = tid;
+      job[1] = a;
+      job[2] = b;
     }
     __syncthreads();
   }
   const uint32_t part = job[0];
   if (part == 0xffffffffu) return;  // the grid is sized for the worst case (entries / tile + partitions blocks per window)
-  const uint32_t lo = job[1], hi = job[2];
-  if (tid < PART_BUCKETS) cnt[tid] = 0;
+  if (tid < PART_BUCKETS) s.cnt[tid] = 0;
   __syncthreads();
-  uint32_t* cur = cursor + (size_t)w * (p.NB + 2) + (size_t)part * PART_BUCKETS + 1;
-  const Rec* in = reinterpret_cast<const Rec*>(inter) + (size_t)w * p.n;
-  uint32_t* so = sorted + (size_t)w * p.n;
-  for (uint32_t t0 = lo; t0 < hi; t0 += L2_TILE) {
-    Rec e[L2_EPT];
-    uint32_t rank[L2_EPT];
-#pragma unroll
-    for (int k = 0; k < L2_EPT; ++k) {
-      const uint32_t i = t0 + k * SORT_BLK + tid;
-      e[k] = i < hi ? __builtin_nontemporal_load(in + i) : 0;
-    }
-#pragma unroll
-    for (int k = 0; k < L2_EPT; ++k) rank[k] = lds_slot(cnt, (uint32_t)(e[k] >> BIN_SHIFT), t0 + k * SORT_BLK + tid < hi);
-    __syncthreads();
-    uint32_t v = 0, incl = 0;
-    if (tid < PART_BUCKETS) {  // waves 0..3, fully active: wave scan + 4 wave totals; and the output run of every bucket of the tile
-      v = cnt[tid];
-      gbase[tid] = v ? atomicAdd(&cur[tid], v) : 0u;
-      incl = v;
-      const int lane = tid & 63;
-#pragma unroll
-      for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t t = (uint32_t)__shfl_up((int)incl, d);
-        if (lane >= d) incl += t;
-      }
-      if (lane == 63) wsum[tid >> 6] = incl;
-    }
-    __syncthreads();
-    if (tid < PART_BUCKETS) {
-      uint32_t base = 0;
-      for (uint32_t q = 0; q < (tid >> 6); ++q) base += wsum[q];
-      toff[tid] = base + incl - v;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < L2_EPT; ++k) {
-      if (t0 + k * SORT_BLK + tid < hi) {
-        const uint32_t bin = (uint32_t)(e[k] >> BIN_SHIFT);
-        const uint32_t slot = toff[bin] + rank[k];
-        if constexpr (REC == 1) pay[slot] = ((uint32_t)e[k] & 0x7fffffu) | ((((uint32_t)e[k] >> 23) & 1u) << 31);
-        else pay[slot] = (uint32_t)e[k];
-        sbin[slot] = (uint8_t)bin;
-      }
-    }
-    __syncthreads();
-    const uint32_t tile_n = hi - t0 < (uint32_t)L2_TILE ? hi - t0 : (uint32_t)L2_TILE;
-#pragma unroll
-    for (int k = 0; k < L2_EPT; ++k) {
-      const uint32_t sl = k * SORT_BLK + tid;
-      if (sl < tile_n) {
-        const uint32_t bin = sbin[sl];
-        so[gbase[bin] + (sl - toff[bin])] = pay[sl];
-      }
-    }
-    __syncthreads();
-    if (tid < PART_BUCKETS) cnt[tid] = 0;
-    __syncthreads();
-  }
+  l2_sort_slice<REC>(s, L2SharedRuns{cursor + (size_t)w * (p.NB + 2) + (size_t)part * PART_BUCKETS + 1},
+                     reinterpret_cast<const SortRec<REC>*>(inter) + (size_t)w * p.n, job[1], job[2], sorted + (size_t)w * p.n);
 }
 
 // Two-level mode pays off once a (partition, window) block has enough records to fill its tiles: n >= 2^20
@@ -508,14 +393,22 @@ bool msm_sort_two_level(const MsmParams& p) {
   return p.n >= (1u << 20);
 }
 
-size_t msm_sort_extra_bytes(const MsmParams& p) {
-  if (!msm_sort_two_level(p)) return 0;
-  return Arena::padded(sizeof(uint64_t) * (size_t)p.n * p.W) + Arena::padded(sizeof(uint32_t) * (size_t)(p.NB / PART_BUCKETS) * p.CH * p.W);
+// the two-level scatter with 4-byte (REC = 1) or 8-byte intermediate records
+template <int REC>
+static void launch_two_level(const MsmParams& p, const SortBuffers& b, hipStream_t st) {
+  const uint32_t nparts = p.NB / PART_BUCKETS;
+  hipLaunchKernelGGL(k_msm_scatter_l1<REC>, dim3(p.CH, p.W), dim3(SORT_BLK), 0, st, p, b.dig, b.part_cnt, (void*)b.inter);
+  // level 2: one block per slice of about one tile of a partition (default), or -- tune "msm_variant" bit 5 -- one block per partition
+  if ((tune().msm_variant.load(std::memory_order_relaxed) & 32) != 0) {
+    hipLaunchKernelGGL(k_msm_scatter_l2<REC>, dim3(nparts, p.W), dim3(SORT_BLK), 0, st, p, b.start, (const void*)b.inter, b.sorted);
+  } else {
+    const uint32_t l2_blocks = (uint32_t)(p.n / L2_TILE) + nparts + 1;
+    hipLaunchKernelGGL(k_msm_scatter_l2t<REC>, dim3(l2_blocks, p.W), dim3(SORT_BLK), 0, st, p, b.start, b.hist, (const void*)b.inter, b.sorted);
+  }
 }
 
 int msm_sort_launch(const MsmParams& p, const SortBuffers& b, hipStream_t st, hipEvent_t* ev) {
   const bool two_level = msm_sort_two_level(p);
-  const uint32_t nparts = p.NB / PART_BUCKETS;
   const size_t sort_lds = sizeof(uint32_t) * p.NB;
   if (sort_lds > 48 * 1024) {
     CSH_TRY(raise_lds_limit((const void*)k_msm_hist_lds, 128 * 1024));
@@ -531,25 +424,14 @@ int msm_sort_launch(const MsmParams& p, const SortBuffers& b, hipStream_t st, hi
   }
   if (ev) CSH_HIP(hipEventRecord(ev[2], st));
   if (two_level) {
-    hipLaunchKernelGGL(k_msm_part_offsets, dim3((nparts + 255) / 256, p.W), dim3(256), 0, st, p, b.start, b.part_cnt);
+    hipLaunchKernelGGL(k_msm_part_offsets, dim3((p.NB / PART_BUCKETS + 255) / 256, p.W), dim3(256), 0, st, p, b.start, b.part_cnt);
     // 4-byte intermediate records when every stored entry id fits 23 bits (n, or rows x bases with tables, <= 2^23); tune "msm_variant"
     // bit 3 forces the 8-byte records (A/B runs, tests). (4-byte records + a separate sign byte for ids up to 2^24 were
     // measured and lose to the 8-byte records: scatter 2.29 against 2.10 ms on BN254 G1 2^24 -- byte-granular scattered
     // writes cost more than the 3 bytes per entry they save, profiles/archive/r02_g_rec_stages.log.)
     const uint64_t max_id = p.remap_n ? (uint64_t)(p.n / p.remap_n) * p.remap_stride : (uint64_t)p.n;  // stored ids: table indices
     const bool wide_only = (tune().msm_variant.load(std::memory_order_relaxed) & 8) != 0;
-    // level 2: one block per slice of about one tile of a partition (default), or -- tune "msm_variant" bit 5 -- one block per partition
-    const bool by_partition = (tune().msm_variant.load(std::memory_order_relaxed) & 32) != 0;
-    const uint32_t l2_blocks = (uint32_t)(p.n / L2_TILE) + nparts + 1;
-    if (!wide_only && max_id <= (1u << 23)) {
-      hipLaunchKernelGGL(k_msm_scatter_l1<1>, dim3(p.CH, p.W), dim3(SORT_BLK), 0, st, p, b.dig, b.part_cnt, (void*)b.inter);
-      if (by_partition) hipLaunchKernelGGL(k_msm_scatter_l2<1>, dim3(nparts, p.W), dim3(SORT_BLK), 0, st, p, b.start, (const void*)b.inter, b.sorted);
-      else hipLaunchKernelGGL(k_msm_scatter_l2t<1>, dim3(l2_blocks, p.W), dim3(SORT_BLK), 0, st, p, b.start, b.hist, (const void*)b.inter, b.sorted);
-    } else {
-      hipLaunchKernelGGL(k_msm_scatter_l1<0>, dim3(p.CH, p.W), dim3(SORT_BLK), 0, st, p, b.dig, b.part_cnt, (void*)b.inter);
-      if (by_partition) hipLaunchKernelGGL(k_msm_scatter_l2<0>, dim3(nparts, p.W), dim3(SORT_BLK), 0, st, p, b.start, (const void*)b.inter, b.sorted);
-      else hipLaunchKernelGGL(k_msm_scatter_l2t<0>, dim3(l2_blocks, p.W), dim3(SORT_BLK), 0, st, p, b.start, b.hist, (const void*)b.inter, b.sorted);
-    }
+    (!wide_only && max_id <= (1u << (31 - PART_LB))) ? launch_two_level<1>(p, b, st) : launch_two_level<0>(p, b, st);
   } else {
     hipLaunchKernelGGL(k_msm_scatter_lds, dim3(p.CH, p.W), dim3(SORT_BLK), sort_lds, st, p, b.dig, b.start, b.blkcnt, b.sorted);
   }

@@ -1,6 +1,8 @@
 // Counting-sort stage of the Pippenger MSM (msm.hip): digit codes -> per-window bucket-ordered index lists.
 // Kept in its own translation unit: the kernels are field-independent.
 #pragma once
+#include <type_traits>
+
 #include "common.hpp"
 
 namespace csh {
@@ -82,10 +84,89 @@ __device__ __forceinline__ uint32_t lds_slot(uint32_t* counter, uint32_t b, bool
   if (todo) slot = atomicAdd(&counter[b], 1u);
   return slot;
 }
+
+// inclusive prefix of one value per lane inside a wave
+__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const uint32_t up = (uint32_t)__shfl_up((int)v, d);
+    if (lane >= d) v += up;
+  }
+  return v;
+}
+
+// exclusive prefix of one value per thread over the first NW waves of a block of BLOCK_WAVES; *total = their sum. Every thread of the
+// block calls it (one barrier inside); waves from NW on skip the shuffles and get only *total. wsum: >= NW LDS words that nobody else
+// touches until the next barrier after the call.
+template <int NW, int BLOCK_WAVES = NW>
+__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* wsum, uint32_t* total) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  uint32_t incl = 0;
+  if (BLOCK_WAVES == NW || wv < NW) {
+    incl = wave_incl_scan(v);
+    if (lane == 63) wsum[wv] = incl;
+  }
+  __syncthreads();
+  uint32_t base = 0, tot = 0;
+#pragma unroll
+  for (int i = 0; i < NW; ++i) {
+    const uint32_t t = wsum[i];
+    if (i < wv) base += t;
+    tot += t;
+  }
+  *total = tot;
+  return base + incl - v;
+}
+
+// Intermediate record of the two-level sorts (level 1 writes it, level 2 reads it), for partitions of 1 << lb buckets:
+// REC = 0: 8 bytes, entry | low key << 32; REC = 1: 4 bytes, id | sign << idb | low key << (idb + 1) with idb = 31 - lb (ids below
+// 2^idb). entry = id | sign << 31 is the form of the sorted list; low key = the low lb bits of bucket - 1.
+template <int REC>
+using SortRec = typename std::conditional<REC != 0, uint32_t, uint64_t>::type;
+template <int REC>
+__device__ __forceinline__ SortRec<REC> rec_pack(uint32_t entry, uint32_t low, uint32_t lb) {
+  if constexpr (REC == 1) {
+    const uint32_t idb = 31 - lb;
+    return (entry & ((1u << idb) - 1)) | ((entry >> 31) << idb) | (low << (idb + 1));
+  } else {
+    return (uint64_t)entry | ((uint64_t)low << 32);
+  }
+}
+template <int REC>
+__device__ __forceinline__ uint32_t rec_low(SortRec<REC> e, uint32_t lb) {
+  if constexpr (REC == 1) return e >> (32 - lb);
+  else return (uint32_t)(e >> 32);
+}
+template <int REC>
+__device__ __forceinline__ uint32_t rec_entry(SortRec<REC> e, uint32_t lb) {
+  if constexpr (REC == 1) {
+    const uint32_t idb = 31 - lb;
+    return (e & ((1u << idb) - 1)) | (((e >> idb) & 1u) << 31);
+  } else {
+    return (uint32_t)e;
+  }
+}
+
+// Level 2 of both sorts works on tiles of L2_TILE records, L2_EPT per thread of a SORT_BLK block. First step of a tile [t0, hi) (at most
+// L2_TILE records): load this thread's records and rank each inside its bucket with the LDS tile histogram cnt (zeroed by the caller).
+constexpr int SORT_BLK = 1024;
+constexpr int L2_EPT = 8;
+constexpr int L2_TILE = L2_EPT * SORT_BLK;
+template <int REC>
+__device__ __forceinline__ void l2_load_rank(const SortRec<REC>* __restrict__ in, uint32_t t0, uint32_t hi, uint32_t lb, uint32_t* cnt,
+                                             SortRec<REC>* e, uint32_t* rank) {
+#pragma unroll
+  for (int k = 0; k < L2_EPT; ++k) {
+    const uint32_t i = t0 + k * SORT_BLK + threadIdx.x;
+    e[k] = i < hi ? __builtin_nontemporal_load(in + i) : 0;
+  }
+#pragma unroll
+  for (int k = 0; k < L2_EPT; ++k) rank[k] = lds_slot(cnt, rec_low<REC>(e[k], lb), t0 + k * SORT_BLK + threadIdx.x < hi);
+}
 #endif
 
 bool msm_sort_two_level(const MsmParams& p);
-size_t msm_sort_extra_bytes(const MsmParams& p);  // arena bytes for inter + part_cnt (0 in single-level mode)
 // Launches hist -> colscan -> scan -> scatter on `st`. ev (nullable): records ev[1] after the histogram, ev[2] after
 // the scan, ev[3] after the scatter.
 int msm_sort_launch(const MsmParams& p, const SortBuffers& b, hipStream_t st, hipEvent_t* ev);

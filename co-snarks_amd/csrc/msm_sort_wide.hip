@@ -22,8 +22,6 @@
 // Output contract = the plain stage's for ONE window: start[NB + 2], nlanes[0], sorted[n W] (table index | sign << 31 in bucket order).
 #include <stdlib.h>
 
-#include <type_traits>
-
 #include "field.hpp"
 #include "msm_digits.hpp"
 #include "msm_sort_wide.hpp"
@@ -32,34 +30,10 @@ namespace csh {
 
 constexpr int WS_BLK = 512;    // level 1: one scalar per thread and tile
 constexpr int WS_MAXW = 16;    // digits per scalar (c >= 16 and bits + 1 <= 256)
-constexpr int W2_BLK = 1024;   // level 2
-constexpr int W2_EPT = 8;
-constexpr int W2_TILE = W2_BLK * W2_EPT;
+constexpr int W2_BLK = SORT_BLK;  // level 2: the tiles of the plain sort's level 2 (l2_load_rank, msm_sort.hpp)
+constexpr int W2_EPT = L2_EPT;
+constexpr int W2_TILE = L2_TILE;
 constexpr uint32_t WCODE_ZERO = 0xFFFFFFFFu;
-
-// exclusive prefix of one value per thread over a block of NW waves; *total = the block's sum. wsum: >= NW LDS words that nobody else
-// touches until the next barrier after the call. One barrier inside.
-template <int NW>
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* wsum, uint32_t* total) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  uint32_t incl = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t up = (uint32_t)__shfl_up((int)incl, d);
-    if (lane >= d) incl += up;
-  }
-  if (lane == 63) wsum[wv] = incl;
-  __syncthreads();
-  uint32_t base = 0, tot = 0;
-#pragma unroll
-  for (int i = 0; i < NW; ++i) {
-    const uint32_t t = wsum[i];
-    if (i < wv) base += t;
-    tot += t;
-  }
-  *total = tot;
-  return base + incl - v;
-}
 
 // Signed-digit codes of scalar i: code[w] = (bucket - 1) | negative << 31, WCODE_ZERO for a zero digit. Same recoding as k_msm_digits /
 // for_each_digit (uniform c-bit windows; the table rows are 2^(c w) P). The window width CB is a template parameter: digit w sits at
@@ -229,7 +203,6 @@ template <class Fr, int CB, int REC>
 __global__ __launch_bounds__(WS_BLK) void k_wide_scatter1(const Fr* __restrict__ scalars, MsmParams pd, MsmParams p, WidePlan wp,
                                                           const uint32_t* __restrict__ part_pre, const uint32_t* __restrict__ part_start,
                                                           void* __restrict__ inter) {
-  using Rec = typename std::conditional<REC != 0, uint32_t, uint64_t>::type;
   extern __shared__ uint32_t wl[];
   const uint32_t P = wp.P, tid = threadIdx.x;
   constexpr int W = WideWin<Fr, CB>::W;
@@ -250,7 +223,7 @@ __global__ __launch_bounds__(WS_BLK) void k_wide_scatter1(const Fr* __restrict__
   __syncthreads();
   const uint32_t per = (P + WS_BLK - 1) / WS_BLK;  // counters per thread in the scan: <= 16
   const uint32_t b0 = tid * per;
-  Rec* out = reinterpret_cast<Rec*>(inter);
+  SortRec<REC>* out = reinterpret_cast<SortRec<REC>*>(inter);
   const uint32_t lbmask = (1u << wp.lb) - 1;
   uint32_t t1 = (ch + 1) * wp.chunk_tiles;
   if (t1 > wp.n_tiles) t1 = wp.n_tiles;
@@ -289,13 +262,7 @@ __global__ __launch_bounds__(WS_BLK) void k_wide_scatter1(const Fr* __restrict__
     __syncthreads();
     for (uint32_t sl = tid; sl < tile_n; sl += WS_BLK) {
       const uint32_t k0 = key[sl], bin = k0 >> wp.lb;
-      const uint32_t dst = gcur[bin] + (sl - cnt[bin]);
-      if constexpr (REC == 1) {
-        const uint32_t idb = 31 - wp.lb;
-        out[dst] = (pay[sl] & ((1u << idb) - 1)) | ((pay[sl] >> 31) << idb) | ((k0 & lbmask) << (idb + 1));
-      } else {
-        out[dst] = (uint64_t)pay[sl] | ((uint64_t)(k0 & lbmask) << 32);
-      }
+      out[gcur[bin] + (sl - cnt[bin])] = rec_pack<REC>(pay[sl], k0 & lbmask, wp.lb);
     }
     __syncthreads();
 #pragma unroll
@@ -310,21 +277,6 @@ __global__ __launch_bounds__(WS_BLK) void k_wide_scatter1(const Fr* __restrict__
 }
 
 // ---- level 2 ------------------------------------------------------------------------------------------------------------------
-template <int REC>
-__device__ __forceinline__ uint32_t rec_sub(typename std::conditional<REC != 0, uint32_t, uint64_t>::type e, uint32_t lb) {
-  if constexpr (REC == 1) return e >> (32 - lb);
-  else return (uint32_t)(e >> 32);
-}
-template <int REC>
-__device__ __forceinline__ uint32_t rec_entry(typename std::conditional<REC != 0, uint32_t, uint64_t>::type e, uint32_t lb) {
-  if constexpr (REC == 1) {
-    const uint32_t idb = 31 - lb;
-    return (e & ((1u << idb) - 1)) | (((e >> idb) & 1u) << 31);
-  } else {
-    return (uint32_t)e;
-  }
-}
-
 struct WideJob {
   uint32_t part, lo, hi;
 };
@@ -345,22 +297,15 @@ __device__ __forceinline__ WideJob wide_job(const uint32_t* __restrict__ job_fir
 template <int REC>
 __global__ __launch_bounds__(W2_BLK) void k_wide_hist2(WidePlan wp, const uint32_t* __restrict__ job_first, const uint32_t* __restrict__ job_part,
                                                        const uint32_t* __restrict__ part_start, const void* __restrict__ inter, uint32_t* cursor) {
-  using Rec = typename std::conditional<REC != 0, uint32_t, uint64_t>::type;
   extern __shared__ uint32_t w2_cnt[];  // B2
   const uint32_t tid = threadIdx.x;
   const WideJob jb = wide_job(job_first, job_part, part_start, wp.P, blockIdx.x);
   if (jb.part == 0xffffffffu) return;
   for (uint32_t b = tid; b < wp.B2; b += W2_BLK) w2_cnt[b] = 0;
   __syncthreads();
-  const Rec* in = reinterpret_cast<const Rec*>(inter);
-  Rec e[W2_EPT];
-#pragma unroll
-  for (int k = 0; k < W2_EPT; ++k) {
-    const uint32_t i = jb.lo + k * W2_BLK + tid;
-    e[k] = i < jb.hi ? __builtin_nontemporal_load(in + i) : 0;
-  }
-#pragma unroll
-  for (int k = 0; k < W2_EPT; ++k) (void)lds_slot(w2_cnt, rec_sub<REC>(e[k], wp.lb), jb.lo + k * W2_BLK + tid < jb.hi);
+  SortRec<REC> e[W2_EPT];
+  uint32_t rank[W2_EPT];  // not needed here
+  l2_load_rank<REC>(reinterpret_cast<const SortRec<REC>*>(inter), jb.lo, jb.hi, wp.lb, w2_cnt, e, rank);
   __syncthreads();
   uint32_t* cur = cursor + 1 + (size_t)jb.part * wp.B2;
   for (uint32_t b = tid; b < wp.B2; b += W2_BLK) {
@@ -398,7 +343,6 @@ template <int REC>
 __global__ __launch_bounds__(W2_BLK) void k_wide_scatter2(WidePlan wp, const uint32_t* __restrict__ job_first, const uint32_t* __restrict__ job_part,
                                                           const uint32_t* __restrict__ part_start, const void* __restrict__ inter, uint32_t* cursor,
                                                           uint32_t* __restrict__ sorted) {
-  using Rec = typename std::conditional<REC != 0, uint32_t, uint64_t>::type;
   extern __shared__ uint32_t w2[];
   const uint32_t tid = threadIdx.x, B2 = wp.B2;
   uint32_t* cnt = w2;              // B2: tile histogram, then tile-local exclusive offsets
@@ -410,16 +354,9 @@ __global__ __launch_bounds__(W2_BLK) void k_wide_scatter2(WidePlan wp, const uin
   if (jb.part == 0xffffffffu) return;
   for (uint32_t b = tid; b < B2; b += W2_BLK) cnt[b] = 0;
   __syncthreads();
-  const Rec* in = reinterpret_cast<const Rec*>(inter);
-  Rec e[W2_EPT];
+  SortRec<REC> e[W2_EPT];
   uint32_t rank[W2_EPT];
-#pragma unroll
-  for (int k = 0; k < W2_EPT; ++k) {
-    const uint32_t i = jb.lo + k * W2_BLK + tid;
-    e[k] = i < jb.hi ? __builtin_nontemporal_load(in + i) : 0;
-  }
-#pragma unroll
-  for (int k = 0; k < W2_EPT; ++k) rank[k] = lds_slot(cnt, rec_sub<REC>(e[k], wp.lb), jb.lo + k * W2_BLK + tid < jb.hi);
+  l2_load_rank<REC>(reinterpret_cast<const SortRec<REC>*>(inter), jb.lo, jb.hi, wp.lb, cnt, e, rank);
   __syncthreads();
   {
     uint32_t* cur = cursor + 1 + (size_t)jb.part * B2;
@@ -446,7 +383,7 @@ __global__ __launch_bounds__(W2_BLK) void k_wide_scatter2(WidePlan wp, const uin
 #pragma unroll
   for (int k = 0; k < W2_EPT; ++k) {
     if (jb.lo + k * W2_BLK + tid < jb.hi) {
-      const uint32_t bin = rec_sub<REC>(e[k], wp.lb);
+      const uint32_t bin = rec_low<REC>(e[k], wp.lb);
       const uint32_t slot = cnt[bin] + rank[k];
       pay[slot] = rec_entry<REC>(e[k], wp.lb);
       sbin[slot] = (uint16_t)bin;
@@ -488,18 +425,50 @@ WidePlan msm_wide_plan(const MsmParams& srt, const MsmParams& dig) {
   return wp;
 }
 
-size_t msm_sort_wide_bytes(const MsmParams& srt, const MsmParams& dig) {
-  const WidePlan wp = msm_wide_plan(srt, dig);
+// Scratch of the stage, taken from `ar` in this order; msm_sort_wide_bytes is the same list run on an arena without memory
+struct WideBufs {
+  uint32_t *cursor, *start, *nlanes, *sorted;
+  void* inter;           // intermediate records
+  uint32_t* part_cnt;    // entries per (chunk, partition)
+  uint32_t *part_start, *job_first;  // partition starts, first job per partition
+  uint32_t* job_part;    // job -> partition
+};
+static WideBufs wide_take(const MsmParams& srt, const WidePlan& wp, Arena& ar) {
+  WideBufs b;
   const size_t len = (size_t)srt.NB + 2;
-  size_t need = 0;
-  need += 2 * Arena::padded(sizeof(uint32_t) * len);                       // cursor, start
-  need += Arena::padded(sizeof(uint32_t) * MAX_WINDOWS);                   // nlanes
-  need += Arena::padded(sizeof(uint32_t) * (size_t)srt.n);                 // sorted
-  need += Arena::padded((wp.rec4 ? sizeof(uint32_t) : sizeof(uint64_t)) * (size_t)srt.n);  // intermediate records
-  need += Arena::padded(sizeof(uint32_t) * (size_t)wp.CH * wp.P);          // entries per (chunk, partition)
-  need += 2 * Arena::padded(sizeof(uint32_t) * ((size_t)wp.P + 1));        // partition starts, first job per partition
-  need += Arena::padded(sizeof(uint32_t) * (size_t)wp.jobs_max);           // job -> partition
-  return need;
+  b.cursor = ar.take<uint32_t>(len);
+  b.start = ar.take<uint32_t>(len);
+  b.nlanes = ar.take<uint32_t>(MAX_WINDOWS);
+  b.sorted = ar.take<uint32_t>(srt.n);
+  b.inter = wp.rec4 ? (void*)ar.take<uint32_t>(srt.n) : (void*)ar.take<uint64_t>(srt.n);
+  b.part_cnt = ar.take<uint32_t>((size_t)wp.CH * wp.P);
+  b.part_start = ar.take<uint32_t>((size_t)wp.P + 1);
+  b.job_first = ar.take<uint32_t>((size_t)wp.P + 1);
+  b.job_part = ar.take<uint32_t>(wp.jobs_max);
+  return b;
+}
+
+size_t msm_sort_wide_bytes(const MsmParams& srt, const MsmParams& dig) {
+  Arena sizing;  // no memory behind it: take() only advances off
+  wide_take(srt, msm_wide_plan(srt, dig), sizing);
+  return sizing.off;
+}
+
+// level-1 scatter and level 2 with 4-byte (REC = 1) or 8-byte intermediate records
+template <class Fr, int CB, int REC>
+static int wide_launch_rec(const MsmParams& p, const MsmParams& pd, const WidePlan& wp, const WideBufs& b, const Fr* sc, size_t lds1, hipStream_t st,
+                           hipEvent_t* ev) {
+  const size_t lds2 = sizeof(uint32_t) * (2 * (size_t)wp.B2 + 16 + W2_TILE) + sizeof(uint16_t) * W2_TILE;
+  CSH_TRY(raise_lds_limit((const void*)k_wide_scatter1<Fr, CB, REC>, 160 * 1024));
+  CSH_TRY(raise_lds_limit((const void*)k_wide_scatter2<REC>, 160 * 1024));
+  hipLaunchKernelGGL((k_wide_scatter1<Fr, CB, REC>), dim3(wp.CH), dim3(WS_BLK), lds1, st, sc, pd, p, wp, b.part_cnt, b.part_start, b.inter);
+  if (ev) CSH_HIP(hipEventRecord(ev[1], st));
+  hipLaunchKernelGGL(k_wide_hist2<REC>, dim3(wp.jobs_max), dim3(W2_BLK), sizeof(uint32_t) * wp.B2, st, wp, b.job_first, b.job_part, b.part_start, b.inter, b.cursor);
+  hipLaunchKernelGGL(k_wide_scan2, dim3(wp.P), dim3(256), 0, st, wp, b.part_start, b.cursor, b.start);
+  if (ev) CSH_HIP(hipEventRecord(ev[2], st));
+  hipLaunchKernelGGL(k_wide_scatter2<REC>, dim3(wp.jobs_max), dim3(W2_BLK), lds2, st, wp, b.job_first, b.job_part, b.part_start, b.inter, b.cursor, b.sorted);
+  if (ev) CSH_HIP(hipEventRecord(ev[3], st));
+  return CSH_OK;
 }
 
 template <class Fr, int CB>
@@ -508,42 +477,19 @@ static int wide_launch_t(const MsmParams& p, const MsmParams& pd, const uint64_t
   constexpr int WIN = WideWin<Fr, CB>::W;
   CSH_REQUIRE(pd.W == WIN, "wide sort: the plan's window count does not match the scalar field");
   const WidePlan wp = msm_wide_plan(p, pd);
-  const size_t len = (size_t)p.NB + 2;
-  uint32_t* cursor = ar.take<uint32_t>(len);
-  uint32_t* start = ar.take<uint32_t>(len);
-  uint32_t* nlanes = ar.take<uint32_t>(MAX_WINDOWS);
-  uint32_t* sorted = ar.take<uint32_t>(p.n);
-  void* inter = wp.rec4 ? (void*)ar.take<uint32_t>(p.n) : (void*)ar.take<uint64_t>(p.n);
-  uint32_t* part_cnt = ar.take<uint32_t>((size_t)wp.CH * wp.P);
-  uint32_t* part_start = ar.take<uint32_t>((size_t)wp.P + 1);
-  uint32_t* job_first = ar.take<uint32_t>((size_t)wp.P + 1);
-  uint32_t* job_part = ar.take<uint32_t>(wp.jobs_max);
+  const WideBufs b = wide_take(p, wp, ar);
   const Fr* sc = reinterpret_cast<const Fr*>(scalars_dev);
   const size_t lds1 = sizeof(uint32_t) * (2 * (size_t)wp.P + 16 + 2 * (size_t)WS_BLK * pd.W);
-  const size_t lds2 = sizeof(uint32_t) * (2 * (size_t)wp.B2 + 16 + W2_TILE) + sizeof(uint16_t) * W2_TILE;
-  CSH_TRY(raise_lds_limit((const void*)k_wide_scatter1<Fr, CB, 0>, 160 * 1024));
-  CSH_TRY(raise_lds_limit((const void*)k_wide_scatter1<Fr, CB, 1>, 160 * 1024));
-  CSH_TRY(raise_lds_limit((const void*)k_wide_scatter2<0>, 160 * 1024));
-  CSH_TRY(raise_lds_limit((const void*)k_wide_scatter2<1>, 160 * 1024));
   CSH_REQUIRE(lds1 <= 160 * 1024, "wide sort: level-1 tile does not fit the LDS");
-  hipLaunchKernelGGL((k_wide_hist1<Fr, CB>), dim3(wp.CH), dim3(WS_BLK), sizeof(uint32_t) * wp.P, st, sc, pd, wp, part_cnt, cursor, (uint32_t)len);
-  hipLaunchKernelGGL(k_wide_colscan, dim3((wp.P + 31) / 32), dim3(1024), 0, st, wp, part_cnt, part_start);
-  hipLaunchKernelGGL(k_wide_partscan, dim3(1), dim3(1024), 0, st, p, wp, part_start, job_first, start, cursor, nlanes);
-  hipLaunchKernelGGL(k_wide_jobs, dim3((wp.jobs_max + 1023) / 1024), dim3(1024), sizeof(uint32_t) * ((size_t)wp.P + 1), st, wp, job_first, job_part);
-  if (wp.rec4) hipLaunchKernelGGL((k_wide_scatter1<Fr, CB, 1>), dim3(wp.CH), dim3(WS_BLK), lds1, st, sc, pd, p, wp, part_cnt, part_start, inter);
-  else hipLaunchKernelGGL((k_wide_scatter1<Fr, CB, 0>), dim3(wp.CH), dim3(WS_BLK), lds1, st, sc, pd, p, wp, part_cnt, part_start, inter);
-  if (ev) CSH_HIP(hipEventRecord(ev[1], st));
-  if (wp.rec4) hipLaunchKernelGGL(k_wide_hist2<1>, dim3(wp.jobs_max), dim3(W2_BLK), sizeof(uint32_t) * wp.B2, st, wp, job_first, job_part, part_start, inter, cursor);
-  else hipLaunchKernelGGL(k_wide_hist2<0>, dim3(wp.jobs_max), dim3(W2_BLK), sizeof(uint32_t) * wp.B2, st, wp, job_first, job_part, part_start, inter, cursor);
-  hipLaunchKernelGGL(k_wide_scan2, dim3(wp.P), dim3(256), 0, st, wp, part_start, cursor, start);
-  if (ev) CSH_HIP(hipEventRecord(ev[2], st));
-  if (wp.rec4) hipLaunchKernelGGL(k_wide_scatter2<1>, dim3(wp.jobs_max), dim3(W2_BLK), lds2, st, wp, job_first, job_part, part_start, inter, cursor, sorted);
-  else hipLaunchKernelGGL(k_wide_scatter2<0>, dim3(wp.jobs_max), dim3(W2_BLK), lds2, st, wp, job_first, job_part, part_start, inter, cursor, sorted);
-  if (ev) CSH_HIP(hipEventRecord(ev[3], st));
+  hipLaunchKernelGGL((k_wide_hist1<Fr, CB>), dim3(wp.CH), dim3(WS_BLK), sizeof(uint32_t) * wp.P, st, sc, pd, wp, b.part_cnt, b.cursor, p.NB + 2);
+  hipLaunchKernelGGL(k_wide_colscan, dim3((wp.P + 31) / 32), dim3(1024), 0, st, wp, b.part_cnt, b.part_start);
+  hipLaunchKernelGGL(k_wide_partscan, dim3(1), dim3(1024), 0, st, p, wp, b.part_start, b.job_first, b.start, b.cursor, b.nlanes);
+  hipLaunchKernelGGL(k_wide_jobs, dim3((wp.jobs_max + 1023) / 1024), dim3(1024), sizeof(uint32_t) * ((size_t)wp.P + 1), st, wp, b.job_first, b.job_part);
+  CSH_TRY(wp.rec4 ? (wide_launch_rec<Fr, CB, 1>(p, pd, wp, b, sc, lds1, st, ev)) : (wide_launch_rec<Fr, CB, 0>(p, pd, wp, b, sc, lds1, st, ev)));
   CSH_HIP(hipGetLastError());
-  *out_start = start;
-  *out_nlanes = nlanes;
-  *out_sorted = sorted;
+  *out_start = b.start;
+  *out_nlanes = b.nlanes;
+  *out_sorted = b.sorted;
   return CSH_OK;
 }
 
