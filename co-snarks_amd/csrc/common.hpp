@@ -136,7 +136,6 @@ struct Domain;
 int ntt_run(const Domain* d, uint64_t* data, uint32_t ncomp, bool dif, hipStream_t st);
 int ntt_coset_table(const Domain* d, const uint64_t* shift, uint64_t* out_dev, hipStream_t st);
 bool ntt_scale_table_supported(const Domain* d);
-int ntt_run_dif_table(const Domain* d, uint64_t* data, uint32_t ncomp, const uint64_t* scale_table, hipStream_t st);
 int ntt_run_pair_table(const Domain* d, uint64_t* data, uint32_t ncomp, const uint64_t* scale_table, hipStream_t st);  // ifft (scaled by the table) + fft, tile passes fused
 int ntt_coset_table_scaled(const Domain* d, const uint64_t* shift, uint64_t* out_dev, hipStream_t st);
 int ntt_coset_table_scaled_cached(const Domain* d, const uint64_t* shift, uint64_t* scratch, hipStream_t st, const uint64_t** table);

@@ -1,4 +1,4 @@
-// Radix-2 NTT over Fr (BN254 / BLS12-381) on gfx950, LDS-tiled multi-pass.
+// Radix-2 NTT over Fr (BN254 / BLS12-381 / BLS12-377) on gfx950, LDS-tiled multi-pass.
 //
 // Conventions (the reference's taceo_ark_algebra::fft::Domain, see include/cosnarks_hip.h):
 //   fft_out_to_in : bit-reversed coefficients -> natural-order evaluations   (decimation in time)
@@ -7,14 +7,17 @@
 //
 // A pass executes stages [s0, s0+k) for one tile entirely in LDS: the tile is the 2^k stage-bit values
 // x 2^cb low "column" entries x ncomp components (ncomp = 2 for Rep3 shares), so every HBM access is a
-// contiguous run of 2^cb * ncomp * 32 bytes (>= 256 B) and a 2^22 transform needs 3 read+write sweeps.
-// Default path: butterflies in the signed lazy 9 x 29-bit field (k_ntt_pass_lazy, limb-major LDS arrays); the 32-bit
-// CIOS pass (k_ntt_pass: two 16-byte halves per element, conflict-free ds_read/write_b128) remains selectable with
-// CSH_NTT_LAZY=0 for A/B measurements.
+// contiguous run of 2^cb * ncomp * 32 bytes (>= 64 B) and a 2^22 transform needs 3 read+write sweeps.
+// Default path: butterflies in the signed lazy 9 x 29-bit field (limb-major LDS arrays), as radix-2 stages (k_ntt_pass_lazy) or as
+// radix-4 rounds (k_ntt_pass_r4, transforms of >= 2^20 points); the 32-bit CIOS pass (k_ntt_pass: two 16-byte halves per element,
+// conflict-free ds_read/write_b128) remains selectable with CSH_NTT_LAZY=0 for A/B measurements.
+// Host side: a transform is planned ONCE per public call (NttPlan: one read of every tune knob, the pass list) and every launch of
+// the call goes through launch_pass with that plan.
 // the butterflies' products run with the pinned multiply-add order (field29.hpp): -5.5 % per transform, 52-61 VGPRs as before
 #define CSH_PIN_MADS 3
 #include <stdlib.h>
 
+#include <memory>
 #include <mutex>
 #include <string.h>
 #include <type_traits>
@@ -33,10 +36,10 @@ struct Domain {
   int device;
   uint32_t log_n;
   size_t n;
-  void* tw_fwd;  // w^j, j < n/2
-  void* tw_inv;  // w^-j
-  void* tw_fwd_lazy;  // the powers the lazy butterflies use, as packed canonical w^j * R' (R' = 2^261), one contiguous run per stage
-  void* tw_inv_lazy;
+  void* tw_fwd = nullptr;  // w^j, j < n/2
+  void* tw_inv = nullptr;  // w^-j
+  void* tw_fwd_lazy = nullptr;  // the powers the lazy butterflies use, as packed canonical w^j * R' (R' = 2^261), one contiguous run per stage
+  void* tw_inv_lazy = nullptr;
   uint32_t n_inv_lazy[8];  // (1/n) * R', packed
   uint32_t gen[8], gen_inv[8], n_inv[8];  // Montgomery
   // The scaled coset table of the witness map (shift^i / n, ntt_coset_table_scaled) for the FIRST shift the domain is asked for: a reduction
@@ -46,6 +49,60 @@ struct Domain {
   uint64_t cs_shift[4] = {0, 0, 0, 0};
   void* cs_table = nullptr;
   hipEvent_t cs_ready = nullptr;
+
+  Domain() = default;
+  Domain(const Domain&) = delete;
+  Domain& operator=(const Domain&) = delete;
+  void release_natural_tables() {
+    if (tw_fwd) (void)hipFree(tw_fwd);
+    if (tw_inv) (void)hipFree(tw_inv);
+    tw_fwd = tw_inv = nullptr;
+  }
+  ~Domain() {  // the one place that knows what a domain owns
+    release_natural_tables();
+    if (tw_fwd_lazy) (void)hipFree(tw_fwd_lazy);
+    if (tw_inv_lazy) (void)hipFree(tw_inv_lazy);
+    if (cs_table) (void)hipFree(cs_table);
+    if (cs_ready) (void)hipEventDestroy(cs_ready);
+  }
+};
+
+// What one pass launch is told (by value to k_ntt_pass_r4 and k_ntt_pass, field by field to k_ntt_pass_lazy, see there). One pass = stages [s0, s0+k) of a size-2^L transform over tiles of 2^k x 2^cb entries of
+// 2^ncomp_log elements. Every field is a run-time, wave-uniform value.
+template <class F>
+struct PassArgs {
+  // (what a kernel reads before its first global load comes first and contiguous: the wavefront fetches it in one batch of scalar loads)
+  F* data;
+  const F* tw;         // the pass's twiddle table: staged w * R' (lazy kernels), natural-order Montgomery (32-bit pass)
+  const F* tw_fwd;     // PAIR only: the staged table of the forward transform that follows
+  const F* scale_tbl;  // lazy kernels: per-entry factor that replaces `scale` (1/n times the coset power), or NULL
+  int L, s0, k, cb, ncomp_log;
+  int swz_mask;        // LazyLds bank swizzle: 31, or 0 = off (tune "ntt_variant" bit 11, A/B runs)
+  bool scale_out;      // multiply by the scale on store (last pass of an inverse transform)
+  bool unit_rounds;    // global stage 0 (and 1 in the radix-4 rounds) skips its unit-twiddle multiplications (tune "ntt_variant" bit 20 = off)
+#ifdef CSH_EXPERIMENTS
+  int ablate;          // k_ntt_pass_r4 timing experiments (tune "ntt_variant" bits 16-19, WRONG RESULTS): 1 = no butterfly rounds, 2 = no global
+                       // loads, 4 = no stores, 8 = no canonicalisation before the store
+#endif
+  F scale;             // 1/n, in the form of the kernel's multiplication (times R' for the lazy kernels)
+};
+
+// Tile <-> vector index map of a pass: LDS entry e = t * CC + cc (t: the k stage bits, cc: column and component, CC = 2^(cb + ncomp_log))
+// is global element (((hi << k | t) << mid_bits | mid) * CC + cc, where tile = (hi << mid_bits) | mid and mid_bits = s0 - cb. With
+// s0 = cb = 0 (the pass over the contiguous tiles) this is tile * E + e.
+struct TileMap {
+  int s0, k, cb, cc_log, ncomp_log, mid_bits;
+  size_t mid, hi;
+  __device__ __forceinline__ TileMap(size_t tile, int s0_, int k_, int cb_, int ncomp_log_)
+      : s0(s0_), k(k_), cb(cb_), cc_log(cb_ + ncomp_log_), ncomp_log(ncomp_log_), mid_bits(s0_ - cb_), mid(tile & ((size_t(1) << (s0_ - cb_)) - 1)), hi(tile >> (s0_ - cb_)) {}
+  __device__ __forceinline__ int entries() const { return 1 << (k + cc_log); }
+  __device__ __forceinline__ size_t global_index(int e) const {
+    const int cc = e & ((1 << cc_log) - 1);
+    const size_t t = e >> cc_log;
+    return (((((hi << k) | t) << mid_bits) | mid) << cc_log) + cc;
+  }
+  // i mod 2^s, s = s0 + q, of the butterfly whose lower entry has local stage bits t_lo (< 2^q) and column / component cc: (t_lo << s0) | (mid << cb) | col
+  __device__ __forceinline__ size_t index_mod_stage(int t_lo, int cc) const { return ((size_t)t_lo << s0) | (mid << cb) | (size_t)(cc >> ncomp_log); }
 };
 
 template <class F>
@@ -63,38 +120,28 @@ __device__ __forceinline__ void lds_put(uint4* lo, uint4* hi, int e, const F& f)
   hi[e] = u.q[1];
 }
 
-// One pass = stages [s0, s0+k) of a size-2^L transform. CC = 2^cb * ncomp contiguous elements.
+// The 32-bit pass (independent arithmetic: CIOS Montgomery on 8 x u32, natural-order twiddle table).
 template <class F, bool DIF>
-__global__ __launch_bounds__(NTT_MAX_THREADS) void k_ntt_pass(F* __restrict__ data, const F* __restrict__ tw, int L, int s0, int k,
-                                                          int cb, int ncomp_log, F scale, int do_scale) {
+__global__ __launch_bounds__(NTT_MAX_THREADS) void k_ntt_pass(const PassArgs<F> a) {
   static_assert(sizeof(F) == 32, "Fr is 8 x u32");
   extern __shared__ uint4 lds_raw[];
-  const int cc_log = cb + ncomp_log;
+  const TileMap map(blockIdx.x, a.s0, a.k, a.cb, a.ncomp_log);
+  const int cc_log = map.cc_log;
   const int CC = 1 << cc_log;
-  const int E = 1 << (k + cc_log);
+  const int E = map.entries();
   uint4* lo = lds_raw;
   uint4* hi = lds_raw + E;
-  const int mid_bits = s0 - cb;
-  const size_t tile = blockIdx.x;
-  const size_t mid = tile & ((size_t(1) << mid_bits) - 1);
-  const size_t hi_idx = tile >> mid_bits;
   const int tid = threadIdx.x;
   const int NTT_THREADS = blockDim.x;
 
-  // gather tile: lds index e = t * CC + cc ; global element = (((hi << k | t) << mid_bits | mid) * CC + cc
-  for (int e = tid; e < E; e += NTT_THREADS) {
-    const int cc = e & (CC - 1);
-    const size_t t = e >> cc_log;
-    const size_t g = ((((hi_idx << k) | t) << mid_bits) | mid) * CC + cc;
-    lds_put<F>(lo, hi, e, data[g]);
-  }
+  for (int e = tid; e < E; e += NTT_THREADS) lds_put<F>(lo, hi, e, a.data[map.global_index(e)]);
   __syncthreads();
 
   const int half_E = E >> 1;
-  for (int qq = 0; qq < k; ++qq) {
-    const int q = DIF ? (k - 1 - qq) : qq;  // local stage; global stage s = s0 + q
+  for (int qq = 0; qq < a.k; ++qq) {
+    const int q = DIF ? (a.k - 1 - qq) : qq;  // local stage; global stage s = s0 + q
     const int half = 1 << q;
-    const int tw_shift = L - 1 - (s0 + q);
+    const int tw_shift = a.L - 1 - (a.s0 + q);
     for (int bidx = tid; bidx < half_E; bidx += NTT_THREADS) {
       const int cc = bidx & (CC - 1);
       const int tb = bidx >> cc_log;
@@ -102,9 +149,7 @@ __global__ __launch_bounds__(NTT_MAX_THREADS) void k_ntt_pass(F* __restrict__ da
       const int t0 = ((tb >> q) << (q + 1)) | t_lo;
       const int e0 = (t0 << cc_log) | cc;
       const int e1 = e0 + (half << cc_log);
-      // i mod 2^s with s = s0+q: (t_lo << s0) | (mid << cb) | col
-      const size_t imod = ((size_t)t_lo << s0) | (mid << cb) | (size_t)(cc >> ncomp_log);
-      const F w = tw[imod << tw_shift];
+      const F w = a.tw[map.index_mod_stage(t_lo, cc) << tw_shift];
       F u = lds_get<F>(lo, hi, e0);
       F v = lds_get<F>(lo, hi, e1);
       if (DIF) {
@@ -122,12 +167,9 @@ __global__ __launch_bounds__(NTT_MAX_THREADS) void k_ntt_pass(F* __restrict__ da
   }
 
   for (int e = tid; e < E; e += NTT_THREADS) {
-    const int cc = e & (CC - 1);
-    const size_t t = e >> cc_log;
-    const size_t g = ((((hi_idx << k) | t) << mid_bits) | mid) * CC + cc;
     F f = lds_get<F>(lo, hi, e);
-    if (do_scale) f = F::mul(f, scale);
-    data[g] = f;
+    if (a.scale_out) f = F::mul(f, a.scale);
+    a.data[map.global_index(e)] = f;
   }
 }
 
@@ -192,36 +234,28 @@ struct LazyLds {
   }
 };
 
-template <class F, class LZ, bool DIF>
-__global__ __launch_bounds__(NTT_MAX_THREADS) __attribute__((amdgpu_waves_per_eu(8))) void k_ntt_pass_lazy(F* __restrict__ data, const F* __restrict__ twl, int L, int s0, int k, int cb,
-                                                                    int ncomp_log, F scale_lazy, int do_scale, const F* __restrict__ scale_tbl) {
-  extern __shared__ uint4 lds_raw[];
-  const int cc_log = cb + ncomp_log;
-  const int CC = 1 << cc_log;
-  const int E = 1 << (k + cc_log);
-  const LazyLds<LZ> lds{reinterpret_cast<int32_t*>(lds_raw), E, (do_scale & 0x1000) ? 0 : 31};
-  const bool unit_skip = !(do_scale & 0x2000);  // stage 0 of the whole transform has twiddle 1 everywhere: no multiplication (see k_ntt_pass_r4)
-  do_scale &= 1;
-  const int mid_bits = s0 - cb;
-  const size_t tile = blockIdx.x;
-  const size_t mid = tile & ((size_t(1) << mid_bits) - 1);
-  const size_t hi_idx = tile >> mid_bits;
+// ---- pieces shared by the lazy kernels ----------------------------------------------------------------------------
+// twiddle of global stage s0 + q for the pair whose lower index has local stage bits t_lo (< 2^q); staged table: stage s starts at 2^s - 1
+template <class F, class LZ>
+__device__ __forceinline__ LZ staged_twiddle(const F* __restrict__ tw, const TileMap& map, int L, int q, int t_lo, int cc) {
+  return load_sliced_twiddle<F, LZ>(tw, ((size_t(1) << (map.s0 + q)) - 1) + map.index_mod_stage(t_lo, cc), (size_t(1) << L) - 1);
+}
+
+// Tile load, four entries per lane with all four global loads issued before the first is consumed: written as one rolled loop
+// (load, unpack, put per iteration) every lane paid four SERIAL trips to HBM per tile -- the 0.04-0.05 ms per sweep that no butterfly
+// stage accounts for (profiles/archive/r04_e_ntt_per_pass.log; shortening the store tail by a third changed nothing, r04_l_ntt.log).
+// `fill` (timing experiments only): the value every entry takes instead of its global load.
+template <class F, class LZ>
+__device__ __forceinline__ void load_tile(const LazyLds<LZ>& lds, const TileMap& map, const F* __restrict__ data, const F* fill = nullptr) {
+  const int E = lds.E;
   const int tid = threadIdx.x;
   const int NT = blockDim.x;
-
-  // Tile load, four entries per lane with all four global loads issued before the first is consumed: written as one rolled loop
-  // (load, unpack, put per iteration) every lane paid four SERIAL trips to HBM per tile -- the 0.04-0.05 ms per sweep that no butterfly
-  // stage accounts for (profiles/archive/r04_e_ntt_per_pass.log; shortening the store tail by a third changed nothing, r04_l_ntt.log).
   for (int base = 0; base < E; base += 4 * NT) {
     F raw[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int e = base + tid + i * NT;
-      if (e < E) {
-        const int cc = e & (CC - 1);
-        const size_t t = e >> cc_log;
-        raw[i] = data[((((hi_idx << k) | t) << mid_bits) | mid) * CC + cc];
-      }
+      if (e < E) raw[i] = fill ? *fill : data[map.global_index(e)];
     }
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -230,84 +264,108 @@ __global__ __launch_bounds__(NTT_MAX_THREADS) __attribute__((amdgpu_waves_per_eu
     }
   }
   __syncthreads();
+}
 
-  const int half_E = E >> 1;
-  // One butterfly stage over the tile. NORM: run the parallel carry step on the decimation-in-time outputs. x is a fresh
-  // product (limbs < 2^B) and u +- x of a normalised u is a two-term sum, still an admissible `a` operand of the next
-  // stage's product, so the carry step is only needed every second stage (and not after the last one: the tile leaves
-  // through mul / canonical_wide, which take two-term limbs).
-  auto stage = [&](int q, auto norm_tag) {
-    constexpr bool NORM = decltype(norm_tag)::value;
-    const int half = 1 << q;
-    const size_t stage_base = (size_t(1) << (s0 + q)) - 1;
-    for (int bidx = tid; bidx < half_E; bidx += NT) {
-      const int cc = bidx & (CC - 1);
-      const int tb = bidx >> cc_log;
-      const int t_lo = tb & (half - 1);
-      const int t0 = ((tb >> q) << (q + 1)) | t_lo;
-      const int e0 = (t0 << cc_log) | cc;
-      const int e1 = e0 + (half << cc_log);
-      const size_t imod = ((size_t)t_lo << s0) | (mid << cb) | (size_t)(cc >> ncomp_log);
-#if defined(CSH_EXPERIMENTS) && defined(CSH_NTT_ABLATE_TW)  // ablation builds only (tools/experiments/gpu_r3_h.sh): one of 64 table entries -- wrong results, no gather
-      const LZ w = load_sliced_twiddle<F, LZ>(twl, imod & 63, (size_t(1) << L) - 1);
-#else
-      const LZ w = load_sliced_twiddle<F, LZ>(twl, stage_base + imod, (size_t(1) << L) - 1);  // staged table: stage s0 + q starts at 2^(s0 + q) - 1
-#endif
-      const LZ u = lds.get(e0);
-      const LZ v = lds.get(e1);
-      if (unit_skip && s0 + q == 0) {  // w = 1 for every butterfly of global stage 0 (wave-uniform branch)
-        if (DIF) {
-          lds.put(e0, LZ::add(u, v).fold_top());
-          lds.put(e1, LZ::sub(u, v));            // the pass's last stage: leaves through mul / canonical_wide, which take two-term limbs
-        } else {
-          lds.put(e0, LZ::add(u, v));            // the pass's first stage: u, v are unpack() outputs, the sums two-term operands as after a product
-          lds.put(e1, LZ::sub(u, v));
-        }
-        continue;
-      }
+// the factor of global element g on the way out: the 1/n of the inverse transform (sc), or -- witness maps -- a per-entry table that
+// already carries it (1/n times the coset power of the entry, in the pass's output order): the coset shift costs no sweep and no
+// multiplication of its own
+template <class F, class LZ>
+__device__ __forceinline__ LZ out_scale(const PassArgs<F>& a, const LZ& sc, size_t g) {
+  return a.scale_tbl ? LZ::unpack(a.scale_tbl[g >> a.ncomp_log]) : sc;
+}
+
+// Store tail: every entry scaled (scale_out), brought back to [0, p) and packed. ablate (timing experiments only): 4 = no stores,
+// 8 = no canonicalisation.
+template <class F, class LZ>
+__device__ __forceinline__ void store_tile(const LazyLds<LZ>& lds, const TileMap& map, const PassArgs<F>& a, bool scale_out, int ablate = 0) {
+  const LZ sc = LZ::unpack(a.scale);
+  for (int e = threadIdx.x; e < lds.E; e += blockDim.x) {
+    const size_t g = map.global_index(e);
+    LZ f = lds.get(e);
+    if (scale_out) f = LZ::mul(f, out_scale<F, LZ>(a, sc, g));
+    if (ablate & 4) continue;
+    a.data[g] = (ablate & 8) ? f.pack() : f.canonical_wide().pack();
+  }
+}
+
+// One radix-2 butterfly stage (local stage q) over the tile. NORM: run the parallel carry step on the decimation-in-time outputs. x is
+// a fresh product (limbs < 2^B) and u +- x of a normalised u is a two-term sum, still an admissible `a` operand of the next
+// stage's product, so the carry step is only needed every second stage (and not after the last one: the tile leaves
+// through mul / canonical_wide, which take two-term limbs).
+template <bool DIF, bool NORM, class F, class LZ>
+__device__ __forceinline__ void radix2_stage(const LazyLds<LZ>& lds, const TileMap& map, const F* __restrict__ tw, int L, int q, bool unit_rounds) {
+  const int cc_log = map.cc_log;
+  const int CC = 1 << cc_log;
+  const int half_E = lds.E >> 1;
+  const int half = 1 << q;
+  for (int bidx = threadIdx.x; bidx < half_E; bidx += blockDim.x) {
+    const int cc = bidx & (CC - 1);
+    const int tb = bidx >> cc_log;
+    const int t_lo = tb & (half - 1);
+    const int t0 = ((tb >> q) << (q + 1)) | t_lo;
+    const int e0 = (t0 << cc_log) | cc;
+    const int e1 = e0 + (half << cc_log);
+    const LZ w = staged_twiddle<F, LZ>(tw, map, L, q, t_lo, cc);
+    const LZ u = lds.get(e0);
+    const LZ v = lds.get(e1);
+    if (unit_rounds && map.s0 + q == 0) {  // w = 1 for every butterfly of global stage 0 (wave-uniform branch)
       if (DIF) {
-        lds.put(e0, LZ::add(u, v).fold_top());   // sums feed sums here: keep the value within (-p, 2p) every stage
-#if defined(CSH_EXPERIMENTS) && defined(CSH_NTT_ABLATE_MUL)
-        lds.put(e1, LZ::add(LZ::sub(u, v), w));
-#else
-        lds.put(e1, LZ::mul(LZ::sub(u, v), w));  // the two-term difference is an admissible product operand as is
-#endif
+        lds.put(e0, LZ::add(u, v).fold_top());
+        lds.put(e1, LZ::sub(u, v));            // the pass's last stage: leaves through mul / canonical_wide, which take two-term limbs
       } else {
-#if defined(CSH_EXPERIMENTS) && defined(CSH_NTT_ABLATE_MUL)  // ablation builds only: no multiplication (wrong results): the memory / LDS / barrier floor of the pass
-        const LZ x = LZ::add(v, w);
-#else
-        const LZ x = LZ::mul(v, w);
-#endif
-        if (NORM) {
-          lds.put(e0, LZ::add(u, x).normalized());
-          lds.put(e1, LZ::sub(u, x).normalized());
-        } else {
-          lds.put(e0, LZ::add(u, x));
-          lds.put(e1, LZ::sub(u, x));
-        }
+        lds.put(e0, LZ::add(u, v));            // the pass's first stage: u, v are unpack() outputs, the sums two-term operands as after a product
+        lds.put(e1, LZ::sub(u, v));
+      }
+      continue;
+    }
+    if (DIF) {
+      lds.put(e0, LZ::add(u, v).fold_top());   // sums feed sums here: keep the value within (-p, 2p) every stage
+      lds.put(e1, LZ::mul(LZ::sub(u, v), w));  // the two-term difference is an admissible product operand as is
+    } else {
+      const LZ x = LZ::mul(v, w);
+      if (NORM) {
+        lds.put(e0, LZ::add(u, x).normalized());
+        lds.put(e1, LZ::sub(u, x).normalized());
+      } else {
+        lds.put(e0, LZ::add(u, x));
+        lds.put(e1, LZ::sub(u, x));
       }
     }
-    __syncthreads();
-  };
-  for (int qq = 0; qq < k; ++qq) {
-    const int q = DIF ? (k - 1 - qq) : qq;
-    if (DIF || (qq & 1))
-      stage(q, std::true_type{});
-    else
-      stage(q, std::false_type{});
   }
+  __syncthreads();
+}
 
-  const LZ sc = LZ::unpack(scale_lazy);
-  for (int e = tid; e < E; e += NT) {
-    const int cc = e & (CC - 1);
-    const size_t t = e >> cc_log;
-    const size_t g = ((((hi_idx << k) | t) << mid_bits) | mid) * CC + cc;
-    LZ f = lds.get(e);
-    // the 1/n of the inverse transform, or -- witness maps -- a per-entry table that already carries it (1/n times the coset
-    // power of the entry, in the pass's output order): the coset shift costs no sweep and no multiplication of its own
-    if (do_scale) f = LZ::mul(f, scale_tbl ? LZ::unpack(scale_tbl[g >> ncomp_log]) : sc);
-    data[g] = f.canonical_wide().pack();
+template <class F, class LZ, bool DIF>
+__global__ __launch_bounds__(NTT_MAX_THREADS) __attribute__((amdgpu_waves_per_eu(8))) void k_ntt_pass_lazy(F* data, const F* tw, const F* scale_tbl, int L, int s0, int k, int cb, int ncomp_log, int swz_mask,
+                                                                                           bool scale_out, bool unit_rounds, F scale) {
+  // PassArgs field by field (launch_pass unpacks it), put together again here: this kernel sits at its 64-VGPR cap and its decimation-in-
+  // frequency form spills 4 VGPRs; with the arguments as one by-value struct the allocator puts a spill reload 11 instructions behind the
+  // twiddle loads of the butterfly block, whose wait (in-order vmcnt) then exposes the twiddle latency: 2^16 inverse +7 %
+  PassArgs<F> a{};
+  a.data = data;
+  a.tw = tw;
+  a.scale_tbl = scale_tbl;
+  a.L = L;
+  a.s0 = s0;
+  a.k = k;
+  a.cb = cb;
+  a.ncomp_log = ncomp_log;
+  a.swz_mask = swz_mask;
+  a.scale_out = scale_out;
+  a.unit_rounds = unit_rounds;
+  a.scale = scale;
+  extern __shared__ uint4 lds_raw[];
+  const TileMap map(blockIdx.x, a.s0, a.k, a.cb, a.ncomp_log);
+  const LazyLds<LZ> lds{reinterpret_cast<int32_t*>(lds_raw), map.entries(), a.swz_mask};
+  load_tile<F, LZ>(lds, map, a.data);
+  for (int qq = 0; qq < a.k; ++qq) {
+    const int q = DIF ? (a.k - 1 - qq) : qq;
+    if (DIF || (qq & 1))
+      radix2_stage<DIF, true, F, LZ>(lds, map, a.tw, a.L, q, a.unit_rounds);
+    else
+      radix2_stage<DIF, false, F, LZ>(lds, map, a.tw, a.L, q, a.unit_rounds);
   }
+  store_tile<F, LZ>(lds, map, a, a.scale_out);
 }
 
 // ---- radix-4 form of the lazy pass ---------------------------------------------------------------------------------
@@ -319,61 +377,30 @@ __global__ __launch_bounds__(NTT_MAX_THREADS) __attribute__((amdgpu_waves_per_eu
 // operand classes: a round starts from normalised values, the second stage multiplies two-term sums, the outputs are normalised
 // once; in decimation in frequency every sum is folded), so the limb-bound contracts checked by the host self-test carry over.
 // An odd stage count leaves one radix-2 stage (last in DIT, last = local stage 0 in DIF).
-// PAIR (round 6; DIF must be true, s0 = 0): the LAST pass of an inverse transform (decimation in frequency, table `twl`) and the FIRST
-// pass of the forward transform that follows it in a witness map (decimation in time, table `twl_fwd`) work on the same contiguous
+// PAIR (round 6; DIF must be true, s0 = cb = 0): the LAST pass of an inverse transform (decimation in frequency, table `tw`) and the FIRST
+// pass of the forward transform that follows it in a witness map (decimation in time, table `tw_fwd`) work on the same contiguous
 // tiles -- ifft_in_to_out, coset table, fft_out_to_in of reduction.rs:141-174 -- so one launch keeps the tile in LDS across both:
 // DIF rounds, the scale (1/n, or the per-entry table carrying 1/n times the coset power) and the canonical form a store + load would
 // have left, DIT rounds, one store. One HBM sweep, one launch and one LDS fill less per pair; the field elements are the same.
 template <class F, class LZ, bool DIF, bool PAIR = false>
-__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_ntt_pass_r4(F* __restrict__ data, const F* __restrict__ twl, int L, int s0, int k,
-                                                                                             int cb, int ncomp_log, F scale_lazy, int do_scale, const F* __restrict__ scale_tbl,
-                                                                                             const F* __restrict__ twl_fwd = nullptr) {
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_ntt_pass_r4(const PassArgs<F> a) {
   static_assert(!PAIR || DIF, "the pair kernel starts with the decimation-in-frequency half");
   extern __shared__ uint4 lds_raw[];
-  const int cc_log = cb + ncomp_log;
+  const TileMap map(blockIdx.x, PAIR ? 0 : a.s0, a.k, PAIR ? 0 : a.cb, a.ncomp_log);
+  const int s0 = map.s0;
+  const int k = a.k;
+  const int cc_log = map.cc_log;
   const int CC = 1 << cc_log;
-  const int E = 1 << (k + cc_log);
-  const LazyLds<LZ> lds{reinterpret_cast<int32_t*>(lds_raw), E, (do_scale & 0x1000) ? 0 : 31};
-  const int mid_bits = s0 - cb;
-  const size_t tile = blockIdx.x;
-  const size_t mid = tile & ((size_t(1) << mid_bits) - 1);
-  const size_t hi_idx = tile >> mid_bits;
+  const int E = map.entries();
+  const LazyLds<LZ> lds{reinterpret_cast<int32_t*>(lds_raw), E, a.swz_mask};
   const int tid = threadIdx.x;
   const int NT = blockDim.x;
-  // timing experiments only (tune "ntt_variant" bits 16-19, wrong results): 1 = no butterfly rounds, 2 = no global loads, 4 = no stores,
-  // 8 = no canonicalisation before the store
-  const int ablate = kExperiments ? (do_scale >> 8) & 0xf : 0;  // product builds: constant 0, the branches below fold away
-  const bool unit_skip = !(do_scale & 0x2000);  // tune "ntt_variant" bit 20 switches the unit-twiddle rounds off (A/B runs)
-  do_scale &= 1;
+  int ablate = 0;  // product builds: constant 0, the branches it guards fold away
+  if constexpr (kExperiments) ablate = a.ablate;
 
-  // Tile load, four entries per lane with all four global loads issued before the first is consumed: written as one rolled loop
-  // (load, unpack, put per iteration) every lane paid four SERIAL trips to HBM per tile -- the 0.04-0.05 ms per sweep that no butterfly
-  // stage accounts for (profiles/archive/r04_e_ntt_per_pass.log; shortening the store tail by a third changed nothing, r04_l_ntt.log).
-  for (int base = 0; base < E; base += 4 * NT) {
-    F raw[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int e = base + tid + i * NT;
-      if (e < E) {
-        const int cc = e & (CC - 1);
-        const size_t t = e >> cc_log;
-        if (ablate & 2) raw[i] = scale_lazy; else
-        raw[i] = data[((((hi_idx << k) | t) << mid_bits) | mid) * CC + cc];
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int e = base + tid + i * NT;
-      if (e < E) lds.put(e, LZ::unpack(raw[i]));
-    }
-  }
-  __syncthreads();
+  load_tile<F, LZ>(lds, map, a.data, (ablate & 2) ? &a.scale : nullptr);
 
-  // twiddle of global stage s0 + q for the pair whose lower index has local stage bits t_lo (< 2^q)
-  auto twiddle = [&](const F* __restrict__ tw, int q, int t_lo, int cc) {
-    const size_t imod = ((size_t)t_lo << s0) | (mid << cb) | (size_t)(cc >> ncomp_log);
-    return load_sliced_twiddle<F, LZ>(tw, ((size_t(1) << (s0 + q)) - 1) + imod, (size_t(1) << L) - 1);  // staged table
-  };
+  auto twiddle = [&](const F* __restrict__ tw, int q, int t_lo, int cc) { return staged_twiddle<F, LZ>(tw, map, a.L, q, t_lo, cc); };
   // stages (q, q + 1) on the four entries t0 + {0, 1, 2, 3} * 2^q of every unit
   auto round4 = [&](auto dif_c, const F* __restrict__ tw, int q) {
     constexpr bool D = decltype(dif_c)::value;
@@ -479,39 +506,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     }
     __syncthreads();
   };
-  // one radix-2 stage (odd stage counts): the radix-2 pass's butterfly; in DIT it is the pass's last stage (outputs leave
-  // through mul / canonical_wide, which take two-term limbs), in DIF its inputs come normalised out of the last round
-  auto stage2 = [&](auto dif_c, const F* __restrict__ tw, int q) {
-    constexpr bool D = decltype(dif_c)::value;
-    const int half_E = E >> 1;
-    const int half = 1 << q;
-    for (int bidx = tid; bidx < half_E; bidx += NT) {
-      const int cc = bidx & (CC - 1);
-      const int tb = bidx >> cc_log;
-      const int t_lo = tb & (half - 1);
-      const int t0 = ((tb >> q) << (q + 1)) | t_lo;
-      const int e0 = (t0 << cc_log) | cc;
-      const int e1 = e0 + (half << cc_log);
-      const LZ u = lds.get(e0);
-      const LZ v = lds.get(e1);
-      if (unit_skip && s0 + q == 0) {  // global stage 0: twiddle 1 everywhere (wave-uniform branch)
-        lds.put(e0, D ? LZ::add(u, v).fold_top() : LZ::add(u, v));
-        lds.put(e1, LZ::sub(u, v));
-        continue;
-      }
-      const LZ w = twiddle(tw, q, t_lo, cc);
-      if constexpr (D) {
-        lds.put(e0, LZ::add(u, v).fold_top());
-        lds.put(e1, LZ::mul(LZ::sub(u, v), w));
-      } else {
-        const LZ x = LZ::mul(v, w);
-        lds.put(e0, LZ::add(u, x));
-        lds.put(e1, LZ::sub(u, x));
-      }
-    }
-    __syncthreads();
-  };
-  const bool unit_round = unit_skip && s0 == 0 && k >= 2;
+  // one radix-2 stage (odd stage counts): the radix-2 pass's butterfly without the carry step; in DIT it is the pass's last stage (outputs
+  // leave through mul / canonical_wide, which take two-term limbs), in DIF its inputs come normalised out of the last round
+  auto stage2 = [&](auto dif_c, const F* __restrict__ tw, int q) { radix2_stage<decltype(dif_c)::value, false, F, LZ>(lds, map, tw, a.L, q, a.unit_rounds); };
+  const bool unit_round = a.unit_rounds && s0 == 0 && k >= 2;
   auto rounds = [&](auto dif_c, const F* __restrict__ tw) {
     constexpr bool D = decltype(dif_c)::value;
     if constexpr (D) {
@@ -530,36 +528,21 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
       if (q < k) stage2(dif_c, tw, q);
     }
   };
-  const LZ sc = LZ::unpack(scale_lazy);
   if constexpr (PAIR) {
-    rounds(std::true_type{}, twl);
+    rounds(std::true_type{}, a.tw);
     // between the two transforms: what the inverse transform's last pass would have stored (scaled, canonical) and the forward
     // transform's first pass would have loaded and unpacked -- each lane on the entries it will store, no traffic
+    const LZ sc = LZ::unpack(a.scale);
     for (int e = tid; e < E; e += NT) {
-      const size_t g = (size_t)tile * (size_t)E + (size_t)e;  // s0 = 0, cb = 0: the tile is contiguous
-      const LZ f = LZ::mul(lds.get(e), scale_tbl ? LZ::unpack(scale_tbl[g >> ncomp_log]) : sc);
+      const LZ f = LZ::mul(lds.get(e), out_scale<F, LZ>(a, sc, map.global_index(e)));
       lds.put(e, LZ::unpack(f.canonical_wide().pack()));
     }
     __syncthreads();
-    rounds(std::false_type{}, twl_fwd);
-    for (int e = tid; e < E; e += NT) data[(size_t)tile * (size_t)E + (size_t)e] = lds.get(e).canonical_wide().pack();
-    return;
-  }
-  if (ablate & 1) {
+    rounds(std::false_type{}, a.tw_fwd);
+    store_tile<F, LZ>(lds, map, a, false);
   } else {
-    rounds(std::integral_constant<bool, DIF>{}, twl);
-  }
-
-  for (int e = tid; e < E; e += NT) {
-    const int cc = e & (CC - 1);
-    const size_t t = e >> cc_log;
-    const size_t g = ((((hi_idx << k) | t) << mid_bits) | mid) * CC + cc;
-    LZ f = lds.get(e);
-    // the 1/n of the inverse transform, or -- witness maps -- a per-entry table that already carries it (1/n times the coset
-    // power of the entry, in the pass's output order): the coset shift costs no sweep and no multiplication of its own
-    if (do_scale) f = LZ::mul(f, scale_tbl ? LZ::unpack(scale_tbl[g >> ncomp_log]) : sc);
-    if (ablate & 4) continue;
-    data[g] = (ablate & 8) ? f.pack() : f.canonical_wide().pack();
+    if (!(ablate & 1)) rounds(std::integral_constant<bool, DIF>{}, a.tw);
+    store_tile<F, LZ>(lds, map, a, a.scale_out, ablate);
   }
 }
 
@@ -646,6 +629,18 @@ static F f_from_words(const void* p) {
   return f;
 }
 
+// the field type of a curve's scalar field, handed to a generic callable as a tag: with_fr(curve, [&](auto fr) -> int { using F = typename decltype(fr)::type; ... })
+template <class F>
+struct FrTag {
+  using type = F;
+};
+template <class Fn>
+static int with_fr(csh_curve_t curve, Fn&& f) {
+  if (curve == CSH_BN254) return f(FrTag<Bn254Fr>{});
+  if (curve == CSH_BLS12_377) return f(FrTag<Bls377Fr>{});
+  return f(FrTag<Bls381Fr>{});
+}
+
 struct Pass {
   int s0, k, cb;
 };
@@ -657,9 +652,8 @@ struct Pass {
 // 0.052 -> 0.028 (2^9), 2^18 0.058 -> 0.039 (2^10); 2^19 .. 2^21 are best at 2^11 (more passes cost more than the parallelism gains);
 // from 2^22 elements on 2^10-element tiles (four independent tiles per CU instead of two: their load / compute / store phases
 // interleave) gain 1-4 % (r04_d_ntt_tile_ab.log, r04_k_ntt_tiles.log). tune "ntt_variant" bits 8-10 = v forces 2^(12-v) (A/B runs).
-static int ntt_tile_log(int L, int ncomp_log) {
-  const int v = (tune().ntt_variant.load(std::memory_order_relaxed) >> 8) & 7;
-  if (v >= 1 && v <= 4) return 12 - v;
+static int ntt_tile_log(int L, int ncomp_log, int forced_tile) {
+  if (forced_tile >= 1 && forced_tile <= 4) return 12 - forced_tile;
   const int total = L + ncomp_log;
   if (total <= 15) return 8;
   if (total <= 17) return 9;
@@ -668,16 +662,15 @@ static int ntt_tile_log(int L, int ncomp_log) {
   return NTT_TILE_LOG;
 }
 
-static int plan_passes(int L, int ncomp_log, Pass* out) {
-  const int TE = ntt_tile_log(L, ncomp_log) - ncomp_log;  // log2(entries per tile)
+static int plan_passes(int L, int ncomp_log, int forced_tile, int forced_run, Pass* out) {
+  const int TE = ntt_tile_log(L, ncomp_log, forced_tile) - ncomp_log;  // log2(entries per tile)
   // Contiguous run of a strided pass: 2^cb entries of ncomp x 32 bytes. 64-byte runs cost nothing against 256-byte ones and save a whole
   // sweep where the stages then fit two passes: 2^20 points 11 + 9 stages (128-byte runs) instead of 11 + 5 + 4, inverse / forward 0.143 / 0.135 ->
   // 0.132 / 0.123 ms, share pairs 0.258 / 0.259 -> 0.246 / 0.242 ms; 2^21 points 11 + 10 (64-byte runs) 0.268 / 0.285 -> 0.261 / 0.270
   // (profiles/archive/r03_q_ntt_runs.log, r03_r_ntt_tiles.log, r03_s_ntt_runs64.log).
   // 32-byte runs do not pay (2^22 as 11 + 11: 0.53 -> 0.60 ms), nor do 2^12-entry tiles at one tile per CU (2^22 as 12 + 10: 0.53 -> 0.55,
   // 2^24 2.2 -> 2.4 ms). tune "ntt_variant" bits 4-6 = log2(run entries) + 1 overrides the run length for A/B runs (0: this default).
-  const int nv_run = (tune().ntt_variant.load(std::memory_order_relaxed) >> 4) & 7;
-  const int cb_min = nv_run ? (nv_run - 1 > ncomp_log ? nv_run - 1 - ncomp_log : 0) : (1 - ncomp_log);
+  const int cb_min = forced_run ? (forced_run - 1 > ncomp_log ? forced_run - 1 - ncomp_log : 0) : (1 - ncomp_log);
   int np = 0;
   int k0 = L < TE ? L : TE;
   out[np++] = {0, k0, 0};
@@ -699,6 +692,102 @@ static int plan_passes(int L, int ncomp_log, Pass* out) {
   return np;
 }
 
+// Everything a public entry decides about a transform, decided ONCE: each tune knob is read one time here and every launch of the call
+// uses this plan. (The knobs are process-wide atomics that tests and A/B tools flip at run time; a fused pair whose strided passes
+// re-read them could run under another plan than its tile pass and skip the wrong stages.)
+struct NttPlan {
+  int L, ncomp_log;
+  bool lazy;         // tune "ntt_lazy": the lazy-field kernels (default) or the 32-bit pass
+  int max_threads;   // tune "ntt_threads": lanes per workgroup of the radix-2 kernels; 16 waves per 2^11-element tile measured best for both field representations
+  bool pair;         // tune "ntt_pair" and "ntt_pair_min_log" allow the fused tile pass at this size
+  int variant;       // tune "ntt_variant" as read, decoded below
+  bool force_r4, force_r2;  // bit 0 / bit 1
+  int forced_run;    // bits 4-6
+  int forced_tile;   // bits 8-10
+  int swz_mask;      // bit 11 switches the LDS bank swizzle off
+  bool unit_rounds;  // bit 20 switches the unit-twiddle rounds off
+  int only_pass;     // timing experiments (-DCSH_EXPERIMENTS only), WRONG RESULTS: bits 12-13 = run ONE pass of the plan,
+  int ablate;        // bits 16-19 = PassArgs::ablate
+  Pass passes[8];
+  int np;
+
+  NttPlan(int L_, uint32_t ncomp) : L(L_), ncomp_log(ncomp == 2 ? 1 : 0) {
+    const Tune& t = tune();
+    lazy = t.ntt_lazy.load(std::memory_order_relaxed) != 0;
+    const int th = t.ntt_threads.load(std::memory_order_relaxed);
+    max_threads = (th == 256 || th == 512 || th == 1024) ? th : 1024;
+    pair = t.ntt_pair.load(std::memory_order_relaxed) != 0 && L >= t.ntt_pair_min_log.load(std::memory_order_relaxed);
+    variant = t.ntt_variant.load(std::memory_order_relaxed);
+    force_r4 = (variant & 1) != 0;
+    force_r2 = (variant & 2) != 0;
+    forced_run = (variant >> 4) & 7;
+    forced_tile = (variant >> 8) & 7;
+    swz_mask = (variant & 0x800) ? 0 : 31;
+    unit_rounds = (variant & 0x100000) == 0;
+    only_pass = kExperiments ? (variant >> 12) & 3 : 0;
+    ablate = kExperiments ? (variant >> 16) & 0xf : 0;
+    np = plan_passes(L, ncomp_log, forced_tile, forced_run, passes);
+  }
+  int tile_elems_log(const Pass& p) const { return p.k + p.cb + ncomp_log; }
+  // Radix-4 pass (two stages per LDS round trip, 512 lanes per tile) or radix-2 pass. With the staged twiddle tables and two
+  // folds per decimation-in-frequency round the radix-4 pass wins from 2^20 points on (one box, inverse / forward ms: 2^22
+  // 0.583 / 0.541 -> 0.553 / 0.526, 2^24 2.36 / 2.04 -> 2.31 / 2.06, 2^20 0.153 / 0.142 -> 0.150 / 0.141; another box 2^22 forward
+  // 0.549 -> 0.510) and ties or loses below (profiles/archive/r03_k_ntt_staged.log, r03_l_ntt_mix.log). Default: transforms of >= 2^20
+  // points take it; tune "ntt_variant" 1 forces it everywhere, 2 forces the radix-2 pass.
+  bool radix4(const Pass& p) const { return lazy && (force_r4 || (L >= 20 && !force_r2)) && p.k >= 2 && tile_elems_log(p) >= 2; }
+  // the fused tile pass of a witness map's transform pair (k_ntt_pass_r4<.., PAIR>): the radix-4 kernel on contiguous tiles, default kernels otherwise
+  bool fusable() const {
+    const Pass& p = passes[0];
+    return lazy && pair && p.s0 == 0 && p.cb == 0 && p.k >= 2 && tile_elems_log(p) >= 2 && (variant & ~0x100800) == 0;
+  }
+};
+
+enum class PassForm { Plain32, LazyR2, LazyR4, LazyPair };
+
+// The one launch site of the pass kernels: picks the instantiation, sizes the workgroup (radix-2 forms: one lane per butterfly of a stage,
+// clamped to [64, max_threads]; radix-4 forms: one lane per 4-entry unit, clamped to [64, 512]), raises the kernel's LDS limit when the tile
+// needs more than the default 48 KiB, launches.
+template <class F>
+static int launch_pass(PassForm form, bool dif, const PassArgs<F>& a, int max_threads, hipStream_t st) {
+  using LZ = typename LazyOf<F>::type;
+  const void* kernel = nullptr;
+  switch (form) {
+    case PassForm::Plain32: kernel = dif ? (const void*)k_ntt_pass<F, true> : (const void*)k_ntt_pass<F, false>; break;
+    case PassForm::LazyR2: kernel = dif ? (const void*)k_ntt_pass_lazy<F, LZ, true> : (const void*)k_ntt_pass_lazy<F, LZ, false>; break;
+    case PassForm::LazyR4: kernel = dif ? (const void*)k_ntt_pass_r4<F, LZ, true> : (const void*)k_ntt_pass_r4<F, LZ, false>; break;
+    case PassForm::LazyPair: kernel = (const void*)k_ntt_pass_r4<F, LZ, true, true>; break;
+  }
+  const bool r4 = form == PassForm::LazyR4 || form == PassForm::LazyPair;
+  const size_t elem_bytes = form == PassForm::Plain32 ? 32 : 4 * LZ::NL;
+  const int elems_log = a.k + a.cb + a.ncomp_log;
+  const size_t lanes = (size_t(1) << elems_log) >> (r4 ? 2 : 1);
+  const size_t lane_max = r4 ? 512 : (size_t)max_threads;
+  const int threads = lanes >= lane_max ? (int)lane_max : (lanes >= 64 ? (int)lanes : 64);
+  const size_t lds_bytes = elem_bytes << elems_log;
+  if (lds_bytes > 48 * 1024) CSH_TRY(raise_lds_limit(kernel, elem_bytes << NTT_TILE_LOG));
+  const size_t tiles = (size_t(1) << a.L) >> (a.k + a.cb);
+  PassArgs<F> args = a;
+  void* by_struct[] = {&args};
+  void* by_field[] = {&args.data, &args.tw, &args.scale_tbl, &args.L, &args.s0, &args.k, &args.cb, &args.ncomp_log, &args.swz_mask, &args.scale_out, &args.unit_rounds, &args.scale};  // k_ntt_pass_lazy
+  (void)hipLaunchKernel(kernel, dim3((unsigned)tiles), dim3(threads), form == PassForm::LazyR2 ? by_field : by_struct, lds_bytes, st);
+  CSH_HIP(hipGetLastError());
+  return CSH_OK;
+}
+
+// tw_fwd / tw_inv = w^j / w^-j, j < max(n/2, 1): allocated and queued on st (a stream of the domain's device); the caller synchronises
+// and, on any error, releases them (Domain::release_natural_tables)
+template <class F>
+static hipError_t build_natural_tables(Domain* d, hipStream_t st) {
+  const size_t half = d->n / 2 ? d->n / 2 : 1;
+  hipError_t e = hipMalloc(&d->tw_fwd, half * sizeof(F));
+  if (e == hipSuccess) e = hipMalloc(&d->tw_inv, half * sizeof(F));
+  if (e != hipSuccess) return e;
+  const dim3 grid(grid_for((half + POW_CHUNK - 1) / POW_CHUNK, 256));
+  hipLaunchKernelGGL((k_powers<F, false>), grid, dim3(256), 0, st, (F*)d->tw_fwd, f_from_words<F>(d->gen), half, 0);
+  hipLaunchKernelGGL((k_powers<F, false>), grid, dim3(256), 0, st, (F*)d->tw_inv, f_from_words<F>(d->gen_inv), half, 0);
+  return hipGetLastError();
+}
+
 // the natural-order twiddle tables of the 32-bit pass, (re)built when that pass is asked for on a domain that has released them
 template <class F>
 static int plain_tables(const Domain* cd) {
@@ -709,7 +798,6 @@ static int plain_tables(const Domain* cd) {
   std::lock_guard<std::mutex> g(mu);
   Domain* d = const_cast<Domain*>(cd);
   if (d->tw_fwd && d->tw_inv) return CSH_OK;
-  const size_t half = d->n / 2 ? d->n / 2 : 1;
   int prev_dev = -1;
   (void)hipGetDevice(&prev_dev);
   const bool switch_dev = prev_dev != d->device;
@@ -717,125 +805,60 @@ static int plain_tables(const Domain* cd) {
     set_error("hipSetDevice(%d) for the domain's twiddle tables failed", d->device);
     return CSH_ERR_HIP;
   }
-  void *f = nullptr, *i = nullptr;
   hipStream_t st = nullptr;
-  hipError_t e = hipMalloc(&f, half * sizeof(F));
-  if (e == hipSuccess) e = hipMalloc(&i, half * sizeof(F));
-  if (e == hipSuccess) e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);  // a stream of the domain's device, not the caller's lane
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL((k_powers<F, false>), dim3(grid_for((half + POW_CHUNK - 1) / POW_CHUNK, 256)), dim3(256), 0, st, (F*)f, f_from_words<F>(d->gen), half, 0);
-    hipLaunchKernelGGL((k_powers<F, false>), dim3(grid_for((half + POW_CHUNK - 1) / POW_CHUNK, 256)), dim3(256), 0, st, (F*)i, f_from_words<F>(d->gen_inv), half, 0);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-  }
+  hipError_t e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);  // a stream of the domain's device, not the caller's lane
+  if (e == hipSuccess) e = build_natural_tables<F>(d, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
   if (st) (void)hipStreamDestroy(st);
-  if (e != hipSuccess) {
-    if (f) (void)hipFree(f);
-    if (i) (void)hipFree(i);
-  }
+  if (e != hipSuccess) d->release_natural_tables();
   if (switch_dev && prev_dev >= 0) (void)hipSetDevice(prev_dev);
   if (e != hipSuccess) {
     set_error("building the natural-order twiddle tables failed: %s", hipGetErrorString(e));
     return e == hipErrorOutOfMemory ? CSH_ERR_OOM : CSH_ERR_HIP;
   }
-  d->tw_fwd = f;
-  d->tw_inv = i;
-  return CSH_OK;
-}
-// the tables of the 32-bit pass, read under plain_tables' rules: (fwd, inv) once they exist
-template <class F>
-static int plain_tables_get(const Domain* d, const void** fwd, const void** inv) {
-  CSH_TRY(plain_tables<F>(d));  // takes the mutex: returns at once when both exist; the pointers never change afterwards (freed with the domain)
-  *fwd = d->tw_fwd;
-  *inv = d->tw_inv;
   return CSH_OK;
 }
 
+// what pass `p` of `plan` is told: everything but the tables comes from the plan and the domain
 template <class F>
-static int run_ntt(const Domain* d, F* data, uint32_t ncomp, bool dif, hipStream_t st, const F* scale_tbl = nullptr, bool skip_pass0 = false) {
-  const int L = (int)d->log_n;
-  if (L == 0) return CSH_OK;  // size-1 transform is the identity (1/n = 1)
-  const int ncomp_log = ncomp == 2 ? 1 : 0;
-  Pass passes[8];
-  const int np = plan_passes(L, ncomp_log, passes);
-  const bool use_lazy = tune().ntt_lazy.load(std::memory_order_relaxed) != 0;
-  if (scale_tbl && (!use_lazy || !dif)) {
+static PassArgs<F> pass_args(const NttPlan& plan, const Domain* d, F* data, const Pass& p, const void* tw, bool scale_out, const F* scale_tbl) {
+  PassArgs<F> a{};
+  a.data = data;
+  a.tw = reinterpret_cast<const F*>(tw);
+  a.L = plan.L;
+  a.s0 = p.s0;
+  a.k = p.k;
+  a.cb = p.cb;
+  a.ncomp_log = plan.ncomp_log;
+  a.scale = f_from_words<F>(plan.lazy ? d->n_inv_lazy : d->n_inv);
+  a.scale_tbl = scale_out ? scale_tbl : nullptr;
+  a.scale_out = scale_out;
+  a.swz_mask = plan.swz_mask;
+  a.unit_rounds = plan.unit_rounds;
+  if constexpr (kExperiments) a.ablate = plan.ablate;
+  return a;
+}
+
+// The passes of one transform under `plan`, from pass `first` of the plan on (0: all of them; 1: the strided passes only, the pass over
+// the contiguous tiles running fused with its neighbour of the other direction, run_ntt_pair). Decimation in frequency walks the plan backwards.
+template <class F>
+static int run_passes(const NttPlan& plan, const Domain* d, F* data, bool dif, hipStream_t st, const F* scale_tbl = nullptr, int first = 0) {
+  if (plan.L == 0) return CSH_OK;  // size-1 transform is the identity (1/n = 1)
+  if (scale_tbl && (!plan.lazy || !dif)) {
     set_error("a scale table needs the lazy decimation-in-frequency passes");
     return CSH_ERR_INVALID;
   }
-  using LZ = typename LazyOf<F>::type;
-  const void *pt_fwd = nullptr, *pt_inv = nullptr;
-  if (!use_lazy) CSH_TRY(plain_tables_get<F>(d, &pt_fwd, &pt_inv));
-  const F* tw = reinterpret_cast<const F*>(use_lazy ? (dif ? d->tw_inv_lazy : d->tw_fwd_lazy) : (dif ? pt_inv : pt_fwd));
-  F scale = f_from_words<F>(use_lazy ? d->n_inv_lazy : d->n_inv);
-  const int NTT_THREADS_MAX = [] {
-    const int v = tune().ntt_threads.load(std::memory_order_relaxed);  // 16 waves per 2^11-element tile: measured best for both field representations
-    return (v == 256 || v == 512 || v == 1024) ? v : 1024;
-  }();
-  const int only_pass = kExperiments ? (tune().ntt_variant.load(std::memory_order_relaxed) >> 12) & 3 : 0;  // timing experiments (-DCSH_EXPERIMENTS only): run ONE pass of the plan (wrong results)
-  for (int pi = 0; pi < np; ++pi) {
-    const Pass& p = dif ? passes[np - 1 - pi] : passes[pi];
-    if (only_pass && (dif ? np - 1 - pi : pi) != only_pass - 1) continue;
-    if (skip_pass0 && p.s0 == 0) continue;  // run_ntt_pair: the pass over the contiguous tiles runs fused with its neighbour of the other direction
-    const int tile_log = p.k + p.cb;  // entries
-    const size_t tiles = d->n >> tile_log;
-    // radix-2 passes: one lane per butterfly of a stage, at least one wave
-    const size_t bfly = (size_t(1) << (tile_log + ncomp_log)) >> 1;
-    const int NTT_THREADS = bfly >= (size_t)NTT_THREADS_MAX ? NTT_THREADS_MAX : (bfly >= 64 ? (int)bfly : 64);
-    const size_t lds_bytes = use_lazy ? (size_t(4 * LZ::NL) << (tile_log + ncomp_log)) : (size_t(32) << (tile_log + ncomp_log));
-    const int do_scale = dif && (p.s0 == 0);
-    const int noswz = ((tune().ntt_variant.load(std::memory_order_relaxed) & 0x800) ? 0x1000 : 0) |        // LDS bank swizzle off (A/B runs)
-                      ((tune().ntt_variant.load(std::memory_order_relaxed) & 0x100000) ? 0x2000 : 0);   // unit-twiddle rounds off (A/B runs)
-    if (use_lazy) {
-      if (lds_bytes > 48 * 1024)
-        CSH_TRY(raise_lds_limit(dif ? (const void*)k_ntt_pass_lazy<F, LZ, true> : (const void*)k_ntt_pass_lazy<F, LZ, false>, (size_t)(4 * LZ::NL) << NTT_TILE_LOG));
-      // Radix-4 pass (two stages per LDS round trip, 512 lanes per tile) or radix-2 pass. With the staged twiddle tables and two
-      // folds per decimation-in-frequency round the radix-4 pass wins from 2^20 points on (one box, inverse / forward ms: 2^22
-      // 0.583 / 0.541 -> 0.553 / 0.526, 2^24 2.36 / 2.04 -> 2.31 / 2.06, 2^20 0.153 / 0.142 -> 0.150 / 0.141; another box 2^22 forward
-      // 0.549 -> 0.510) and ties or loses below (profiles/archive/r03_k_ntt_staged.log, r03_l_ntt_mix.log). Default: transforms of >= 2^20
-      // points take it; tune "ntt_variant" 1 forces it everywhere, 2 forces the radix-2 pass.
-      const int nv = tune().ntt_variant.load(std::memory_order_relaxed);
-      const bool r4_default = L >= 20;
-      const bool r4 = ((nv & 1) != 0 || (r4_default && (nv & 2) == 0)) && p.k >= 2 && tile_log + ncomp_log >= 2;
-      if (r4) {
-        if (lds_bytes > 48 * 1024)
-          CSH_TRY(raise_lds_limit(dif ? (const void*)k_ntt_pass_r4<F, LZ, true> : (const void*)k_ntt_pass_r4<F, LZ, false>, (size_t)(4 * LZ::NL) << NTT_TILE_LOG));
-        const size_t units = (size_t(1) << (tile_log + ncomp_log)) >> 2;
-        const int nt = units >= 512 ? 512 : (units >= 64 ? (int)units : 64);
-        if (dif)
-          hipLaunchKernelGGL((k_ntt_pass_r4<F, LZ, true>), dim3((unsigned)tiles), dim3(nt), lds_bytes, st, data, tw, L, p.s0, p.k, p.cb, ncomp_log, scale, do_scale | (((nv >> 16) & 0xf) << 8) | noswz, scale_tbl);
-        else
-          hipLaunchKernelGGL((k_ntt_pass_r4<F, LZ, false>), dim3((unsigned)tiles), dim3(nt), lds_bytes, st, data, tw, L, p.s0, p.k, p.cb, ncomp_log, scale, (((nv >> 16) & 0xf) << 8) | noswz, (const F*)nullptr);
-        CSH_HIP(hipGetLastError());
-        continue;
-      }
-      if (dif)
-        hipLaunchKernelGGL((k_ntt_pass_lazy<F, LZ, true>), dim3((unsigned)tiles), dim3(NTT_THREADS), lds_bytes, st, data, tw, L, p.s0, p.k, p.cb,
-                           ncomp_log, scale, do_scale | noswz, scale_tbl);
-      else
-        hipLaunchKernelGGL((k_ntt_pass_lazy<F, LZ, false>), dim3((unsigned)tiles), dim3(NTT_THREADS), lds_bytes, st, data, tw, L, p.s0, p.k, p.cb,
-                           ncomp_log, scale, noswz, (const F*)nullptr);
-      CSH_HIP(hipGetLastError());
-      continue;
-    }
-    if (lds_bytes > 48 * 1024)
-      CSH_TRY(raise_lds_limit(dif ? (const void*)k_ntt_pass<F, true> : (const void*)k_ntt_pass<F, false>, (size_t)32 << NTT_TILE_LOG));
-    if (dif)
-      hipLaunchKernelGGL((k_ntt_pass<F, true>), dim3((unsigned)tiles), dim3(NTT_THREADS), lds_bytes, st, data, tw, L, p.s0, p.k, p.cb,
-                         ncomp_log, scale, do_scale);
-    else
-      hipLaunchKernelGGL((k_ntt_pass<F, false>), dim3((unsigned)tiles), dim3(NTT_THREADS), lds_bytes, st, data, tw, L, p.s0, p.k, p.cb,
-                         ncomp_log, scale, 0);
-    CSH_HIP(hipGetLastError());
+  // the tables of the 32-bit pass are read under plain_tables' rules: it takes the mutex and returns at once when both exist; the pointers
+  // never change afterwards (freed with the domain)
+  if (!plan.lazy) CSH_TRY(plain_tables<F>(d));
+  const void* tw = plan.lazy ? (dif ? d->tw_inv_lazy : d->tw_fwd_lazy) : (dif ? d->tw_inv : d->tw_fwd);
+  for (int i = first; i < plan.np; ++i) {
+    const int pi = dif ? plan.np - 1 - (i - first) : i;
+    if (plan.only_pass && pi != plan.only_pass - 1) continue;
+    const Pass& p = plan.passes[pi];
+    const PassForm form = !plan.lazy ? PassForm::Plain32 : (plan.radix4(p) ? PassForm::LazyR4 : PassForm::LazyR2);
+    CSH_TRY(launch_pass<F>(form, dif, pass_args<F>(plan, d, data, p, tw, dif && p.s0 == 0, scale_tbl), plan.max_threads, st));
   }
-  return CSH_OK;
-}
-
-template <class F>
-static int run_bit_reverse(F* data, uint32_t log_n, uint32_t ncomp, hipStream_t st) {
-  if (log_n == 0) return CSH_OK;
-  hipLaunchKernelGGL(k_bit_reverse<F>, dim3(grid_for(size_t(1) << log_n, 256)), dim3(256), 0, st, data, (int)log_n, (int)ncomp);
-  CSH_HIP(hipGetLastError());
   return CSH_OK;
 }
 
@@ -882,7 +905,7 @@ static int create_domain_t(csh_curve_t curve, uint32_t log_n, const uint64_t* ge
       return CSH_ERR_DOMAIN;
     }
   }
-  Domain* d = new Domain();
+  std::unique_ptr<Domain> d(new Domain());  // frees whatever exists on every error path
   d->curve = curve;
   if (hipGetDevice(&d->device) != hipSuccess) d->device = 0;
   d->log_n = log_n;
@@ -892,22 +915,13 @@ static int create_domain_t(csh_curve_t curve, uint32_t log_n, const uint64_t* ge
   memcpy(d->gen, &gen, 32);
   memcpy(d->gen_inv, &gen_inv, 32);
   memcpy(d->n_inv, &n_inv, 32);
-  const size_t half = d->n / 2 ? d->n / 2 : 1;
-  d->tw_fwd = d->tw_inv = nullptr;
-  hipError_t e1 = hipMalloc(&d->tw_fwd, half * sizeof(F));
-  hipError_t e2 = hipMalloc(&d->tw_inv, half * sizeof(F));
-  if (e1 != hipSuccess || e2 != hipSuccess) {
-    if (d->tw_fwd) (void)hipFree(d->tw_fwd);
-    if (d->tw_inv) (void)hipFree(d->tw_inv);
-    delete d;
-    set_error("hipMalloc of twiddle tables failed");
-    return CSH_ERR_OOM;
-  }
   hipStream_t st = resolve_stream(nullptr);
-  hipLaunchKernelGGL((k_powers<F, false>), dim3(grid_for((half + POW_CHUNK - 1) / POW_CHUNK, 256)), dim3(256), 0, st, (F*)d->tw_fwd, gen, half, 0);
-  hipLaunchKernelGGL((k_powers<F, false>), dim3(grid_for((half + POW_CHUNK - 1) / POW_CHUNK, 256)), dim3(256), 0, st, (F*)d->tw_inv, gen_inv, half, 0);
+  hipError_t e = build_natural_tables<F>(d.get(), st);
+  if (e != hipSuccess) {
+    set_error("building the natural-order twiddle tables failed: %s", hipGetErrorString(e));
+    return e == hipErrorOutOfMemory ? CSH_ERR_OOM : CSH_ERR_HIP;
+  }
   using LZ = typename LazyOf<F>::type;
-  d->tw_fwd_lazy = d->tw_inv_lazy = nullptr;
   const size_t staged = d->n > 1 ? d->n - 1 : 1;  // one contiguous run per stage: 2^L - 1 entries
   hipError_t e4 = hipMalloc(&d->tw_fwd_lazy, staged * (sizeof(F) + sizeof(int32_t)));  // pre-sliced: 8 + 1 limbs per entry
   hipError_t e5 = hipMalloc(&d->tw_inv_lazy, staged * (sizeof(F) + sizeof(int32_t)));
@@ -920,33 +934,15 @@ static int create_domain_t(csh_curve_t curve, uint32_t log_n, const uint64_t* ge
     memcpy(d->n_inv_lazy, &nl, 32);
   }
   hipError_t e3 = hipStreamSynchronize(st);
+  if (e3 != hipSuccess || e4 != hipSuccess || e5 != hipSuccess) {
+    set_error("twiddle generation failed: %s", hipGetErrorString(e3 != hipSuccess ? e3 : (e4 != hipSuccess ? e4 : e5)));
+    return e3 != hipSuccess ? CSH_ERR_HIP : CSH_ERR_OOM;
+  }
   // Footprint: the staged, pre-sliced tables are (2^L - 1) x 36 bytes per direction (2^24: 1.2 GB for both, 2^26: 4.8 GB);
   // the natural tables they were made from (2^(L-1) x 32 bytes per direction) are only read by the 32-bit pass (CSH_NTT_LAZY=0, A/B
   // runs), so they are released here and rebuilt on demand (plain_tables) -- a third less per cached domain.
-  if (e3 == hipSuccess && e4 == hipSuccess && e5 == hipSuccess && tune().ntt_lazy.load(std::memory_order_relaxed) != 0) {
-    (void)hipFree(d->tw_fwd);
-    (void)hipFree(d->tw_inv);
-    d->tw_fwd = d->tw_inv = nullptr;
-  }
-  if (e3 != hipSuccess || e4 != hipSuccess || e5 != hipSuccess) {
-    set_error("twiddle generation failed: %s", hipGetErrorString(e3 != hipSuccess ? e3 : (e4 != hipSuccess ? e4 : e5)));
-    (void)hipFree(d->tw_fwd);
-    (void)hipFree(d->tw_inv);
-    if (d->tw_fwd_lazy) (void)hipFree(d->tw_fwd_lazy);
-    if (d->tw_inv_lazy) (void)hipFree(d->tw_inv_lazy);
-    delete d;
-    return e3 != hipSuccess ? CSH_ERR_HIP : CSH_ERR_OOM;
-  }
-  *out = d;
-  return CSH_OK;
-}
-
-template <class F>
-static int coset_table_t(const Domain* d, const uint64_t* shift, uint64_t* out_dev, hipStream_t st) {
-  F sh = f_from_words<F>(shift);
-  hipLaunchKernelGGL((k_powers<F, true>), dim3(grid_for((d->n + POW_CHUNK - 1) / POW_CHUNK, 256)), dim3(256), 0, st, (F*)out_dev, sh, d->n,
-                     (int)d->log_n);
-  CSH_HIP(hipGetLastError());
+  if (tune().ntt_lazy.load(std::memory_order_relaxed) != 0) d->release_natural_tables();
+  *out = d.release();
   return CSH_OK;
 }
 
@@ -954,70 +950,47 @@ static int coset_table_t(const Domain* d, const uint64_t* shift, uint64_t* out_d
 // ifft_in_to_out (its last pass multiplying entry i by scale_table[i], or by 1/n when the table is NULL) followed by fft_out_to_in
 // on the same vector, the two passes over the contiguous tiles fused into ONE launch (k_ntt_pass_r4<.., PAIR>): reduction.rs:141-174 per
 // vector. Falls back to the two transforms when the radix-4 pass does not apply to the plan's first pass (or tune "ntt_pair" = 0).
+// One plan serves the fused pass and the strided passes on either side of it.
 template <class F>
 static int run_ntt_pair(const Domain* d, F* data, uint32_t ncomp, hipStream_t st, const F* scale_tbl) {
-  const int L = (int)d->log_n;
-  if (L == 0) return CSH_OK;
-  using LZ = typename LazyOf<F>::type;
-  const int ncomp_log = ncomp == 2 ? 1 : 0;
-  Pass passes[8];
-  const int np = plan_passes(L, ncomp_log, passes);
-  const Pass& p = passes[0];
-  const int tile_log = p.k + p.cb;
-  const bool use_lazy = tune().ntt_lazy.load(std::memory_order_relaxed) != 0;
-  const int nv = tune().ntt_variant.load(std::memory_order_relaxed);
-  const bool fusable = use_lazy && tune().ntt_pair.load(std::memory_order_relaxed) != 0 && p.s0 == 0 && p.cb == 0 && p.k >= 2 && tile_log + ncomp_log >= 2 &&
-                       (nv & ~0x100800) == 0 && L >= tune().ntt_pair_min_log.load(std::memory_order_relaxed);
-  if (!fusable) {
-    CSH_TRY(run_ntt<F>(d, data, ncomp, true, st, scale_tbl));
-    return run_ntt<F>(d, data, ncomp, false, st);
+  const NttPlan plan((int)d->log_n, ncomp);
+  if (plan.L == 0) return CSH_OK;
+  if (!plan.fusable()) {
+    CSH_TRY(run_passes<F>(plan, d, data, true, st, scale_tbl));
+    return run_passes<F>(plan, d, data, false, st);
   }
-  if (np > 1) CSH_TRY(run_ntt<F>(d, data, ncomp, true, st, scale_tbl, true));   // the strided passes of the inverse transform
-  const size_t tiles = d->n >> tile_log;
-  const size_t lds_bytes = size_t(4 * LZ::NL) << (tile_log + ncomp_log);
-  if (lds_bytes > 48 * 1024) CSH_TRY(raise_lds_limit((const void*)k_ntt_pass_r4<F, LZ, true, true>, (size_t)(4 * LZ::NL) << NTT_TILE_LOG));
-  const size_t units = (size_t(1) << (tile_log + ncomp_log)) >> 2;
-  const int nt = units >= 512 ? 512 : (units >= 64 ? (int)units : 64);
-  const int noswz = ((nv & 0x800) ? 0x1000 : 0) | ((nv & 0x100000) ? 0x2000 : 0);
-  const F scale = f_from_words<F>(d->n_inv_lazy);
-  hipLaunchKernelGGL((k_ntt_pass_r4<F, LZ, true, true>), dim3((unsigned)tiles), dim3(nt), lds_bytes, st, data, reinterpret_cast<const F*>(d->tw_inv_lazy), L, p.s0, p.k,
-                     p.cb, ncomp_log, scale, 1 | noswz, scale_tbl, reinterpret_cast<const F*>(d->tw_fwd_lazy));
-  CSH_HIP(hipGetLastError());
-  if (np > 1) CSH_TRY(run_ntt<F>(d, data, ncomp, false, st, nullptr, true));   // the strided passes of the forward transform
-  return CSH_OK;
+  CSH_TRY(run_passes<F>(plan, d, data, true, st, scale_tbl, 1));  // the strided passes of the inverse transform
+  PassArgs<F> a = pass_args<F>(plan, d, data, plan.passes[0], d->tw_inv_lazy, true, scale_tbl);
+  a.tw_fwd = reinterpret_cast<const F*>(d->tw_fwd_lazy);
+  CSH_TRY(launch_pass<F>(PassForm::LazyPair, true, a, plan.max_threads, st));
+  return run_passes<F>(plan, d, data, false, st, nullptr, 1);  // the strided passes of the forward transform
 }
 int ntt_run_pair_table(const Domain* d, uint64_t* data, uint32_t ncomp, const uint64_t* scale_table, hipStream_t st) {
-  if (d->curve == CSH_BN254) return run_ntt_pair<Bn254Fr>(d, (Bn254Fr*)data, ncomp, st, (const Bn254Fr*)scale_table);
-  if (d->curve == CSH_BLS12_377) return run_ntt_pair<Bls377Fr>(d, (Bls377Fr*)data, ncomp, st, (const Bls377Fr*)scale_table);
-  return run_ntt_pair<Bls381Fr>(d, (Bls381Fr*)data, ncomp, st, (const Bls381Fr*)scale_table);
+  return with_fr(d->curve, [&](auto fr) -> int {
+    using F = typename decltype(fr)::type;
+    return run_ntt_pair<F>(d, (F*)data, ncomp, st, (const F*)scale_table);
+  });
 }
 
 int ntt_run(const Domain* d, uint64_t* data, uint32_t ncomp, bool dif, hipStream_t st) {
-  if (d->curve == CSH_BN254) return run_ntt<Bn254Fr>(d, (Bn254Fr*)data, ncomp, dif, st);
-  if (d->curve == CSH_BLS12_377) return run_ntt<Bls377Fr>(d, (Bls377Fr*)data, ncomp, dif, st);
-  return run_ntt<Bls381Fr>(d, (Bls381Fr*)data, ncomp, dif, st);
+  return with_fr(d->curve, [&](auto fr) -> int {
+    using F = typename decltype(fr)::type;
+    return run_passes<F>(NttPlan((int)d->log_n, ncomp), d, (F*)data, dif, st);
+  });
 }
-// ifft_in_to_out whose last pass multiplies entry i by table[i] instead of 1/n (table from ntt_coset_table_scaled); false when
-// the lazy passes are switched off (the caller then runs the unfused sequence)
+// whether ntt_run_pair_table / ntt_coset_table_scaled apply (the table is in the lazy passes' storage form); false when the lazy
+// passes are switched off (the caller then runs the unfused sequence)
 bool ntt_scale_table_supported(const Domain* d) { return tune().ntt_lazy.load(std::memory_order_relaxed) != 0 && d->log_n >= 1; }
-int ntt_run_dif_table(const Domain* d, uint64_t* data, uint32_t ncomp, const uint64_t* scale_table, hipStream_t st) {
-  if (d->curve == CSH_BN254) return run_ntt<Bn254Fr>(d, (Bn254Fr*)data, ncomp, true, st, (const Bn254Fr*)scale_table);
-  if (d->curve == CSH_BLS12_377) return run_ntt<Bls377Fr>(d, (Bls377Fr*)data, ncomp, true, st, (const Bls377Fr*)scale_table);
-  return run_ntt<Bls381Fr>(d, (Bls381Fr*)data, ncomp, true, st, (const Bls381Fr*)scale_table);
-}
-template <class F>
-static int coset_table_scaled_t(const Domain* d, const uint64_t* shift, uint64_t* out_dev, hipStream_t st) {
-  using LZ = typename LazyOf<F>::type;
-  hipLaunchKernelGGL((k_powers_lazy_scaled<F, LZ>), dim3(grid_for((d->n + POW_CHUNK - 1) / POW_CHUNK, 256)), dim3(256), 0, st, (F*)out_dev, f_from_words<F>(shift),
-                     f_from_words<F>(d->n_inv), d->n, (int)d->log_n);
-  CSH_HIP(hipGetLastError());
-  return CSH_OK;
-}
-// table[bitrev(i)] = shift^i / n in the storage form of the lazy passes
+// table[bitrev(i)] = shift^i / n in the storage form of the lazy passes (the 1/n of the inverse transform folded into the coset table)
 int ntt_coset_table_scaled(const Domain* d, const uint64_t* shift, uint64_t* out_dev, hipStream_t st) {
-  if (d->curve == CSH_BN254) return coset_table_scaled_t<Bn254Fr>(d, shift, out_dev, st);
-  if (d->curve == CSH_BLS12_377) return coset_table_scaled_t<Bls377Fr>(d, shift, out_dev, st);
-  return coset_table_scaled_t<Bls381Fr>(d, shift, out_dev, st);
+  return with_fr(d->curve, [&](auto fr) -> int {
+    using F = typename decltype(fr)::type;
+    using LZ = typename LazyOf<F>::type;
+    hipLaunchKernelGGL((k_powers_lazy_scaled<F, LZ>), dim3(grid_for((d->n + POW_CHUNK - 1) / POW_CHUNK, 256)), dim3(256), 0, st, (F*)out_dev, f_from_words<F>(shift),
+                       f_from_words<F>(d->n_inv), d->n, (int)d->log_n);
+    CSH_HIP(hipGetLastError());
+    return CSH_OK;
+  });
 }
 // The same table, kept with the domain (see Domain::cs_table): *table = the cached copy, valid for work queued on `st` after this call
 // (the builder's stream records an event every other stream waits for), or `scratch` freshly filled when the shift is not the cached one,
@@ -1053,14 +1026,22 @@ int ntt_coset_table_scaled_cached(const Domain* dc, const uint64_t* shift, uint6
   return ntt_coset_table_scaled(d, shift, scratch, st);
 }
 int ntt_coset_table(const Domain* d, const uint64_t* shift, uint64_t* out_dev, hipStream_t st) {
-  if (d->curve == CSH_BN254) return coset_table_t<Bn254Fr>(d, shift, out_dev, st);
-  if (d->curve == CSH_BLS12_377) return coset_table_t<Bls377Fr>(d, shift, out_dev, st);
-  return coset_table_t<Bls381Fr>(d, shift, out_dev, st);
+  return with_fr(d->curve, [&](auto fr) -> int {
+    using F = typename decltype(fr)::type;
+    hipLaunchKernelGGL((k_powers<F, true>), dim3(grid_for((d->n + POW_CHUNK - 1) / POW_CHUNK, 256)), dim3(256), 0, st, (F*)out_dev, f_from_words<F>(shift), d->n,
+                       (int)d->log_n);
+    CSH_HIP(hipGetLastError());
+    return CSH_OK;
+  });
 }
 int ntt_bit_reverse(csh_curve_t c, uint64_t* data, uint32_t log_n, uint32_t ncomp, hipStream_t st) {
-  if (c == CSH_BN254) return run_bit_reverse<Bn254Fr>((Bn254Fr*)data, log_n, ncomp, st);
-  if (c == CSH_BLS12_377) return run_bit_reverse<Bls377Fr>((Bls377Fr*)data, log_n, ncomp, st);
-  return run_bit_reverse<Bls381Fr>((Bls381Fr*)data, log_n, ncomp, st);
+  if (log_n == 0) return CSH_OK;
+  return with_fr(c, [&](auto fr) -> int {
+    using F = typename decltype(fr)::type;
+    hipLaunchKernelGGL(k_bit_reverse<F>, dim3(grid_for(size_t(1) << log_n, 256)), dim3(256), 0, st, (F*)data, (int)log_n, (int)ncomp);
+    CSH_HIP(hipGetLastError());
+    return CSH_OK;
+  });
 }
 
 size_t domain_size_of(const Domain* d) { return d->n; }
@@ -1088,18 +1069,19 @@ int csh_domain_create(csh_curve_t field_of, uint32_t log_n, const uint64_t group
   CSH_REQUIRE(out, "out is NULL");
   CSH_REQUIRE(log_n <= 31, "log_n too large");
   CSH_TRY(ensure_device());
-  Domain* d = nullptr;
-  int rc;
+  uint64_t ark_generator;  // ark_{bn254, bls12_381, bls12_377}::Fr::GENERATOR
   if (field_of == CSH_BN254)
-    rc = create_domain_t<Bn254Fr>(field_of, log_n, group_gen, 5, &d);
+    ark_generator = 5;
   else if (field_of == CSH_BLS12_381)
-    rc = create_domain_t<Bls381Fr>(field_of, log_n, group_gen, 7, &d);
+    ark_generator = 7;
   else if (field_of == CSH_BLS12_377)
-    rc = create_domain_t<Bls377Fr>(field_of, log_n, group_gen, 22, &d);  // ark_bls12_377::Fr::GENERATOR
+    ark_generator = 22;
   else {
     set_error("unknown curve %d", (int)field_of);
     return CSH_ERR_INVALID;
   }
+  Domain* d = nullptr;
+  const int rc = with_fr(field_of, [&](auto fr) -> int { return create_domain_t<typename decltype(fr)::type>(field_of, log_n, group_gen, ark_generator, &d); });
   if (rc != CSH_OK) return rc;
   *out = reinterpret_cast<csh_domain_t>(d);
   return CSH_OK;
@@ -1112,12 +1094,6 @@ int csh_domain_size(csh_domain_t dom, size_t* n) {
 int csh_domain_free(csh_domain_t dom) {
   if (!dom) return CSH_OK;
   Domain* d = reinterpret_cast<Domain*>(dom);
-  if (d->tw_fwd) (void)hipFree(d->tw_fwd);
-  if (d->tw_inv) (void)hipFree(d->tw_inv);
-  if (d->tw_fwd_lazy) (void)hipFree(d->tw_fwd_lazy);
-  if (d->tw_inv_lazy) (void)hipFree(d->tw_inv_lazy);
-  if (d->cs_table) (void)hipFree(d->cs_table);
-  if (d->cs_ready) (void)hipEventDestroy(d->cs_ready);
   delete d;
   return CSH_OK;
 }

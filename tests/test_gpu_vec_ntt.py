@@ -251,6 +251,49 @@ def test_ntt_32bit_pass_rebuilds_its_tables_on_demand(gpu, curve):
         assert H.unpack(F, dg.fft_out_to_in(pv)) == want_f
 
 
+_THREADS_LOGN = (1, 5, 6, 7, 9, 11, 12)
+
+
+@pytest.fixture(scope="module")
+def threads_cases():
+    """Inputs and oracle transforms of test_ntt_threads_knob, computed once: per logn the plain vector, the share vector and the four
+    expected outputs."""
+    F = fl.BN254_FR
+    out = {}
+    for logn in _THREADS_LOGN:
+        n = 1 << logn
+        r = H.rng(700 + logn)
+        do = ntt.Domain(F, n, ntt.roots_of_unity(F)[1][logn])
+        v = H.rand_elems(F, n, r)
+        sh = [(r.randrange(F.p), r.randrange(F.p)) for _ in range(n)]
+        comps = [[s[0] for s in sh], [s[1] for s in sh]]
+        out[logn] = (H.pack(F, v), H.pack_shares(F, sh), do.ifft_in_to_out(v), do.fft_out_to_in(v),
+                     list(zip(*(do.ifft_in_to_out(c) for c in comps))), list(zip(*(do.fft_out_to_in(c) for c in comps))))
+    return out
+
+
+@pytest.mark.parametrize("variant", [2, 1, 0x102, 0x101])
+@pytest.mark.parametrize("threads", [256, 512])
+def test_ntt_threads_knob(gpu, threads_cases, threads, variant):
+    """tune "ntt_threads" caps the workgroup of the radix-2 pass (variants 2, 0x102: one lane per butterfly of a stage, clamped to
+    [64, ntt_threads]); the radix-4 pass (variants 1, 0x101) sizes its workgroups on its own (one lane per 4-entry unit, [64, 512]) and
+    must not be disturbed by the knob. With the default 2^8-element tiles of these sizes (variants 2, 1) a tile has at most 128
+    butterflies: below one wave (2^1, 2^5), one wave (2^7; 2^6 with two components), between a wave and the cap (2^9 on: 128), and two
+    to four passes from 2^9 on. With 2^11-element tiles forced (0x102, 0x101) the butterfly count also reaches the cap (2^9 at 256, 2^10
+    with two components at 512) and exceeds it (2^11), and 2^12 (2^11 with two components) is the first two-pass plan.
+    Both directions, plain and share vectors, bit-exact and canonical."""
+    F = fl.BN254_FR
+    with gpu.tuned(ntt_threads=threads, ntt_variant=variant):
+        for logn in _THREADS_LOGN:
+            dg, _ = _domain(gpu, "bn254", logn)
+            pv, psh, want_i, want_f, want_si, want_sf = threads_cases[logn]
+            for got, want, unpack in ((dg.ifft_in_to_out(pv), want_i, H.unpack), (dg.fft_out_to_in(pv), want_f, H.unpack),
+                                      (dg.ifft_in_to_out(psh, ncomp=2), want_si, H.unpack_shares),
+                                      (dg.fft_out_to_in(psh, ncomp=2), want_sf, H.unpack_shares)):
+                H.assert_canonical(F, got)
+                assert unpack(F, got) == want, (logn, threads, variant)
+
+
 def test_inherited_experiment_environment_cannot_change_a_transform(gpu):
     """with CSH_NTT_VARIANT carrying the "skip the butterflies" / "run one pass" experiment bits in the environment the
     product library still returns the oracle's transform (the bits are dropped at load; radix-4 and radix-2 pass forms, 2^12 and 2^20)."""
