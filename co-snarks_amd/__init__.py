@@ -25,6 +25,7 @@ from .bindings import (  # noqa: F401
     DeviceBuffer,
     Domain,
     device_count,
+    eval_poly,
     fr_bytes,
     groth16_h,
     have_device,
@@ -42,7 +43,9 @@ from .bindings import (  # noqa: F401
     tune_set,
     tuned,
     vec_add,
+    vec_batch_inverse,
     vec_mul,
     vec_mul_table,
+    vec_prefix_prod,
     vec_sub,
 )

@@ -416,6 +416,49 @@ def vec_mul_table(curve: int, v, table, ncomp: int = 1):
     return v
 
 
+def vec_prefix_prod(curve: int, v, n: int | None = None, out=None, stream=None):
+    """csh_vec_prefix_prod: out[i] = v[0] * ... * v[i]. A host array gives a host array; a DeviceBuffer (with n) runs the stream-ordered
+    form into `out` (default: in place) and returns that buffer."""
+    if isinstance(v, DeviceBuffer):
+        out = v if out is None else out
+        _check(lib().csh_vec_prefix_prod_dev(curve, _devptr(v), _devptr(out), C.c_size_t(n), _stream(stream)))
+        return out
+    a = _u64(v)
+    res = np.empty_like(a)
+    _check(lib().csh_vec_prefix_prod(curve, _p(a), _p(res), C.c_size_t(a.size // 4)))
+    return res
+
+
+def vec_batch_inverse(curve: int, v, n: int | None = None, out=None, zero_count=None, stream=None):
+    """csh_vec_batch_inverse: -> (out, zero_count); out[i] = v[i]^-1, zeros stay zero. Host array: host results. DeviceBuffer (with n):
+    the stream-ordered form into `out` (default: in place); zero_count = an 8-byte DeviceBuffer for the count, or None (NULL),
+    handed back as given."""
+    if isinstance(v, DeviceBuffer):
+        out = v if out is None else out
+        _check(lib().csh_vec_batch_inverse_dev(curve, _devptr(v), _devptr(out), C.c_size_t(n), _devptr(zero_count), _stream(stream)))
+        return out, zero_count
+    a = _u64(v)
+    res = np.empty_like(a)
+    zc = C.c_size_t(0)
+    _check(lib().csh_vec_batch_inverse(curve, _p(a), _p(res), C.c_size_t(a.size // 4), C.byref(zc)))
+    return res, zc.value
+
+
+def eval_poly(curve: int, coeffs, point, ncomp: int = 1, n: int | None = None, out=None, stream=None):
+    """csh_eval_poly: sum_i coeffs[i] point^i per share component -> ncomp field elements. `point` is a host element (4 limbs).
+    DeviceBuffer coefficients (with n): the stream-ordered form into the DeviceBuffer `out` (32 * ncomp bytes), which is returned."""
+    pt = _u64(point)
+    assert pt.size == 4
+    if isinstance(coeffs, DeviceBuffer):
+        out = DeviceBuffer(32 * ncomp) if out is None else out
+        _check(lib().csh_eval_poly_dev(curve, _devptr(coeffs), C.c_size_t(n), C.c_uint32(ncomp), _p(pt), _devptr(out), _stream(stream)))
+        return out
+    a = _u64(coeffs)
+    res = np.empty(4 * ncomp, dtype=np.uint64)
+    _check(lib().csh_eval_poly(curve, _p(a) if a.size else None, C.c_size_t(a.size // (4 * ncomp)), C.c_uint32(ncomp), _p(pt), _p(res)))
+    return res
+
+
 def rep3_local_mul_vec(curve: int, lhs_ab, rhs_ab, mask=None):
     l, r = _u64(lhs_ab), _u64(rhs_ab)
     n = l.size // 8

@@ -469,7 +469,11 @@ static const TuneEntry kTune[] = {
     {"stat_finish_us", "CSH_STAT_FINISH_US", &Tune::stat_finish_us},
     {"stat_d2h_slow", "CSH_STAT_D2H_SLOW", &Tune::stat_d2h_slow},
     {"stat_d2h_staged", "CSH_STAT_D2H_STAGED", &Tune::stat_d2h_staged},
+    {"scan_lane_run", "CSH_SCAN_LANE_RUN", &Tune::scan_lane_run},
+    {"scan_tile_lanes", "CSH_SCAN_TILE_LANES", &Tune::scan_tile_lanes},
+    {"scan_spine_step", "CSH_SCAN_SPINE_STEP", &Tune::scan_spine_step},
 };
+static bool is_scan_knob(std::atomic<int> Tune::*f) { return f == &Tune::scan_lane_run || f == &Tune::scan_tile_lanes || f == &Tune::scan_spine_step; }
 Tune& tune() {
   static Tune* t = [] {
     Tune* x = new Tune();
@@ -743,6 +747,10 @@ int csh_tune_set(const char* key, int value) {
       if (!kExperiments && ((e.field == &Tune::ntt_variant && (value & NTT_VARIANT_EXPERIMENT_BITS) != 0) ||
                             (e.field == &Tune::allow_unmasked_rep3 && value != 0))) {
         set_error("csh_tune_set: '%s' = %d selects a timing experiment that returns wrong results; it only exists in builds with -DCSH_EXPERIMENTS", key, value);
+        return CSH_ERR_INVALID;
+      }
+      if (is_scan_knob(e.field) && !scan_knob_ok(e.field, value)) {
+        set_error("csh_tune_set: '%s' = %d is out of range (scan_lane_run: 4 or 8; scan_tile_lanes: 64, 128, 256; scan_spine_step: a power of two, 64 .. 1024)", key, value);
         return CSH_ERR_INVALID;
       }
       (tune().*(e.field)).store(value);

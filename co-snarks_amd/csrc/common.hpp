@@ -188,8 +188,18 @@ struct Tune {
   std::atomic<int> comm_timeout_ms{120000};  // deadline of an RCCL communicator's construction (0 = on the calling thread, no deadline)
   std::atomic<int> comm_nonblocking{0};  // csh_comm_init_rank: 1 = ncclCommInitRankConfig(blocking = 0) + polling instead of ncclCommInitRank
   std::atomic<int> host_populate{0x101};  // low byte: threads populating a large D2H destination's pages before the copy (0 = off); bit 8: huge-page hint
+  // field scans (field_scan.hip): the decomposition only -- results are canonical field elements, identical under every setting
+  std::atomic<int> scan_lane_run{8};      // elements a lane reduces / scans serially in registers: 4 or 8
+  std::atomic<int> scan_tile_lanes{256};  // lanes of a tile's workgroup: 64, 128 or 256 (tile = scan_lane_run x scan_tile_lanes elements)
+  std::atomic<int> scan_spine_step{1024}; // tile totals the one-workgroup spine takes per step (= its lanes): a power of two, 64 .. 1024
 };
 Tune& tune();
+// the values csh_tune_set accepts for the field-scan keys (the launchers fall back to the defaults for anything else)
+inline bool scan_knob_ok(std::atomic<int> Tune::*key, int v) {
+  if (key == &Tune::scan_lane_run) return v == 4 || v == 8;
+  const int hi = key == &Tune::scan_tile_lanes ? 256 : 1024;
+  return v >= 64 && v <= hi && (v & (v - 1)) == 0;
+}
 
 // A Rep3 local multiplication without its correlated mask is not a valid sharing step: once opened, the products leak
 // cross terms (rep3/arithmetic.rs:132-146 always adds masking_field_elements_vec). NULL masks / seeds are therefore an

@@ -1,0 +1,411 @@
+// Whole-vector field arithmetic that is a scan or a reduction: running product, batch inverse, polynomial evaluation.
+// Reference call sites: array_prod_mul (co-plonk/src/round2.rs:164-165), inv_vec / inv_many (co-noir-common/src/mpc/rep3.rs:208-257),
+// evaluate_poly_public (co-plonk/src/round4.rs:126-132), eval_poly (rep3/poly.rs:39-68).
+//
+// One decomposition for all three: a lane takes a contiguous run of E elements (tune "scan_lane_run"), a tile is one workgroup of
+// "scan_tile_lanes" lanes, and every operation is  per-tile totals -> a spine run by ONE workgroup that walks the totals "scan_spine_step"
+// at a time with a running carry (any tile count, no recursion) -> a per-tile downsweep (the evaluation has none: its spine's carry is the
+// result). Products run in the signed lazy field; field_scan.hpp says which scale every value has.
+#include "field_scan.hpp"
+
+#include <string.h>
+
+#include <type_traits>
+
+namespace csh {
+
+template <class F>
+using LzOf = typename LazyOf<F>::type;
+
+constexpr int SCAN_TILE_MAX = 256;     // lanes of a tile kernel: 4 waves, so that the downsweep's register arrays need no occupancy
+constexpr int SCAN_SPINE_MAX = 1024;   // lanes of the spine
+constexpr size_t SCAN_MAX_N = size_t(1) << 28;
+
+struct ScanPlan {
+  int E, lg_e, lanes, lg_lanes, spine, lg_spine;
+  size_t tile, tiles;
+};
+static int ilog2(size_t v) {
+  int l = 0;
+  while ((size_t(1) << (l + 1)) <= v) ++l;
+  return l;
+}
+static ScanPlan scan_plan(size_t n) {
+  ScanPlan p;
+  p.E = tune().scan_lane_run.load(std::memory_order_relaxed);
+  p.lanes = tune().scan_tile_lanes.load(std::memory_order_relaxed);
+  p.spine = tune().scan_spine_step.load(std::memory_order_relaxed);
+  // csh_tune_set refuses other values; the environment is not validated, so anything else means the default here
+  if (!scan_knob_ok(&Tune::scan_lane_run, p.E)) p.E = 8;
+  if (!scan_knob_ok(&Tune::scan_tile_lanes, p.lanes)) p.lanes = 256;
+  if (!scan_knob_ok(&Tune::scan_spine_step, p.spine)) p.spine = 1024;
+  p.lg_e = ilog2(p.E);
+  p.lg_lanes = ilog2(p.lanes);
+  p.lg_spine = ilog2(p.spine);
+  p.tile = (size_t)p.E * p.lanes;
+  p.tiles = (n + p.tile - 1) / p.tile;
+  return p;
+}
+
+// ---- products ---------------------------------------------------------------------------------------------------------------------------
+// Launch 1: tot[tile] = product of the tile's elements, R' domain. INV: zeros count as 1 and are counted (one atomic per tile that has any).
+template <class F, bool INV>
+__global__ __launch_bounds__(SCAN_TILE_MAX) void k_scan_totals(const F* in, size_t n, int E, LzOf<F>* tot, unsigned long long* zero_count) {
+  using LZ = LzOf<F>;
+  __shared__ LZ lds[16];
+  __shared__ unsigned zc;
+  const size_t base = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * (size_t)E;
+  unsigned zeros = 0;
+  auto load = [&](size_t i) {
+    F x = F::one();
+    if (i < n) {
+      x = in[i];
+      if (INV && x.is_zero()) {
+        x = F::one();
+        ++zeros;
+      }
+    }
+    return LZ::unpack(x);
+  };
+  LZ acc = load(base);
+#pragma unroll 1
+  for (int e = 1; e < E; ++e) acc = LZ::mul(acc, load(base + e).times32());
+  const LZ total = block_reduce(to_domain(acc), lds, MulOp<LZ>());
+  if (threadIdx.x == 0) tot[blockIdx.x] = total;
+  if (INV) {
+    if (threadIdx.x == 0) zc = 0;
+    __syncthreads();
+    if (zeros) atomicAdd(&zc, zeros);
+    __syncthreads();
+    if (threadIdx.x == 0 && zc && zero_count) atomicAdd(zero_count, (unsigned long long)zc);
+  }
+}
+
+// Launch 2: pre[t] = product of tot[0 .. t) (R' domain). INV: also suf[t] = T^-1 x product of tot(t .. tiles), R scale, with T the
+// product of everything: the one inversion of the batch, a dependent chain on lane 0.
+template <class F, bool INV>
+__global__ __launch_bounds__(SCAN_SPINE_MAX) void k_scan_spine(const LzOf<F>* tot, size_t tiles, LzOf<F>* pre, LzOf<F>* suf) {
+  using LZ = LzOf<F>;
+  __shared__ ScanLds<LZ> s;
+  const size_t S = blockDim.x;
+  LZ carry = LZ::one(), total;
+  for (size_t c0 = 0; c0 < tiles; c0 += S) {
+    const size_t i = c0 + threadIdx.x;
+    const LZ p = block_excl_scan_mul<false>(i < tiles ? tot[i] : LZ::one(), carry, s, &total);
+    if (i < tiles) pre[i] = p;
+    carry = total;
+  }
+  if constexpr (INV) {
+    __shared__ InvScratch<LZ> inv;
+    __shared__ LZ tinv;
+    if (threadIdx.x == 0) tinv = from_domain(lazy_inv(carry, inv));
+    __syncthreads();
+    carry = tinv;
+    for (size_t c = (tiles + S - 1) / S; c-- > 0;) {
+      const size_t i = c * S + threadIdx.x;
+      const LZ p = block_excl_scan_mul<true>(i < tiles ? tot[i] : LZ::one(), carry, s, &total);
+      if (i < tiles) suf[i] = p;
+      carry = total;
+    }
+  }
+}
+
+// A loop over the lane's run with the index a compile-time constant: the bodies below hold whole multiplications, and a #pragma unroll
+// loop of that size silently stays a loop -- the run's register arrays would then be indexed at run time and go to scratch.
+template <int I, int N, class Fn>
+__device__ __forceinline__ void run_for(Fn&& body) {
+  if constexpr (I < N) {
+    body(std::integral_constant<int, I>());
+    run_for<I + 1, N>(body);
+  }
+}
+
+// the lane's run: elements into registers (1 past the end; INV: 1 for a zero, its bit set in *zmask), lane total in the R' domain
+template <class F, int E, bool INV>
+__device__ __forceinline__ LzOf<F> load_run(const F* in, size_t n, size_t base, F (&x)[E], uint32_t* zmask) {
+  using LZ = LzOf<F>;
+  run_for<0, E>([&](auto ic) CSH_LAMBDA_INLINE {
+    constexpr int e = decltype(ic)::value;
+    x[e] = F::one();
+    if (base + e < n) {
+      x[e] = in[base + e];
+      if (INV && x[e].is_zero()) {
+        x[e] = F::one();
+        *zmask |= 1u << e;
+      }
+    }
+  });
+  LZ acc = LZ::unpack(x[0]);
+  run_for<1, E>([&](auto ic) CSH_LAMBDA_INLINE { acc = LZ::mul(acc, LZ::unpack(x[decltype(ic)::value]).times32()); });
+  return to_domain(acc);
+}
+
+// Launch 3, running product: out[i] = in[0] ... in[i]. A lane reads its whole run before it writes any of it, and no lane touches
+// another's: out may equal in.
+template <class F, int E>
+__global__ __launch_bounds__(SCAN_TILE_MAX) void k_prefix_down(const F* in, F* out, size_t n, const LzOf<F>* pre) {
+  using LZ = LzOf<F>;
+  __shared__ ScanLds<LZ> s;
+  const size_t base = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * (size_t)E;
+  F x[E];
+  const LZ lane_total = load_run<F, E, false>(in, n, base, x, nullptr);
+  LZ total;
+  const LZ before = block_excl_scan_mul<false>(lane_total, pre[blockIdx.x], s, &total);
+  LZ acc = LZ::mul(LZ::unpack(x[0]), before);  // R scale x R' domain: R scale
+  run_for<0, E>([&](auto ic) CSH_LAMBDA_INLINE {
+    constexpr int e = decltype(ic)::value;
+    if (e) acc = LZ::mul(acc, LZ::unpack(x[e]).times32());
+    if (base + e < n) out[base + e] = acc.canonical_wide().pack();
+  });
+}
+
+// Launch 3, batch inverse: out[i] = T^-1 x (everything before i) x (everything after i); zeros stay zero.
+template <class F, int E>
+__global__ __launch_bounds__(SCAN_TILE_MAX) void k_inverse_down(const F* in, F* out, size_t n, const LzOf<F>* pre, const LzOf<F>* suf) {
+  using LZ = LzOf<F>;
+  __shared__ ScanLds<LZ> s;
+  const size_t base = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * (size_t)E;
+  F x[E];
+  uint32_t zmask = 0;
+  const LZ lane_total = load_run<F, E, true>(in, n, base, x, &zmask);
+  LZ total;
+  LZ f[E];  // f[e] = everything before element e, R' domain
+  f[0] = block_excl_scan_mul<false>(lane_total, pre[blockIdx.x], s, &total);
+  LZ after = block_excl_scan_mul<true>(lane_total, suf[blockIdx.x], s, &total);  // T^-1 x everything after the lane's run, R scale
+  run_for<1, E>([&](auto ic) CSH_LAMBDA_INLINE {
+    constexpr int e = decltype(ic)::value;
+    f[e] = LZ::mul(f[e - 1], LZ::unpack(x[e - 1]).times32());
+  });
+  run_for<0, E>([&](auto ic) CSH_LAMBDA_INLINE {
+    constexpr int e = E - 1 - decltype(ic)::value;
+    const F r = LZ::mul(f[e], after).canonical_wide().pack();
+    if (base + e < n) out[base + e] = ((zmask >> e) & 1u) ? F::zero() : r;
+    if (e) after = LZ::mul(after, LZ::unpack(x[e]).times32());
+  });
+}
+
+// ---- polynomial evaluation --------------------------------------------------------------------------------------------------------------
+// pw.p[j] = x^(2^j), R' domain, canonical and packed: every length in the decomposition is a power of two, so these are all the powers.
+constexpr int SCAN_POWERS = 32;
+template <class F>
+struct PowTable {
+  F p[SCAN_POWERS];
+};
+// lo + x^(len 2^k) hi with len = 2^base positions per lane. Values are R scale; one carry step per level keeps the limbs inside the
+// product's operand bound, fold_top() after the lane and the wave levels keeps the value below 8 p.
+template <class F>
+struct EvalOp {
+  using LZ = LzOf<F>;
+  const PowTable<F>* pw;
+  int base;
+  __device__ __forceinline__ LZ operator()(const LZ& lo, const LZ& hi, int k) const {
+    return LZ::add(lo, LZ::mul(hi, LZ::unpack(pw->p[base + k]))).normalized();
+  }
+  __device__ __forceinline__ LZ settle(const LZ& v) const { return v.fold_top(); }
+  __device__ __forceinline__ LZ identity() const { return LZ::zero(); }
+};
+
+// Launch 1: tot[comp][tile] = sum over the tile of coeffs[i][comp] x^(i - tile start); blockIdx.y = component
+template <class F>
+__global__ __launch_bounds__(SCAN_TILE_MAX) void k_eval_totals(const F* __restrict__ coeffs, size_t n, uint32_t ncomp, int E, int lg_e,
+                                                                PowTable<F> pw, LzOf<F>* tot) {
+  using LZ = LzOf<F>;
+  __shared__ LZ lds[16];
+  const size_t base = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * (size_t)E;
+  const uint32_t comp = blockIdx.y;
+  const LZ x = LZ::unpack(pw.p[0]);
+  LZ v = LZ::zero();
+#pragma unroll 1
+  for (int e = E - 1; e >= 0; --e) {  // Horner over the lane's run
+    const size_t i = base + e;
+    const LZ c = i < n ? LZ::unpack(coeffs[i * ncomp + comp]) : LZ::zero();
+    v = LZ::add(LZ::mul(v, x), c).normalized();
+  }
+  const LZ total = block_reduce(v, lds, EvalOp<F>{&pw, lg_e});
+  if (threadIdx.x == 0) tot[(size_t)comp * gridDim.x + blockIdx.x] = total;
+}
+// Launch 2: Horner over the steps of the spine, highest first; blockIdx.x = component
+template <class F>
+__global__ __launch_bounds__(SCAN_SPINE_MAX) void k_eval_spine(const LzOf<F>* tot, size_t tiles, int lg_tile, int lg_spine, PowTable<F> pw, F* out) {
+  using LZ = LzOf<F>;
+  __shared__ LZ lds[16];
+  const LZ* t = tot + (size_t)blockIdx.x * tiles;
+  const size_t S = blockDim.x;
+  const LZ xs = LZ::unpack(pw.p[lg_tile + lg_spine]);
+  LZ acc = LZ::zero();
+  for (size_t c = (tiles + S - 1) / S; c-- > 0;) {
+    const size_t i = c * S + threadIdx.x;
+    const LZ step = block_reduce(i < tiles ? t[i] : LZ::zero(), lds, EvalOp<F>{&pw, lg_tile});
+    acc = LZ::add(step, LZ::mul(acc, xs)).fold_top();
+  }
+  if (threadIdx.x == 0) out[blockIdx.x] = acc.canonical_wide().pack();
+}
+
+// ---- typed launchers ------------------------------------------------------------------------------------------------------------------
+template <class F>
+struct ScanScratch {
+  LzOf<F>*tot, *pre, *suf;
+};
+template <class F>
+static int scan_scratch(const ScanPlan& p, size_t arrays, size_t rows, hipStream_t st, ScanScratch<F>* s) {
+  Arena& ar = arena_for(st);
+  const size_t count = p.tiles * rows;
+  CSH_TRY(ar.reserve(arrays * Arena::padded(count * sizeof(LzOf<F>))));
+  s->tot = ar.take<LzOf<F>>(count);
+  s->pre = arrays > 1 ? ar.take<LzOf<F>>(count) : nullptr;
+  s->suf = arrays > 2 ? ar.take<LzOf<F>>(count) : nullptr;
+  return CSH_OK;
+}
+
+template <class F>
+static int prefix_prod_t(const uint64_t* in, uint64_t* out, size_t n, hipStream_t st) {
+  if (n == 0) return CSH_OK;
+  const ScanPlan p = scan_plan(n);
+  ScanScratch<F> s;
+  CSH_TRY(scan_scratch<F>(p, 2, 1, st, &s));
+  const dim3 grid((unsigned)p.tiles), blk(p.lanes);
+  hipLaunchKernelGGL((k_scan_totals<F, false>), grid, blk, 0, st, (const F*)in, n, p.E, s.tot, (unsigned long long*)nullptr);
+  hipLaunchKernelGGL((k_scan_spine<F, false>), dim3(1), dim3(p.spine), 0, st, s.tot, p.tiles, s.pre, s.suf);
+  if (p.E == 4) hipLaunchKernelGGL((k_prefix_down<F, 4>), grid, blk, 0, st, (const F*)in, (F*)out, n, s.pre);
+  else hipLaunchKernelGGL((k_prefix_down<F, 8>), grid, blk, 0, st, (const F*)in, (F*)out, n, s.pre);
+  CSH_HIP(hipGetLastError());
+  return CSH_OK;
+}
+
+template <class F>
+static int batch_inverse_t(const uint64_t* in, uint64_t* out, size_t n, uint64_t* zero_count, hipStream_t st) {
+  if (zero_count) CSH_HIP(hipMemsetAsync(zero_count, 0, sizeof(uint64_t), st));
+  if (n == 0) return CSH_OK;
+  const ScanPlan p = scan_plan(n);
+  ScanScratch<F> s;
+  CSH_TRY(scan_scratch<F>(p, 3, 1, st, &s));
+  const dim3 grid((unsigned)p.tiles), blk(p.lanes);
+  hipLaunchKernelGGL((k_scan_totals<F, true>), grid, blk, 0, st, (const F*)in, n, p.E, s.tot, (unsigned long long*)zero_count);
+  hipLaunchKernelGGL((k_scan_spine<F, true>), dim3(1), dim3(p.spine), 0, st, s.tot, p.tiles, s.pre, s.suf);
+  if (p.E == 4) hipLaunchKernelGGL((k_inverse_down<F, 4>), grid, blk, 0, st, (const F*)in, (F*)out, n, s.pre, s.suf);
+  else hipLaunchKernelGGL((k_inverse_down<F, 8>), grid, blk, 0, st, (const F*)in, (F*)out, n, s.pre, s.suf);
+  CSH_HIP(hipGetLastError());
+  return CSH_OK;
+}
+
+template <class F>
+static int eval_poly_t(const uint64_t* coeffs, size_t n, uint32_t ncomp, const uint64_t point[4], uint64_t* out, hipStream_t st) {
+  using LZ = LzOf<F>;
+  if (n == 0) {
+    CSH_HIP(hipMemsetAsync(out, 0, sizeof(F) * ncomp, st));
+    return CSH_OK;
+  }
+  F x;
+  memcpy(&x, point, sizeof(F));
+  if (x.is_zero()) {  // the value at 0 is the constant term
+    CSH_HIP(hipMemcpyAsync(out, coeffs, sizeof(F) * ncomp, hipMemcpyDeviceToDevice, st));
+    return CSH_OK;
+  }
+  PowTable<F> pw;  // about 30 squarings on the host: cheaper than a launch
+  LZ sq = LZ::from_fp(x);
+  for (int j = 0; j < SCAN_POWERS; ++j) {
+    pw.p[j] = sq.canonical().pack();
+    sq = LZ::sqr(sq);
+  }
+  const ScanPlan p = scan_plan(n);
+  ScanScratch<F> s;
+  CSH_TRY(scan_scratch<F>(p, 1, ncomp, st, &s));
+  hipLaunchKernelGGL(k_eval_totals<F>, dim3((unsigned)p.tiles, ncomp), dim3(p.lanes), 0, st, (const F*)coeffs, n, ncomp, p.E, p.lg_e, pw, s.tot);
+  hipLaunchKernelGGL(k_eval_spine<F>, dim3(ncomp), dim3(p.spine), 0, st, s.tot, p.tiles, p.lg_e + p.lg_lanes, p.lg_spine, pw, (F*)out);
+  CSH_HIP(hipGetLastError());
+  return CSH_OK;
+}
+
+}  // namespace csh
+
+using namespace csh;
+
+#define FR_DISPATCH(field_of, CALL)                                  \
+  switch (field_of) {                                                \
+    case CSH_BN254: { using F = Bn254Fr; return CALL; }              \
+    case CSH_BLS12_381: { using F = Bls381Fr; return CALL; }         \
+    case CSH_BLS12_377: { using F = Bls377Fr; return CALL; }         \
+    default: set_error("unknown curve %d", (int)(field_of)); return CSH_ERR_INVALID; \
+  }
+// the argument checks every entry point makes before it asks for a device
+#define SCAN_REQUIRE_FIELD(f) CSH_REQUIRE((f) == CSH_BN254 || (f) == CSH_BLS12_381 || (f) == CSH_BLS12_377, "field_of: BN254, BLS12-381 or BLS12-377")
+#define SCAN_REQUIRE_N(n) CSH_REQUIRE((n) <= SCAN_MAX_N, "n exceeds 2^28, the largest domain")
+
+extern "C" {
+
+int csh_vec_prefix_prod_dev(csh_curve_t f, const uint64_t* in, uint64_t* out, size_t n, void* stream) {
+  SCAN_REQUIRE_FIELD(f);
+  SCAN_REQUIRE_N(n);
+  CSH_REQUIRE(n == 0 || (in && out), "vec_prefix_prod: NULL argument");
+  CSH_TRY(ensure_device());
+  hipStream_t st = resolve_stream(stream);
+  FR_DISPATCH(f, prefix_prod_t<F>(in, out, n, st));
+}
+int csh_vec_batch_inverse_dev(csh_curve_t f, const uint64_t* in, uint64_t* out, size_t n, uint64_t* zero_count, void* stream) {
+  SCAN_REQUIRE_FIELD(f);
+  SCAN_REQUIRE_N(n);
+  CSH_REQUIRE(n == 0 || (in && out), "vec_batch_inverse: NULL argument");
+  CSH_TRY(ensure_device());
+  hipStream_t st = resolve_stream(stream);
+  FR_DISPATCH(f, batch_inverse_t<F>(in, out, n, zero_count, st));
+}
+int csh_eval_poly_dev(csh_curve_t f, const uint64_t* coeffs, size_t n, uint32_t ncomp, const uint64_t point[4], uint64_t* out, void* stream) {
+  SCAN_REQUIRE_FIELD(f);
+  SCAN_REQUIRE_N(n);
+  CSH_REQUIRE(ncomp >= 1 && ncomp <= 2, "ncomp must be 1 or 2");
+  CSH_REQUIRE(point && out && (n == 0 || coeffs), "eval_poly: NULL argument");
+  CSH_TRY(ensure_device());
+  hipStream_t st = resolve_stream(stream);
+  FR_DISPATCH(f, eval_poly_t<F>(coeffs, n, ncomp, point, out, st));
+}
+
+// ---- host-pointer forms: H2D, compute, D2H on the thread's stream ------------------------------------------------------------------------
+int csh_vec_prefix_prod(csh_curve_t f, const uint64_t* in, uint64_t* out, size_t n) {
+  SCAN_REQUIRE_FIELD(f);
+  SCAN_REQUIRE_N(n);
+  CSH_REQUIRE(n == 0 || (in && out), "vec_prefix_prod: NULL argument");
+  HostStage h;
+  const size_t eb = 32 * n;
+  CSH_TRY(h.begin(Arena::padded(eb)));
+  if (n == 0) return CSH_OK;
+  uint64_t* d;
+  CSH_TRY(h.up(d, in, eb));
+  CSH_TRY(csh_vec_prefix_prod_dev(f, d, d, n, h.st));
+  return h.down(out, d, eb);
+}
+int csh_vec_batch_inverse(csh_curve_t f, const uint64_t* in, uint64_t* out, size_t n, size_t* zero_count) {
+  SCAN_REQUIRE_FIELD(f);
+  SCAN_REQUIRE_N(n);
+  CSH_REQUIRE(n == 0 || (in && out), "vec_batch_inverse: NULL argument");
+  HostStage h;
+  const size_t eb = 32 * n;
+  CSH_TRY(h.begin(Arena::padded(eb) + Arena::padded(sizeof(uint64_t))));
+  if (zero_count) *zero_count = 0;
+  if (n == 0) return CSH_OK;
+  uint64_t *d, *dz;
+  CSH_TRY(h.up(d, in, eb));
+  CSH_TRY(h.up(dz, nullptr, sizeof(uint64_t)));
+  CSH_TRY(csh_vec_batch_inverse_dev(f, d, d, n, dz, h.st));
+  uint64_t zc = 0;
+  CSH_HIP(hipMemcpyAsync(&zc, dz, sizeof zc, hipMemcpyDeviceToHost, h.st));
+  CSH_TRY(h.down(out, d, eb));
+  CSH_HIP(hipStreamSynchronize(h.st));
+  if (zero_count) *zero_count = (size_t)zc;
+  return CSH_OK;
+}
+int csh_eval_poly(csh_curve_t f, const uint64_t* coeffs, size_t n, uint32_t ncomp, const uint64_t point[4], uint64_t* out) {
+  SCAN_REQUIRE_FIELD(f);
+  SCAN_REQUIRE_N(n);
+  CSH_REQUIRE(ncomp >= 1 && ncomp <= 2, "ncomp must be 1 or 2");
+  CSH_REQUIRE(point && out && (n == 0 || coeffs), "eval_poly: NULL argument");
+  HostStage h;
+  const size_t cb = 32 * n * ncomp, ob = 32 * ncomp;
+  CSH_TRY(h.begin(Arena::padded(cb) + Arena::padded(ob)));
+  uint64_t *dc, *dout;
+  CSH_TRY(h.up(dc, coeffs, cb));
+  CSH_TRY(h.up(dout, nullptr, ob));
+  CSH_TRY(csh_eval_poly_dev(f, dc, n, ncomp, point, dout, h.st));
+  return h.down(out, dout, ob);
+}
+
+}  // extern "C"

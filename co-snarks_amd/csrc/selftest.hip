@@ -11,6 +11,7 @@
 #include "curve_lazy.hpp"
 #include "chacha.hpp"
 #include "field29.hpp"
+#include "field_scan.hpp"
 #include "msm_digits.hpp"
 
 using namespace csh;
@@ -288,7 +289,77 @@ static int zero_flags_t(const int32_t* limbs, size_t n, uint8_t* flags) {
   }
   return CSH_OK;
 }
+// Host run of the field scans' arithmetic (field_scan.hip) with the limb-bound checks on: the same routines and the same order of
+// scales, lane after lane instead of side by side. op 0: running product; 1: batch inverse (zeros stay zero); 2: lazy_inv alone
+// (n = 1). run = elements per lane. All arkworks-Montgomery in and out.
+template <class LZ, class F>
+static int scan_host_t(int op, const uint64_t* in, size_t n, int run, uint64_t* out) {
+  std::vector<F> x(n);
+  if (n) memcpy(x.data(), in, n * sizeof(F));
+  InvScratch<LZ> scratch;
+  if (op == 2) {
+    for (size_t i = 0; i < n; ++i) {
+      const F r = lazy_inv(LZ::from_fp(x[i]), scratch).to_fp();
+      memcpy(out + 4 * i, &r, sizeof(F));
+    }
+    return CSH_OK;
+  }
+  std::vector<F> y(x);
+  if (op == 1)
+    for (F& v : y)
+      if (v.is_zero()) v = F::one();
+  const size_t lanes = (n + run - 1) / run;
+  std::vector<LZ> tot(lanes), pre(lanes), suf(lanes);
+  for (size_t l = 0; l < lanes; ++l) {  // k_scan_totals / load_run
+    LZ acc = LZ::unpack(y[l * run]);
+    for (size_t i = l * run + 1; i < n && i < (l + 1) * run; ++i) acc = LZ::mul(acc, LZ::unpack(y[i]).times32());
+    tot[l] = to_domain(acc);
+  }
+  LZ carry = LZ::one();
+  for (size_t l = 0; l < lanes; ++l) {  // block_excl_scan_mul<false>
+    pre[l] = carry;
+    carry = LZ::mul(carry, tot[l]);
+  }
+  if (op == 1) {
+    carry = from_domain(lazy_inv(carry, scratch));  // k_scan_spine<INV>
+    for (size_t l = lanes; l-- > 0;) {
+      suf[l] = carry;
+      carry = LZ::mul(carry, tot[l]);
+    }
+  }
+  for (size_t l = 0; l < lanes; ++l) {
+    const size_t lo = l * run, hi = (l + 1) * run < n ? (l + 1) * run : n;
+    if (op == 0) {  // k_prefix_down
+      LZ acc = LZ::mul(LZ::unpack(y[lo]), pre[l]);
+      for (size_t i = lo; i < hi; ++i) {
+        if (i > lo) acc = LZ::mul(acc, LZ::unpack(y[i]).times32());
+        const F r = acc.canonical_wide().pack();
+        memcpy(out + 4 * i, &r, sizeof(F));
+      }
+    } else {  // k_inverse_down
+      std::vector<LZ> f(hi - lo);
+      f[0] = pre[l];
+      for (size_t i = lo + 1; i < hi; ++i) f[i - lo] = LZ::mul(f[i - lo - 1], LZ::unpack(y[i - 1]).times32());
+      LZ after = suf[l];
+      for (size_t i = hi; i-- > lo;) {
+        const F r = x[i].is_zero() ? F::zero() : LZ::mul(f[i - lo], after).canonical_wide().pack();
+        memcpy(out + 4 * i, &r, sizeof(F));
+        after = LZ::mul(after, LZ::unpack(y[i]).times32());
+      }
+    }
+  }
+  return CSH_OK;
+}
+
 extern "C" {
+
+int csh_selftest_scan_host(int field_of, int op, const uint64_t* in, size_t n, int run, uint64_t* out) {
+  if (op < 0 || op > 2 || run < 1) return CSH_ERR_INVALID;
+  if (field_of == CSH_BN254) return scan_host_t<Fr29s, Bn254Fr>(op, in, n, run, out);
+  if (field_of == CSH_BLS12_381) return scan_host_t<Bls381Fr29s, Bls381Fr>(op, in, n, run, out);
+  if (field_of == CSH_BLS12_377) return scan_host_t<Bls377Fr29s, Bls377Fr>(op, in, n, run, out);
+  return CSH_ERR_INVALID;
+}
 
 // type: 0 Fq29s, 1 Fq28s, 2 Fr29s, 3 Fq28s377, 4 Fq29s2, 5 Fq28s2, 6 Fq28s377x2
 int csh_selftest_zero_flags(int type, const int32_t* limbs, size_t n, uint8_t* flags) {

@@ -362,6 +362,44 @@ def driver_local_mul_vec(curve: int, driver: int, a_mont, b_mont, seed: int = 1)
     return out.reshape(3, n, 4) if driver == REP3 else out.reshape(n, 4)
 
 
+def driver_eval_poly(curve: int, driver: int, coeffs_mont, point_mont, seed: int = 1):
+    """::eval_poly / ::evaluate_poly_public. Plain / Shamir: (4,) limbs; Rep3: (3, 2, 4), every party's share of the evaluation
+    (the coefficients are shared inside with `seed`)."""
+    c = np.ascontiguousarray(coeffs_mont, dtype=np.uint64).reshape(-1, 4)
+    pt = np.ascontiguousarray(point_mont, dtype=np.uint64).reshape(4)
+    out = np.zeros((6 if driver == REP3 else 1) * 4, dtype=np.uint64)
+    rc = glib().cog16_driver_eval_poly(curve, driver, c.ctypes.data_as(C.c_void_p), C.c_size_t(len(c)), pt.ctypes.data_as(C.c_void_p),
+                                       C.c_uint64(seed), out.ctypes.data_as(C.c_void_p))
+    if rc < 0:
+        raise CoSnarksHipError(glib().cog16_last_error().decode())
+    return out.reshape(3, 2, 4) if driver == REP3 else out
+
+
+def driver_inv_vec(curve: int, driver: int, a_mont, seed: int = 1, leaking_zeros=False, in_place=False):
+    """::inv_vec, ::inv_many_in_place (in_place) or ::inv_many_in_place_leaking_zeros (leaking_zeros). Plain: (n, 4); Rep3:
+    (3, n, 2, 4); Shamir (three parties, threshold 1): (3, n, 4). The strict forms raise the reference's message on a zero."""
+    a = np.ascontiguousarray(a_mont, dtype=np.uint64).reshape(-1, 4)
+    n = len(a)
+    per = {PLAIN: 1, REP3: 6, SHAMIR: 3}[driver]
+    out = np.zeros(per * n * 4, dtype=np.uint64)
+    rc = glib().cog16_driver_inv_vec(curve, driver, a.ctypes.data_as(C.c_void_p), C.c_size_t(n), C.c_uint64(seed),
+                                     1 if leaking_zeros else 2 if in_place else 0, out.ctypes.data_as(C.c_void_p))
+    if rc < 0:
+        raise CoSnarksHipError(glib().cog16_last_error().decode())
+    return out.reshape(3, n, 2, 4) if driver == REP3 else out.reshape(3, n, 4) if driver == SHAMIR else out.reshape(n, 4)
+
+
+def driver_array_prod_mul(curve: int, a1_mont, a2_mont, a3_mont, inv: bool = False):
+    """PlainPlonkDriver::array_prod_mul: the running product of a1 a2 a3, or its inverses -> (n, 4)."""
+    arrs = [np.ascontiguousarray(x, dtype=np.uint64).reshape(-1, 4) for x in (a1_mont, a2_mont, a3_mont)]
+    n = len(arrs[0])
+    out = np.zeros(n * 4, dtype=np.uint64)
+    rc = glib().cog16_driver_array_prod_mul(curve, int(inv), *[x.ctypes.data_as(C.c_void_p) for x in arrs], C.c_size_t(n), out.ctypes.data_as(C.c_void_p))
+    if rc < 0:
+        raise CoSnarksHipError(glib().cog16_last_error().decode())
+    return out.reshape(n, 4)
+
+
 def driver_msm(curve: int, driver: int, points: np.ndarray, scalars_mont, seed: int = 1):
     """::msm_public_points(_g1) / HonkCurve::fast_msm (driver FAST_MSM; curve 2 = Grumpkin). Returns affine limbs:
     (point_words,) or for Rep3 (3, 2, point_words): the (a, b) point share of every party."""

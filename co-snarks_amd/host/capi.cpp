@@ -1024,6 +1024,114 @@ int driver_mul_t(int driver, const uint64_t* a, const uint64_t* b, size_t n, uin
   return 0;
 }
 
+// ::eval_poly / ::evaluate_poly_public. Plain / Shamir: 4 limbs (a linear map of whatever vector it is handed); Rep3: the coefficients
+// are shared inside with `seed`, out = [party][component][limb].
+template <class P>
+int driver_eval_poly_t(int driver, const uint64_t* coeffs, size_t n, const uint64_t* point, uint64_t seed, uint64_t* out) {
+  using Fr = typename P::Fr;
+  std::vector<Fr> v(n);
+  if (n) memcpy((void*)v.data(), coeffs, 32 * n);
+  Fr x;
+  memcpy((void*)&x, point, 32);
+  if (driver != 1) {
+    const Fr e = driver == 0 ? PlainPlonkDriver<P>::evaluate_poly_public(v, x).first : ShamirPlonkDriver<P>::eval_poly(v, x);
+    memcpy(out, &e, 32);
+    return 0;
+  }
+  std::vector<Rep3PrimeFieldShare<Fr>> sh[3];
+  Rep3Sharer<Fr>(seed).share(v, sh);
+  for (int p = 0; p < 3; ++p) {  // local operation: no network, no randomness
+    const auto e = p == 0 ? Rep3PlonkDriver<P>::evaluate_poly_public(sh[p], x).first : Rep3PlonkDriver<P>::eval_poly(sh[p], x);
+    memcpy(out + 8 * p, &e, 64);
+  }
+  return 0;
+}
+
+// ::inv_vec (leaking_zeros = 0), ::inv_many_in_place_leaking_zeros (1) and ::inv_many_in_place (2: inv_vec's protocol, the noir
+// drivers' name and message). Plain: (n, 4); Rep3: [party][n][component][limb]; Shamir (3 parties, threshold 1):
+// [party][n][limb]. The values are shared inside with `seed`; a dealer hands the Shamir parties their double sharings.
+template <class P>
+int driver_inv_vec_t(int driver, const uint64_t* a, size_t n, uint64_t seed, int leaking_zeros, uint64_t* out) {
+  using Fr = typename P::Fr;
+  std::vector<Fr> v(n);
+  if (n) memcpy((void*)v.data(), a, 32 * n);
+  if (driver == 0) {
+    if (leaking_zeros == 1) PlainPlonkDriver<P>::inv_many_in_place_leaking_zeros(v);
+    else if (leaking_zeros == 2) PlainPlonkDriver<P>::inv_many_in_place(v);
+    else v = PlainPlonkDriver<P>::inv_vec(std::move(v));
+    if (n) memcpy(out, v.data(), 32 * n);
+    return 0;
+  }
+  if (driver == 1) {
+    std::vector<Rep3PrimeFieldShare<Fr>> sh[3];
+    Rep3Sharer<Fr>(seed).share(v, sh);
+    auto nets = LocalNetwork::new_parties(3);
+    run_three_parties(seed, [&](int p, Rep3State& st) {
+      try {
+        std::vector<Rep3PrimeFieldShare<Fr>> r = sh[p];
+        if (leaking_zeros == 1) Rep3PlonkDriver<P>::inv_many_in_place_leaking_zeros(r, nets[p], st);
+        else if (leaking_zeros == 2) Rep3PlonkDriver<P>::inv_many_in_place(r, nets[p], st);
+        else r = Rep3PlonkDriver<P>::inv_vec(sh[p], nets[p], st);
+        if (n) memcpy(out + 8 * n * p, r.data(), 64 * n);
+      } catch (...) {
+        nets[p].abort();
+        throw;
+      }
+    });
+    return 0;
+  }
+  const int np = 3, t = 1;
+  SeededShamirSharer<Fr> sharer(seed, np), dealer(seed, np, /*domain=*/12);
+  std::vector<std::vector<Fr>> sh(np, std::vector<Fr>(n));
+  std::vector<std::deque<std::pair<Fr, Fr>>> pairs(np);
+  for (size_t i = 0; i < n; ++i) {
+    const auto s = sharer.share(v[i], t);
+    const Fr rv = dealer.rnd();
+    const auto st = dealer.share(rv, t), s2t = dealer.share(rv, 2 * t);
+    for (int p = 0; p < np; ++p) {
+      sh[p][i] = s[p];
+      pairs[p].push_back({st[p], s2t[p]});
+    }
+  }
+  auto nets = LocalNetwork::new_parties(np);
+  std::string errs[3];
+  std::vector<std::thread> th;
+  for (int p = 0; p < np; ++p) {
+    th.emplace_back([&, p] {
+      try {
+        check(csh_init(0), "csh_init");
+        auto state = ShamirState<Fr>::create(p, np, t, pairs[p]);
+        std::vector<Fr> r = sh[p];
+        if (leaking_zeros == 1) ShamirPlonkDriver<P>::inv_many_in_place_leaking_zeros(r, nets[p], state);
+        else if (leaking_zeros == 2) ShamirPlonkDriver<P>::inv_many_in_place(r, nets[p], state);
+        else r = ShamirPlonkDriver<P>::inv_vec(sh[p], nets[p], state);
+        if (n) memcpy(out + 4 * n * p, r.data(), 32 * n);
+      } catch (const std::exception& e) {
+        errs[p] = e.what();
+        nets[p].abort();
+      }
+    });
+  }
+  for (auto& x : th) x.join();
+  throw_first_party_error(errs, np);
+  return 0;
+}
+
+// PlainPlonkDriver::array_prod_mul (co-plonk plain.rs:195-247): out (n, 4)
+template <class P>
+int driver_array_prod_mul_t(int inv, const uint64_t* a1, const uint64_t* a2, const uint64_t* a3, size_t n, uint64_t* out) {
+  using Fr = typename P::Fr;
+  std::vector<Fr> v[3];
+  const uint64_t* in[3] = {a1, a2, a3};
+  for (int k = 0; k < 3; ++k) {
+    v[k].resize(n);
+    if (n) memcpy((void*)v[k].data(), in[k], 32 * n);
+  }
+  const std::vector<Fr> r = PlainPlonkDriver<P>::array_prod_mul(inv != 0, v[0], v[1], v[2]);
+  if (n) memcpy(out, r.data(), 32 * n);
+  return 0;
+}
+
 template <class C, class P>
 int driver_msm_t(int driver, const void* points, size_t n_points, const uint64_t* scalars, size_t n_scalars, uint64_t seed, void* out) {
   using Fr = typename C::Fr;
@@ -1341,6 +1449,39 @@ int cog16_driver_local_mul_vec(int curve, int driver, const uint64_t* a, const u
   try {
     if (curve == 0) return driver_mul_t<Bn254>(driver, a, b, n, seed, out);
     if (curve == 1) return driver_mul_t<Bls12_381>(driver, a, b, n, seed, out);
+    g_err = "unknown curve";
+    return -1;
+  } catch (const std::exception& e) {
+    g_err = e.what();
+    return -1;
+  }
+}
+int cog16_driver_eval_poly(int curve, int driver, const uint64_t* coeffs, size_t n, const uint64_t* point, uint64_t seed, uint64_t* out) {
+  try {
+    if (curve == 0) return driver_eval_poly_t<Bn254>(driver, coeffs, n, point, seed, out);
+    if (curve == 1) return driver_eval_poly_t<Bls12_381>(driver, coeffs, n, point, seed, out);
+    g_err = "unknown curve";
+    return -1;
+  } catch (const std::exception& e) {
+    g_err = e.what();
+    return -1;
+  }
+}
+int cog16_driver_inv_vec(int curve, int driver, const uint64_t* a, size_t n, uint64_t seed, int leaking_zeros, uint64_t* out) {
+  try {
+    if (curve == 0) return driver_inv_vec_t<Bn254>(driver, a, n, seed, leaking_zeros, out);
+    if (curve == 1) return driver_inv_vec_t<Bls12_381>(driver, a, n, seed, leaking_zeros, out);
+    g_err = "unknown curve";
+    return -1;
+  } catch (const std::exception& e) {
+    g_err = e.what();
+    return -1;
+  }
+}
+int cog16_driver_array_prod_mul(int curve, int inv, const uint64_t* a1, const uint64_t* a2, const uint64_t* a3, size_t n, uint64_t* out) {
+  try {
+    if (curve == 0) return driver_array_prod_mul_t<Bn254>(inv, a1, a2, a3, n, out);
+    if (curve == 1) return driver_array_prod_mul_t<Bls12_381>(inv, a1, a2, a3, n, out);
     g_err = "unknown curve";
     return -1;
   } catch (const std::exception& e) {

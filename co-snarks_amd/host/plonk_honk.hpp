@@ -4,8 +4,13 @@
 //       impls co-plonk/src/mpc/{plain.rs:60-185, rep3.rs:60-175, shamir.rs}, Domains (co-plonk/src/types.rs:70-109)
 //   NoirUltraHonkProver::{local_mul_vec, msm_public_points, fft, ifft}        co-noir/co-noir-common/src/mpc/mod.rs:236-379,
 //       impls mpc/{plain.rs:271, rep3.rs:258-288, shamir.rs:255}, HonkCurve::fast_msm (honk_curve.rs:35, 81-83, 175-177)
-// Only these data-parallel methods are mirrored: the PLONK rounds / sumcheck / relations above them are control logic and
-// stay in the Rust host (SURVEY.md 8 "out of scope").
+//   CircomPlonkProver::{evaluate_poly_public, inv_vec, array_prod_mul (plain driver)}   co-plonk/src/mpc.rs, round2.rs:164-165, round4.rs:126-132
+//   NoirUltraHonkProver::{eval_poly, inv_many_in_place, inv_many_in_place_leaking_zeros}  co-noir-common/src/mpc/rep3.rs:208-257, rep3/poly.rs:39-68
+// These data-parallel methods are mirrored, the whole-vector scans among them (running product, batch inverse, polynomial
+// evaluation: csh_vec_prefix_prod / csh_vec_batch_inverse / csh_eval_poly). The PLONK rounds / sumcheck / relations above them are
+// control logic and stay in the Rust host (SURVEY.md 8 "out of scope"). NOT mirrored: the Rep3 / Shamir array_prod_mul
+// (co-plonk/src/mpc/rep3.rs:187-260), which is four network multiplication rounds around the same running product -- its opened
+// vector would go through csh_vec_prefix_prod exactly as the plain driver's does below.
 #pragma once
 #include "groth16.hpp"
 
@@ -101,6 +106,32 @@ inline Proj<F> msm_unchecked(csh_curve_t curve, csh_group_t group, const std::ve
   if (out.is_inf()) return Proj<F>::inf();
   return Proj<F>::from_affine(AffineT<F>{out.x, out.y});
 }
+// sum_i coeffs[i] point^i on every component of the share type (poly::eval_poly, rep3/poly.rs:39-68; DensePolynomial::evaluate)
+template <class P, class Share>
+inline Share eval_poly(const std::vector<Share>& coeffs, const typename P::Fr& point) {
+  constexpr uint32_t ncomp = sizeof(Share) / sizeof(typename P::Fr);
+  Share out{};
+  check(csh_eval_poly(P::ID, (const uint64_t*)coeffs.data(), coeffs.size(), ncomp, (const uint64_t*)&point, (uint64_t*)&out), "csh_eval_poly");
+  return out;
+}
+// y[i] <- y[i]^-1 with ONE field inversion (zeros stay zero); returns how many zeros there were
+template <class P>
+inline size_t batch_inverse(std::vector<typename P::Fr>& y) {
+  size_t zeros = 0;
+  check(csh_vec_batch_inverse(P::ID, (const uint64_t*)y.data(), (uint64_t*)y.data(), y.size(), &zeros), "csh_vec_batch_inverse");
+  return zeros;
+}
+// The shared tail of every MPC inversion (rep3/arithmetic.rs:233-246, shamir/arithmetic.rs:157-172, co-noir-common rep3.rs:216-257):
+// y = open(a r) is public; the result is r y^-1 -- one batch inverse on y, one table multiplication on the shares of r. A zero makes
+// the strict forms fail with the reference's message; the leaking form leaves the default (all-zero) share there, which r * 0 is.
+template <class P, class Share>
+inline std::vector<Share> unmask_inverse(std::vector<Share> r, std::vector<typename P::Fr> y, const char* zero_message) {
+  const size_t zeros = batch_inverse<P>(y);
+  if (zeros && zero_message) throw Error(zero_message);
+  constexpr uint32_t ncomp = sizeof(Share) / sizeof(typename P::Fr);
+  check(csh_vec_mul_table(P::ID, (uint64_t*)r.data(), (const uint64_t*)y.data(), r.size(), ncomp), "csh_vec_mul_table");
+  return r;
+}
 }  // namespace detail
 
 template <class F>
@@ -148,6 +179,30 @@ struct PlainPlonkDriver {
   static PointShareG1 msm_public_points(const std::vector<AffineT<Fq>>& points, const std::vector<Fr>& scalars) {  // co-noir plain.rs:271
     return msm_public_points_g1(points, scalars);
   }
+  // co-plonk plain.rs:186-193: (evaluation, the coefficients handed back)
+  static std::pair<Fr, std::vector<Fr>> evaluate_poly_public(std::vector<Fr> coeffs, const Fr& point) {
+    const Fr e = detail::eval_poly<P, Fr>(coeffs, point);
+    return {e, std::move(coeffs)};
+  }
+  static Fr eval_poly(const std::vector<Fr>& coeffs, const Fr& point) { return detail::eval_poly<P, Fr>(coeffs, point); }
+  // co-plonk plain.rs:127-140 / co-noir plain.rs:240-252: every element's own inverse() there
+  static std::vector<Fr> inv_vec(std::vector<Fr> a) {
+    if (detail::batch_inverse<P>(a)) throw Error("Cannot invert zero");
+    return a;
+  }
+  static void inv_many_in_place(std::vector<Fr>& a) {
+    a = inv_vec(std::move(a));
+  }
+  static void inv_many_in_place_leaking_zeros(std::vector<Fr>& a) { detail::batch_inverse<P>(a); }
+  // co-plonk plain.rs:195-247: the blinding r cancels in the clear, what is left is the running product of a1 a2 a3 (or its inverses)
+  static std::vector<Fr> array_prod_mul(bool inv, const std::vector<Fr>& a1, const std::vector<Fr>& a2, const std::vector<Fr>& a3) {
+    const size_t n = std::min(a1.size(), std::min(a2.size(), a3.size()));  // izip!
+    std::vector<Fr> v(n);
+    check(csh_vec_mul(P::ID, (const uint64_t*)a1.data(), (const uint64_t*)a2.data(), (uint64_t*)v.data(), n), "csh_vec_mul");
+    check(csh_vec_mul(P::ID, (const uint64_t*)v.data(), (const uint64_t*)a3.data(), (uint64_t*)v.data(), n), "csh_vec_mul");
+    check(csh_vec_prefix_prod(P::ID, (const uint64_t*)v.data(), (uint64_t*)v.data(), n), "csh_vec_prefix_prod");
+    return inv ? inv_vec(std::move(v)) : v;
+  }
 };
 
 // ---- Rep3 drivers (co-plonk/src/mpc/rep3.rs, co-noir-common/src/mpc/rep3.rs) -------------------------------------------
@@ -191,6 +246,43 @@ struct Rep3PlonkDriver {
   static PointShareG1 msm_public_points(const std::vector<AffineT<Fq>>& points, const std::vector<ArithmeticShare>& scalars) {
     return msm_public_points_g1(points, scalars);
   }
+  // poly::eval_poly on {a, b} shares (rep3/poly.rs:39-68): a linear map, no network
+  static std::pair<ArithmeticShare, std::vector<ArithmeticShare>> evaluate_poly_public(std::vector<ArithmeticShare> coeffs, const Fr& point) {  // co-plonk rep3.rs:177-183
+    const ArithmeticShare e = detail::eval_poly<P, ArithmeticShare>(coeffs, point);
+    return {e, std::move(coeffs)};
+  }
+  static ArithmeticShare eval_poly(const std::vector<ArithmeticShare>& coeffs, const Fr& point) { return detail::eval_poly<P, ArithmeticShare>(coeffs, point); }
+  // arithmetic::mul_open_vec (rep3/arithmetic.rs:342-354): masked local products, broadcast, sum of the three
+  static std::vector<Fr> mul_open_vec(const std::vector<ArithmeticShare>& a, const std::vector<ArithmeticShare>& b, const LocalNetwork& net, State& st) {
+    const std::vector<Fr> mine = local_mul_vec(a, b, st);
+    const size_t bytes = sizeof(Fr) * mine.size();
+    Bytes m(bytes);
+    if (bytes) memcpy(m.data(), mine.data(), bytes);
+    net.send((net.id() + 1) % 3, m);
+    net.send((net.id() + 2) % 3, std::move(m));
+    const Bytes pv = net.recv((net.id() + 2) % 3), nx = net.recv((net.id() + 1) % 3);
+    if (pv.size() != bytes || nx.size() != bytes) throw Error("mul_open_vec: invalid number of elements received");
+    std::vector<Fr> y(mine.size());
+    const uint64_t* parts[3] = {(const uint64_t*)mine.data(), (const uint64_t*)pv.data(), (const uint64_t*)nx.data()};
+    const Fr ones[3] = {Fr::one(), Fr::one(), Fr::one()};
+    check(csh_lincomb(P::ID, parts, (const uint64_t*)ones, 3, (uint64_t*)y.data(), y.size()), "csh_lincomb");
+    return y;
+  }
+  static std::vector<ArithmeticShare> inverse_of(const std::vector<ArithmeticShare>& a, const LocalNetwork& net, State& st, const char* zero_message) {
+    std::vector<ArithmeticShare> r(a.size());
+    for (auto& x : r) x = Rep3Groth16Driver<P>::rand(&net, st);
+    std::vector<Fr> y = mul_open_vec(a, r, net, st);
+    return detail::unmask_inverse<P, ArithmeticShare>(std::move(r), std::move(y), zero_message);
+  }
+  static std::vector<ArithmeticShare> inv_vec(const std::vector<ArithmeticShare>& a, const LocalNetwork& net, State& st) {  // rep3/arithmetic.rs:233-246
+    return inverse_of(a, net, st, "During execution of inverse in MPC: cannot compute inverse of zero");
+  }
+  static void inv_many_in_place(std::vector<ArithmeticShare>& a, const LocalNetwork& net, State& st) {  // co-noir-common rep3.rs:216-235
+    a = inverse_of(a, net, st, "Cannot compute inverse of zero");
+  }
+  static void inv_many_in_place_leaking_zeros(std::vector<ArithmeticShare>& a, const LocalNetwork& net, State& st) {  // rep3.rs:237-257
+    a = inverse_of(a, net, st, nullptr);
+  }
 };
 
 // ---- Shamir drivers (co-plonk/src/mpc/shamir.rs, co-noir-common/src/mpc/shamir.rs) ----------------------------------
@@ -213,6 +305,47 @@ struct ShamirPlonkDriver {
   }
   static PointShareG1 msm_public_points(const std::vector<AffineT<Fq>>& points, const std::vector<Fr>& scalars) {  // co-noir shamir.rs:255
     return msm_public_points_g1(points, scalars);
+  }
+  // linear on the shares (shamir/poly.rs; co-plonk shamir.rs evaluate_poly_public)
+  static std::pair<Fr, std::vector<Fr>> evaluate_poly_public(std::vector<Fr> coeffs, const Fr& point) {
+    const Fr e = detail::eval_poly<P, Fr>(coeffs, point);
+    return {e, std::move(coeffs)};
+  }
+  static Fr eval_poly(const std::vector<Fr>& coeffs, const Fr& point) { return detail::eval_poly<P, Fr>(coeffs, point); }
+  // arithmetic::mul_open_vec (shamir/arithmetic.rs:262-290): degree-2t products, broadcast_next(n, 2t + 1) (network.rs:96-126),
+  // reconstruction with open_lagrange_2t
+  static std::vector<Fr> mul_open_vec(const std::vector<Fr>& a, const std::vector<Fr>& b, const LocalNetwork& net, ShamirState<Fr>& st) {
+    UnitState us;
+    const std::vector<Fr> mine = local_mul_vec(a, b, us);
+    const size_t n = st.num_parties, num = 2 * st.threshold + 1, bytes = sizeof(Fr) * mine.size();
+    Bytes m(bytes);
+    if (bytes) memcpy(m.data(), mine.data(), bytes);
+    for (size_t s = 1; s < num; ++s) net.send((int)((st.id + s) % n), m);
+    std::vector<Bytes> got;
+    std::vector<const uint64_t*> parts{(const uint64_t*)mine.data()};
+    for (size_t r = 1; r < num; ++r) {
+      got.push_back(net.recv((int)((st.id + n - r) % n)));
+      if (got.back().size() != bytes) throw Error("mul_open_vec: invalid number of elements received");
+    }
+    for (const Bytes& g : got) parts.push_back((const uint64_t*)g.data());
+    std::vector<Fr> y(mine.size());
+    check(csh_lincomb(P::ID, parts.data(), (const uint64_t*)st.open_lagrange_2t.data(), num, (uint64_t*)y.data(), y.size()), "csh_lincomb");
+    return y;
+  }
+  static std::vector<Fr> inverse_of(const std::vector<Fr>& a, const LocalNetwork& net, ShamirState<Fr>& st, const char* zero_message) {
+    std::vector<Fr> r(a.size());
+    for (auto& x : r) x = ShamirGroth16Driver<P>::rand(&net, st);
+    std::vector<Fr> y = mul_open_vec(a, r, net, st);
+    return detail::unmask_inverse<P, Fr>(std::move(r), std::move(y), zero_message);
+  }
+  static std::vector<Fr> inv_vec(const std::vector<Fr>& a, const LocalNetwork& net, ShamirState<Fr>& st) {  // shamir/arithmetic.rs:157-172
+    return inverse_of(a, net, st, "Cannot compute inverse of zero");
+  }
+  static void inv_many_in_place(std::vector<Fr>& a, const LocalNetwork& net, ShamirState<Fr>& st) {  // co-noir-common shamir.rs
+    a = inverse_of(a, net, st, "Cannot compute inverse of zero");
+  }
+  static void inv_many_in_place_leaking_zeros(std::vector<Fr>& a, const LocalNetwork& net, ShamirState<Fr>& st) {  // shamir.rs:228-248
+    a = inverse_of(a, net, st, nullptr);
   }
 };
 

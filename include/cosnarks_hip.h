@@ -119,7 +119,8 @@ int csh_device_count(int* count);
  * equal length and offset -- and return when it has written their results; 0 = every call uploads and runs for itself; counter
  * "stat_uploads_shared"), "host_timing" (diagnostics: phase times of the host-facing witness map in "stat_wm_h2d_us" / "_dev_us" / "_d2h_us"),
  * "msm_balanced" (1 = default: the MSM's windows share the scalar bits evenly, widths c and c - 1; 0 = uniform c-bit windows),
- * "msm_w" (balanced windows: forced number of windows, 0 = the tuned count). Read-only counters
+ * "msm_w" (balanced windows: forced number of windows, 0 = the tuned count), "scan_lane_run" / "scan_tile_lanes" / "scan_spine_step"
+ * (field scans, see there). Read-only counters
  * (csh_tune_get): "stat_arena_grows", "stat_lanes", "stat_populate_us", "stat_join_wait_us", "stat_finish_us", "stat_d2h_slow",
  * "stat_d2h_staged". */
 int csh_tune_set(const char* key, int value);
@@ -308,6 +309,30 @@ int csh_rep3_to_shamir_vec(csh_curve_t field_of, const uint64_t* in_ab, const ui
  * rep3/arithmetic.rs:249-271). `shares` = k host pointers. */
 int csh_lincomb(csh_curve_t field_of, const uint64_t* const* shares, const uint64_t* coeffs /* k*4 */,
                 size_t k, uint64_t* out, size_t n);
+
+/* ---- field scans: running product, batch inverse, polynomial evaluation -------------------------------
+ * The whole-vector steps between two transforms of a PLONK / UltraHonk proof that are a scan or a reduction, not element-wise.
+ * `field_of`, the limbs, `ncomp` and `stream` as above; n = 0 .. 2^28 (the reference's largest domain). The _dev forms are
+ * stream-ordered: no host synchronisation, scratch from the stream's workspace. Outputs are canonical. tune keys "scan_lane_run"
+ * (4 or 8 elements per lane), "scan_tile_lanes" (64 / 128 / 256 lanes per tile; a tile is their product), "scan_spine_step"
+ * (64 .. 1024, a power of two: tile totals per step of the one-workgroup spine) change the decomposition only, never a result;
+ * csh_tune_set refuses other values. */
+/* out[i] = in[0] * ... * in[i]: the serial running product of array_prod_mul (co-plonk/src/round2.rs:164-165, impls
+ * co-plonk/src/mpc/rep3.rs:211-213, mpc/plain.rs, mpc/shamir.rs). out may equal in. */
+int csh_vec_prefix_prod_dev(csh_curve_t field_of, const uint64_t* in_dev, uint64_t* out_dev, size_t n, void* stream);
+int csh_vec_prefix_prod(csh_curve_t field_of, const uint64_t* in, uint64_t* out, size_t n);
+/* out[i] = in[i]^-1 with ONE field inversion for the whole vector: the per-element y.inverse() of inv_vec / inv_many /
+ * inv_many_in_place[_leaking_zeros] (co-noir-common/src/mpc/rep3.rs:208-257, mpc-core rep3/arithmetic.rs:233-246, rep3/detail.rs:487,
+ * co-plonk/src/mpc/plain.rs:127-140). A zero stays zero (the rule of inv_many_in_place_leaking_zeros and of ark_ff::batch_inversion);
+ * the number of zeros is reported so that inv_vec's caller can bail as the reference does -- CSH_OK either way. out may equal in;
+ * zero_count(_dev) may be NULL. */
+int csh_vec_batch_inverse_dev(csh_curve_t field_of, const uint64_t* in_dev, uint64_t* out_dev, size_t n, uint64_t* zero_count_dev, void* stream);
+int csh_vec_batch_inverse(csh_curve_t field_of, const uint64_t* in, uint64_t* out, size_t n, size_t* zero_count);
+/* out[c] = sum_i coeffs[i*ncomp + c] * point^i, c < ncomp (1 = plain / Shamir, 2 = a Rep3 share {a, b}): evaluate_poly_public
+ * (co-plonk/src/round4.rs:126-132) and eval_poly (co-noir co_shplemini_prover.rs:382-444, 765; mpc-core rep3/poly.rs:39-68).
+ * n == 0 gives 0, point == 0 gives coeffs[0]. `point` is read on the host during the call. */
+int csh_eval_poly_dev(csh_curve_t field_of, const uint64_t* coeffs_dev, size_t n, uint32_t ncomp, const uint64_t point[4], uint64_t* out_dev, void* stream);
+int csh_eval_poly(csh_curve_t field_of, const uint64_t* coeffs, size_t n, uint32_t ncomp, const uint64_t point[4], uint64_t* out);
 
 /* Rep3 correlated masks generated on the device ("next" row f2): out[i] = from_be_bytes_mod_order(a_i) -
  * from_be_bytes_mod_order(b_i), a_i / b_i = the 32-byte chunks number elem_offset{1,2} + i of the ChaCha12 keystreams

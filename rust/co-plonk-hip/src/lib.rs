@@ -10,3 +10,5 @@
 mod cold;
 pub mod drivers;
 pub use drivers::{HipPlainPlonkDriver, HipRep3PlonkDriver, HipShamirPlonkDriver};
+pub mod scans;
+pub use scans::{hip_batch_inverse, hip_eval_poly, hip_prefix_product};
