@@ -18,6 +18,7 @@
 // sites). The result is a group element; it is bit-identical to the reference after affine normalisation.
 #include <algorithm>
 #include <condition_variable>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -54,6 +55,43 @@ CSH_MSM_ACCUM_PAIR_INSTANTIATE(extern, Bls381G2Cfg)
 CSH_MSM_ACCUM_PAIR_INSTANTIATE(extern, Bls377G2Cfg)
 
 static int repack_bases(Bases* B, hipStream_t st);
+
+template <class Cfg>
+static GroupOps group_ops_of(csh_curve_t curve, csh_group_t group) {
+  using Fq = typename Cfg::Fq;
+  return GroupOps{curve, group, Cfg::Fr::Params::BITS, sizeof(Affine<Fq>), sizeof(XYZZ<Fq>), msm_sort_stage<typename Cfg::Fr>,
+                  msm_bucket_bytes<Cfg>, msm_bucket_stage<Cfg>, fold_windows_erased<Cfg>, accum_occupancy<Cfg>};
+}
+const GroupOps* group_ops(csh_curve_t curve, csh_group_t group) {
+  static const GroupOps table[] = {
+      group_ops_of<Bn254G1Cfg>(CSH_BN254, CSH_G1),       group_ops_of<Bn254G2Cfg>(CSH_BN254, CSH_G2),       group_ops_of<Bls381G1Cfg>(CSH_BLS12_381, CSH_G1),
+      group_ops_of<Bls381G2Cfg>(CSH_BLS12_381, CSH_G2),  group_ops_of<GrumpkinG1Cfg>(CSH_GRUMPKIN, CSH_G1), group_ops_of<Bls377G1Cfg>(CSH_BLS12_377, CSH_G1),
+      group_ops_of<Bls377G2Cfg>(CSH_BLS12_377, CSH_G2)};
+  for (const GroupOps& o : table)
+    if (o.curve == curve && o.group == group) return &o;
+  set_error("unknown curve/group %d/%d", (int)curve, (int)group);
+  return nullptr;
+}
+
+// A handle from the moment it is created until it is handed out (or freed: csh_bases_free)
+struct BasesFree {
+  void operator()(Bases* B) const {
+    if (B->points) (void)hipFree(B->points);
+    if (B->table) (void)hipFree(B->table);
+    delete B;
+  }
+};
+using BasesPtr = std::unique_ptr<Bases, BasesFree>;
+
+// handles are per device: the calling thread must be bound to the one the bases live on
+static int on_callers_device(const Bases* B) {
+  int cur = -1;
+  if (hipGetDevice(&cur) == hipSuccess && cur != B->device) {
+    set_error("bases were uploaded on device %d but the calling thread is bound to device %d (csh_init): upload a copy per device", B->device, cur);
+    return CSH_ERR_INVALID;
+  }
+  return CSH_OK;
+}
 
 }  // namespace csh
 
@@ -96,7 +134,12 @@ struct SharedUpload {
 };
 std::mutex g_up_mu;
 std::vector<SharedUpload*> g_up_live;                       // entries with refs > 0
-std::vector<std::pair<int, std::pair<size_t, void*>>> g_up_pool;  // (device, (capacity, buffer)) free device buffers
+struct PooledBuffer {
+  int device;
+  size_t cap;
+  void* dev;
+};
+std::vector<PooledBuffer> g_up_pool;  // free device buffers
 constexpr size_t UP_POOL_MAX = 8;
 constexpr size_t UP_POOL_MAX_BYTES = size_t(1) << 30;  // the free buffers together (a 2^24 scalar vector is 512 MB): beyond it a buffer is freed
 
@@ -131,10 +174,10 @@ struct SharedUploadRef {
         e->curve = curve, e->mont = mont;
         size_t best = (size_t)-1;
         for (size_t i = 0; i < g_up_pool.size(); ++i)
-          if (g_up_pool[i].first == device && g_up_pool[i].second.first >= bytes && (best == (size_t)-1 || g_up_pool[i].second.first < g_up_pool[best].second.first)) best = i;
+          if (g_up_pool[i].device == device && g_up_pool[i].cap >= bytes && (best == (size_t)-1 || g_up_pool[i].cap < g_up_pool[best].cap)) best = i;
         if (best != (size_t)-1) {
-          e->cap = g_up_pool[best].second.first;
-          e->dev = g_up_pool[best].second.second;
+          e->cap = g_up_pool[best].cap;
+          e->dev = g_up_pool[best].dev;
           g_up_pool.erase(g_up_pool.begin() + (ptrdiff_t)best);
         }
         g_up_live.push_back(e);
@@ -227,9 +270,9 @@ struct SharedUploadRef {
         g_up_live.erase(std::find(g_up_live.begin(), g_up_live.end(), e));
         dead = e;
         size_t pooled = 0;
-        for (auto& b : g_up_pool) pooled += b.second.first;
+        for (const PooledBuffer& b : g_up_pool) pooled += b.cap;
         if (dead->dev && g_up_pool.size() < UP_POOL_MAX && pooled + dead->cap <= UP_POOL_MAX_BYTES) {
-          g_up_pool.push_back({dead->device, {dead->cap, dead->dev}});
+          g_up_pool.push_back({dead->device, dead->cap, dead->dev});
           dead->dev = nullptr;
         }
       }
@@ -247,25 +290,20 @@ static int csh::repack_bases(Bases* B, hipStream_t st) {
   CURVE_DISPATCH(B->curve, B->group, (repack_bases_t<Cfg>(B, st)));
 }
 
-static int valid_cg(csh_curve_t c, csh_group_t g) {
-  CSH_REQUIRE(c == CSH_BN254 || c == CSH_BLS12_381 || c == CSH_GRUMPKIN || c == CSH_BLS12_377, "unknown curve");
-  CSH_REQUIRE(g == CSH_G1 || (g == CSH_G2 && c != CSH_GRUMPKIN), "unknown group");
-  return CSH_OK;
-}
-
 extern "C" {
 
 static int bases_upload_common(csh_curve_t curve, csh_group_t group, const void* pts, size_t n, size_t stride, bool src_dev, void* stream,
                                csh_bases_t* out) {
   CSH_REQUIRE(out, "out is NULL");
-  CSH_TRY(valid_cg(curve, group));
+  const GroupOps* G = group_ops(curve, group);
+  if (!G) return CSH_ERR_INVALID;
   CSH_REQUIRE(n < (size_t(1) << 31), "at most 2^31-1 bases per handle");
   CSH_REQUIRE(pts || n == 0, "points is NULL");
   CSH_TRY(ensure_device());
-  const size_t pb = point_bytes_of(curve, group);
+  const size_t pb = G->point_bytes;
   if (stride == 0) stride = pb;
   CSH_REQUIRE(stride >= pb, "stride_bytes smaller than a packed affine point");
-  Bases* B = new Bases();
+  BasesPtr B(new Bases());
   B->curve = curve;
   B->group = group;
   B->n = n;
@@ -274,7 +312,7 @@ static int bases_upload_common(csh_curve_t curve, csh_group_t group, const void*
   if (hipGetDevice(&B->device) != hipSuccess) B->device = 0;
   hipError_t e = hipMalloc(&B->points, n ? n * pb : 1);
   if (e != hipSuccess) {
-    delete B;
+    B->points = nullptr;
     set_error("hipMalloc(%zu bytes) for bases failed: %s", n * pb, hipGetErrorString(e));
     return CSH_ERR_OOM;
   }
@@ -288,19 +326,12 @@ static int bases_upload_common(csh_curve_t curve, csh_group_t group, const void*
     }
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) {
-      (void)hipFree(B->points);
-      delete B;
       set_error("bases upload failed: %s", hipGetErrorString(e));
       return CSH_ERR_HIP;
     }
-    int rc = repack_bases(B, st);
-    if (rc != CSH_OK) {
-      (void)hipFree(B->points);
-      delete B;
-      return rc;
-    }
+    CSH_TRY(repack_bases(B.get(), st));
   }
-  *out = reinterpret_cast<csh_bases_t>(B);
+  *out = reinterpret_cast<csh_bases_t>(B.release());
   return CSH_OK;
 }
 
@@ -326,11 +357,11 @@ int csh_bases_clone_range(csh_bases_t src, size_t offset, size_t n, int device, 
   CSH_HIP(hipGetDeviceCount(&ndev));
   CSH_REQUIRE(device >= 0 && device < ndev, "device out of range");
   CSH_HIP(hipGetDevice(&cur));
-  Bases* B = new Bases(*S);
+  BasesPtr B(new Bases(*S));
+  B->points = nullptr;  // the copy owns nothing of the source
+  B->table = nullptr;
   B->device = device;
   B->n = n;
-  B->points = nullptr;
-  B->table = nullptr;
   const size_t pb = S->point_bytes, pbytes = n * pb, rows = S->table ? (size_t)S->table_W : 0;
   if (!rows) B->table_c = B->table_W = 0;
   hipError_t e = hipSetDevice(device);
@@ -346,14 +377,10 @@ int csh_bases_clone_range(csh_bases_t src, size_t offset, size_t n, int device, 
   }
   (void)hipSetDevice(cur);
   if (e != hipSuccess) {
-    const bool oom = e == hipErrorOutOfMemory;
-    if (B->points) (void)hipFree(B->points);
-    if (B->table) (void)hipFree(B->table);
-    delete B;
     set_error("csh_bases_clone_range to device %d failed: %s", device, hipGetErrorString(e));
-    return oom ? CSH_ERR_OOM : CSH_ERR_HIP;
+    return e == hipErrorOutOfMemory ? CSH_ERR_OOM : CSH_ERR_HIP;
   }
-  *out = reinterpret_cast<csh_bases_t>(B);
+  *out = reinterpret_cast<csh_bases_t>(B.release());
   return CSH_OK;
 }
 int csh_bases_clone(csh_bases_t src, int device, csh_bases_t* out) {
@@ -361,11 +388,7 @@ int csh_bases_clone(csh_bases_t src, int device, csh_bases_t* out) {
   return csh_bases_clone_range(src, 0, reinterpret_cast<const Bases*>(src)->n, device, out);
 }
 int csh_bases_free(csh_bases_t bases) {
-  if (!bases) return CSH_OK;
-  Bases* B = reinterpret_cast<Bases*>(bases);
-  if (B->points) (void)hipFree(B->points);
-  if (B->table) (void)hipFree(B->table);
-  delete B;
+  const BasesPtr freed(reinterpret_cast<Bases*>(bases));  // NULL: nothing to do
   return CSH_OK;
 }
 
@@ -428,13 +451,7 @@ static int bases_precompute(csh_bases_t bases, int c, int groups) {
     c = 16;
     while (c > 10 && (size_t(1) << (c + 1)) > B->n) --c;  // ~2 points per bucket and window at least
   }
-  {
-    int cur = -1;
-    if (hipGetDevice(&cur) == hipSuccess && cur != B->device) {
-      set_error("bases were uploaded on device %d but the calling thread is bound to device %d (csh_init)", B->device, cur);
-      return CSH_ERR_INVALID;
-    }
-  }
+  CSH_TRY(on_callers_device(B));
   hipStream_t st = resolve_stream(nullptr);
   CURVE_DISPATCH(B->curve, B->group, (precompute_table_t<Cfg>(B, c, groups, st)));
 }
@@ -445,12 +462,7 @@ static int msm_args(csh_bases_t bases, size_t offset, size_t n, const void* scal
   Bases* B = reinterpret_cast<Bases*>(bases);
   CSH_REQUIRE(offset <= B->n && n <= B->n - offset, "offset + n exceeds the uploaded bases");
   CSH_REQUIRE(scalars || n == 0, "scalars is NULL");
-  int cur = -1;
-  if (hipGetDevice(&cur) == hipSuccess && cur != B->device) {
-    set_error("bases were uploaded on device %d but the calling thread is bound to device %d (csh_init): upload a copy per device", B->device, cur);
-    return CSH_ERR_INVALID;
-  }
-  return CSH_OK;
+  return on_callers_device(B);
 }
 
 int csh_msm_dev(csh_bases_t bases, size_t offset, size_t n, const uint64_t* scalars_dev, int mont, void* out_host, void* stream) {
@@ -459,6 +471,32 @@ int csh_msm_dev(csh_bases_t bases, size_t offset, size_t n, const uint64_t* scal
   Bases* B = reinterpret_cast<Bases*>(bases);
   hipStream_t st = resolve_stream(stream);
   CURVE_DISPATCH(B->curve, B->group, (msm_t<Cfg>(B, offset, n, scalars_dev, mont, out_host, st)));
+}
+
+// The owner of a shared upload, after its copy is queued: closes the batch and runs its own request together with the joiners' as ONE
+// csh_msm_multi_dev (alone: the ordinary csh_msm_dev); the joiners get the call's result code and error text.
+static int run_owned_batch(SharedUploadRef& up, SharedUpload::Req& own, size_t n, const uint64_t* dsc, int mont, hipStream_t st) {
+  const std::vector<SharedUpload::Req*> others = up.seal();
+  if (others.empty()) {
+    up.finish_batch();
+    return csh_msm_dev(own.bases, own.offset, n, dsc, mont, own.out, st);
+  }
+  // G2 handles first: their host fold (Horner over Fp2 windows) then runs under the G1 bucket stages that follow (as the mirror's prover orders them)
+  std::vector<SharedUpload::Req*> all;
+  all.push_back(&own);
+  for (SharedUpload::Req* r : others) all.push_back(r);
+  std::stable_sort(all.begin(), all.end(), [](const SharedUpload::Req* a, const SharedUpload::Req* b) {
+    return reinterpret_cast<const Bases*>(a->bases)->group > reinterpret_cast<const Bases*>(b->bases)->group;
+  });
+  std::vector<csh_bases_t> hs;
+  std::vector<size_t> offs;
+  std::vector<void*> outs;
+  for (SharedUpload::Req* r : all) hs.push_back(r->bases), offs.push_back(r->offset), outs.push_back(r->out);
+  const int rc = csh_msm_multi_dev(hs.data(), offs.data(), all.size(), n, dsc, mont, outs.data(), st);
+  const std::string err = rc == CSH_OK ? std::string() : std::string(csh_last_error());
+  for (SharedUpload::Req* r : others) r->rc = rc, r->err = err;
+  up.finish_batch();
+  return rc;
 }
 
 int csh_msm(csh_bases_t bases, size_t offset, size_t n, const uint64_t* scalars, int mont, void* out) {
@@ -484,27 +522,7 @@ int csh_msm(csh_bases_t bases, size_t offset, size_t n, const uint64_t* scalars,
     }
     const uint64_t* dsc = reinterpret_cast<const uint64_t*>(up.dev());
     if (!up.is_owner || !batching) return csh_msm_dev(bases, offset, n, dsc, mont, out, st);
-    const std::vector<SharedUpload::Req*> others = up.seal();
-    if (others.empty()) {
-      up.finish_batch();
-      return csh_msm_dev(bases, offset, n, dsc, mont, out, st);
-    }
-    // G2 handles first: their host fold (Horner over Fp2 windows) then runs under the G1 bucket stages that follow (as the mirror's prover orders them)
-    std::vector<SharedUpload::Req*> all;
-    all.push_back(&req);
-    for (SharedUpload::Req* r : others) all.push_back(r);
-    std::stable_sort(all.begin(), all.end(), [](const SharedUpload::Req* a, const SharedUpload::Req* b) {
-      return reinterpret_cast<const Bases*>(a->bases)->group > reinterpret_cast<const Bases*>(b->bases)->group;
-    });
-    std::vector<csh_bases_t> hs;
-    std::vector<size_t> offs;
-    std::vector<void*> outs;
-    for (SharedUpload::Req* r : all) hs.push_back(r->bases), offs.push_back(r->offset), outs.push_back(r->out);
-    const int rc = csh_msm_multi_dev(hs.data(), offs.data(), all.size(), n, dsc, mont, outs.data(), st);
-    const std::string err = rc == CSH_OK ? std::string() : std::string(csh_last_error());
-    for (SharedUpload::Req* r : others) r->rc = rc, r->err = err;
-    up.finish_batch();
-    return rc;
+    return run_owned_batch(up, req, n, dsc, mont, st);
   }
   HostStage h;
   CSH_TRY(h.begin(Arena::padded(bytes)));
@@ -534,7 +552,7 @@ int csh_msm_shares(csh_bases_t bases, size_t offset, size_t n, const uint64_t* s
 
 int csh_msm_partial_bytes(csh_curve_t curve, csh_group_t group, size_t* bytes) {
   CSH_REQUIRE(bytes, "bytes is NULL");
-  CSH_TRY(valid_cg(curve, group));
+  if (!group_ops(curve, group)) return CSH_ERR_INVALID;
   *bytes = partial_bytes_of(curve, group);
   return CSH_OK;
 }
@@ -561,133 +579,78 @@ int csh_msm_multi_dev(const csh_bases_t* bases, const size_t* offsets, size_t k,
   CSH_REQUIRE(scalars_dev || n == 0, "scalars is NULL");
   CSH_REQUIRE(n < (size_t(1) << 31), "n too large");
   CSH_TRY(ensure_device());
-  const Bases* B0 = reinterpret_cast<const Bases*>(bases[0]);
+  const auto handle = [&](size_t i) { return reinterpret_cast<const Bases*>(bases[i]); };
+  const Bases* B0 = handle(0);
   CSH_REQUIRE(B0, "bases[0] is NULL");
   for (size_t i = 0; i < k; ++i) {
-    const Bases* B = reinterpret_cast<const Bases*>(bases[i]);
+    const Bases* B = handle(i);
     CSH_REQUIRE(B && outs_host[i], "msm_multi: NULL handle or output");
     CSH_REQUIRE(B->curve == B0->curve, "msm_multi: all bases must belong to one curve");
     CSH_REQUIRE(offsets[i] <= B->n && n <= B->n - offsets[i], "msm_multi: offset + n exceeds the number of bases");
     CSH_REQUIRE(B->device == B0->device, "msm_multi: bases live on different devices");
   }
-  {
-    int cur = -1;
-    if (hipGetDevice(&cur) == hipSuccess && cur != B0->device) {
-      set_error("bases were uploaded on device %d but the calling thread is bound to device %d (csh_init)", B0->device, cur);
-      return CSH_ERR_INVALID;
-    }
-  }
+  CSH_TRY(on_callers_device(B0));
   hipStream_t st = resolve_stream(stream);
-  struct Ops {
-    size_t (*bytes)(const MsmParams*);
-    int (*bucket)(const void*, const MsmParams*, const SortOut*, hipStream_t, Arena*, void*, hipEvent_t*);
-    void (*fold)(const void*, int, int, int, void*);
-    size_t xyzz_bytes;
-    int (*occ)();  // accumulate waves of the group's kernel that fit one SIMD
-  };
-  auto ops_of = [](const Bases* B, Ops* o) -> bool {
-#define CSH_OPS(CFG) *o = Ops{msm_bucket_bytes<CFG>, msm_bucket_stage<CFG>, fold_windows_erased<CFG>, sizeof(XYZZ<CFG::Fq>), accum_occupancy<CFG>}; return true
-    if (B->curve == CSH_BN254 && B->group == CSH_G1) { CSH_OPS(Bn254G1Cfg); }
-    if (B->curve == CSH_BN254 && B->group == CSH_G2) { CSH_OPS(Bn254G2Cfg); }
-    if (B->curve == CSH_BLS12_381 && B->group == CSH_G1) { CSH_OPS(Bls381G1Cfg); }
-    if (B->curve == CSH_BLS12_381 && B->group == CSH_G2) { CSH_OPS(Bls381G2Cfg); }
-    if (B->curve == CSH_GRUMPKIN && B->group == CSH_G1) { CSH_OPS(GrumpkinG1Cfg); }
-    if (B->curve == CSH_BLS12_377 && B->group == CSH_G1) { CSH_OPS(Bls377G1Cfg); }
-    if (B->curve == CSH_BLS12_377 && B->group == CSH_G2) { CSH_OPS(Bls377G2Cfg); }
-#undef CSH_OPS
-    return false;
-  };
-  std::vector<Ops> ops(k);
-  for (size_t i = 0; i < k; ++i) CSH_REQUIRE(ops_of(reinterpret_cast<const Bases*>(bases[i]), &ops[i]), "msm_multi: unknown curve/group");
+  std::vector<const GroupOps*> ops(k);
+  for (size_t i = 0; i < k; ++i)
+    if (!(ops[i] = group_ops(handle(i)->curve, handle(i)->group))) return CSH_ERR_INVALID;
   if (n == 0) {
-    for (size_t i = 0; i < k; ++i) ops[i].fold(nullptr, 0, 2, 0, outs_host[i]);
+    for (size_t i = 0; i < k; ++i) ops[i]->fold(nullptr, 0, 2, 0, outs_host[i]);
     return CSH_OK;
   }
-  const int bits = scalar_bits_of(B0->curve);
   // merged-window mode needs every handle to carry tables of one window width (the digit codes are shared)
   bool merged = true;
-  for (size_t i = 0; i < k; ++i) {
-    const Bases* B = reinterpret_cast<const Bases*>(bases[i]);
-    merged = merged && msm_use_table(B, n) && B->table_c == B0->table_c && B->table_W == B0->table_W;
-  }
+  for (size_t i = 0; i < k; ++i) merged = merged && msm_use_table(handle(i), n) && handle(i)->table_c == B0->table_c && handle(i)->table_W == B0->table_W;
   int occ = 8;  // the shared plan's lane length suits the group with the fewest co-resident accumulate waves (a G2 handle: 1)
-  for (auto& o : ops) occ = std::min(occ, o.occ());
-  const MsmParams pdig = merged ? msm_plan_merged(n, bits, mont, B0->table_c, B0->table_W, B0->n, 0, occ).dig : msm_plan(n, bits, mont, occ);
-  MsmParams p = merged ? msm_plan_merged(n, bits, mont, B0->table_c, B0->table_W, B0->n, 0, occ).srt : pdig;
-  size_t bucket_max = 0, win_bytes = 0;
-  for (auto& o : ops) {
-    bucket_max = std::max(bucket_max, o.bytes(&p));
-    win_bytes += Arena::padded(o.xyzz_bytes * MAX_WINDOWS);
+  for (const GroupOps* o : ops) occ = std::min(occ, o->occ());
+  const MsmTable table{B0->table_c, B0->table_W, B0->n, 0};
+  MsmPlan plan = msm_plan(n, ops[0]->scalar_bits, mont, occ, merged ? &table : nullptr);
+  msm_record_params(plan.srt);
+  const MsmParams& pdig = plan.dig;
+  MsmParams& p = plan.srt;  // merged: remap_stride / remap_off follow the handle the list is sorted for
+  size_t bucket_max = 0, win_bytes = 0, slice = 0;
+  for (const GroupOps* o : ops) {
+    bucket_max = std::max(bucket_max, o->bucket_bytes(&p));
+    win_bytes += Arena::padded(o->xyzz_bytes * MAX_WINDOWS);
+    slice = std::max(slice, Arena::padded(o->xyzz_bytes * MAX_WINDOWS));
   }
   Arena& ar = arena_for(st);
-  // merged mode: the remap (table stride, offset) differs per handle, so the scatter runs per handle on shared digit
-  // codes; otherwise one sort serves all
   // two bucket-stage scratch regions: consecutive bucket stages alternate between the caller's stream and a second one, so
-  // the latency-bound bucket reduction of MSM i overlaps the throughput-bound accumulation of MSM i + 1
+  // the latency-bound bucket reduction of MSM i overlaps the throughput-bound accumulation of MSM i + 1 (with ONE bucket set per MSM,
+  // merged mode, the reduction is 0.2-0.4 ms of a 1.4 ms G1 MSM)
   CSH_TRY(ar.reserve(msm_sort_bytes(p, pdig) + 2 * Arena::padded(bucket_max)));
   Arena& wa = arena_for((hipStream_t)((uintptr_t)st ^ 0x2));
   CSH_TRY(wa.reserve(win_bytes));
-  auto sort_stage = [&](const MsmParams& ps, SortOut* so) -> int {
-    if (B0->curve == CSH_BLS12_381) return msm_sort_stage<Bls381Fr>(ps, pdig, scalars_dev, st, ar, so, nullptr);
-    if (B0->curve == CSH_GRUMPKIN) return msm_sort_stage<Bn254Fq>(ps, pdig, scalars_dev, st, ar, so, nullptr);
-    if (B0->curve == CSH_BLS12_377) return msm_sort_stage<Bls377Fr>(ps, pdig, scalars_dev, st, ar, so, nullptr);
-    return msm_sort_stage<Bn254Fr>(ps, pdig, scalars_dev, st, ar, so, nullptr);
-  };
-  SortOut so;
-  std::vector<char*> win_dev(k);
   hipStream_t aux = nullptr;
-  std::vector<hipStream_t> stage_stream(k, st);
-  if (!merged) {
-    const bool overlap = tune().msm_multi_overlap.load(std::memory_order_relaxed) != 0;
-    if (overlap && k > 1) aux = resolve_aux_stream();  // pooled with the thread's lane: no stream creation per call
-    const bool two = overlap && k > 1 && aux != nullptr;
-    CSH_TRY(sort_stage(p, &so));
-    const size_t mark = ar.off;
-    hipEvent_t sorted_ev = nullptr;
-    if (two) {
-      CSH_HIP(hipEventCreateWithFlags(&sorted_ev, hipEventDisableTiming));
-      CSH_HIP(hipEventRecord(sorted_ev, st));
-      CSH_HIP(hipStreamWaitEvent(aux, sorted_ev, 0));
-    }
-    for (size_t i = 0; i < k; ++i) {
-      const bool on_aux = two && (i & 1);
-      stage_stream[i] = on_aux ? aux : st;
-      ar.off = mark + (on_aux ? Arena::padded(bucket_max) : 0);  // per-stream scratch region: stages on one stream are ordered
-      const Bases* B = reinterpret_cast<const Bases*>(bases[i]);
-      win_dev[i] = wa.take<char>(ops[i].xyzz_bytes * MAX_WINDOWS);
-      CSH_TRY(ops[i].bucket(static_cast<const char*>(B->points) + offsets[i] * B->point_bytes, &p, &so, stage_stream[i], &ar, win_dev[i], nullptr));
-    }
-    if (sorted_ev) (void)hipEventDestroy(sorted_ev);
-  } else {
-    // Handles that share (table stride, offset) share the sorted index list; a different pair needs its own scatter. Round 6: the bucket
-    // stages alternate between the caller's stream and the lane's second stream here too (each with its own scratch region), so the
-    // latency-bound bucket reduction of MSM i runs under the accumulation of MSM i + 1 -- with ONE bucket set per MSM the reduction is
-    // 0.2-0.4 ms of a 1.4 ms G1 MSM. A re-sort waits for the other stream's readers of the previous list.
-    const bool overlap = tune().msm_multi_overlap.load(std::memory_order_relaxed) != 0;
-    if (overlap && k > 1) aux = resolve_aux_stream();
-    const bool two = overlap && k > 1 && aux != nullptr;
-    size_t last_stride = (size_t)-1, last_off = (size_t)-1;
-    size_t mark = 0;
-    hipEvent_t sorted_ev = nullptr, aux_done = nullptr;
-    if (two) {
-      CSH_HIP(hipEventCreateWithFlags(&sorted_ev, hipEventDisableTiming));
-      CSH_HIP(hipEventCreateWithFlags(&aux_done, hipEventDisableTiming));
-    }
+  if (tune().msm_multi_overlap.load(std::memory_order_relaxed) != 0 && k > 1) aux = resolve_aux_stream();  // pooled with the thread's lane: no stream creation per call
+  const bool two = aux != nullptr;
+  // every event of the call: [i] the window sums of result i have arrived; with two streams [k] "sorted" and [k + 1] "aux done"
+  Events evs;
+  CSH_TRY(evs.create(k + (two ? 2 : 0), hipEventDisableTiming));
+  const hipEvent_t sorted_ev = two ? evs[k] : nullptr, aux_done = two ? evs[k + 1] : nullptr;
+  auto body = [&]() -> int {
+    SortOut so;
+    std::vector<char*> win_dev(k);
+    std::vector<hipStream_t> stage_stream(k, st);
+    size_t mark = 0, sorted_stride = (size_t)-1, sorted_off = (size_t)-1;
     bool aux_used = false;
     for (size_t i = 0; i < k; ++i) {
-      const Bases* B = reinterpret_cast<const Bases*>(bases[i]);
-      if (B->n != last_stride || offsets[i] != last_off) {
+      const Bases* B = handle(i);
+      // Plain: one sort serves all handles. Merged: the remap (table stride, offset) is part of the scatter, so handles that share the
+      // pair share the sorted index list (on shared digit codes); a different pair needs its own scatter.
+      const bool resort = merged ? (B->n != sorted_stride || offsets[i] != sorted_off) : i == 0;
+      if (resort) {
         if (two && aux_used) {  // bucket stages on the second stream still read the list this sort overwrites
           CSH_HIP(hipEventRecord(aux_done, aux));
           CSH_HIP(hipStreamWaitEvent(st, aux_done, 0));
         }
         ar.off = 0;
-        p.remap_stride = (uint32_t)B->n;
-        p.remap_off = (uint32_t)offsets[i];
-        CSH_TRY(sort_stage(p, &so));
+        if (merged) {
+          p.remap_stride = (uint32_t)(sorted_stride = B->n);
+          p.remap_off = (uint32_t)(sorted_off = offsets[i]);
+        }
+        CSH_TRY(ops[0]->sort(p, pdig, scalars_dev, st, ar, &so, nullptr));
         mark = ar.off;
-        last_stride = B->n;
-        last_off = offsets[i];
         if (two) {
           CSH_HIP(hipEventRecord(sorted_ev, st));
           CSH_HIP(hipStreamWaitEvent(aux, sorted_ev, 0));
@@ -696,68 +659,57 @@ int csh_msm_multi_dev(const csh_bases_t* bases, const size_t* offsets, size_t k,
       const bool on_aux = two && (i & 1);
       stage_stream[i] = on_aux ? aux : st;
       aux_used = aux_used || on_aux;
-      ar.off = mark + (on_aux ? Arena::padded(bucket_max) : 0);
-      win_dev[i] = wa.take<char>(ops[i].xyzz_bytes * MAX_WINDOWS);
-      CSH_TRY(ops[i].bucket(B->table, &p, &so, stage_stream[i], &ar, win_dev[i], nullptr));
+      ar.off = mark + (on_aux ? Arena::padded(bucket_max) : 0);  // per-stream scratch region: stages on one stream are ordered
+      win_dev[i] = wa.take<char>(ops[i]->xyzz_bytes * MAX_WINDOWS);
+      const void* src = merged ? B->table : static_cast<const char*>(B->points) + offsets[i] * B->point_bytes;
+      CSH_TRY(ops[i]->bucket(src, &p, &so, stage_stream[i], &ar, win_dev[i], nullptr));
     }
-    if (sorted_ev) (void)hipEventDestroy(sorted_ev);
-    if (aux_done) (void)hipEventDestroy(aux_done);
-  }
-  // window sums of all k results through one page-locked buffer of the lane (DMA copies, no staging), pageable fallback
-  size_t slice = 0;
-  for (size_t i = 0; i < k; ++i) slice = std::max(slice, Arena::padded(ops[i].xyzz_bytes * MAX_WINDOWS));
-  void *pin_host = nullptr, *pin_dev = nullptr;
-  std::vector<char> pageable;
-  char* wins = nullptr;
-  if (pinned_for((hipStream_t)((uintptr_t)st ^ 0x4), slice * k, &pin_host, &pin_dev)) {
-    wins = static_cast<char*>(pin_host);
-  } else {
-    pageable.resize(slice * k);
-    wins = pageable.data();
-  }
-  // each result is folded on the host (Horner over its windows: ~80 us on G1, ~250 us on G2) as soon as ITS window sums have
-  // arrived, while the device is still busy with the later bucket stages
-  std::vector<hipEvent_t> arrived(k, nullptr);
-  auto drop_events = [&] {
-    for (hipEvent_t e : arrived)
-      if (e) (void)hipEventDestroy(e);
+    // window sums of all k results through one page-locked buffer of the lane (DMA copies, no staging), pageable fallback
+    void *pin_host = nullptr, *pin_dev = nullptr;
+    std::vector<char> pageable;
+    char* wins = nullptr;
+    if (pinned_for((hipStream_t)((uintptr_t)st ^ 0x4), slice * k, &pin_host, &pin_dev)) {
+      wins = static_cast<char*>(pin_host);
+    } else {
+      pageable.resize(slice * k);
+      wins = pageable.data();
+    }
+    // each result is folded on the host (Horner over its windows: ~80 us on G1, ~250 us on G2) as soon as ITS window sums have
+    // arrived, while the device is still busy with the later bucket stages
+    for (size_t i = 0; i < k; ++i) {
+      hipError_t e = hipMemcpyAsync(wins + slice * i, win_dev[i], ops[i]->xyzz_bytes * p.W, hipMemcpyDeviceToHost, stage_stream[i]);
+      if (e == hipSuccess) e = hipEventRecord(evs[i], stage_stream[i]);
+      if (e != hipSuccess) {
+        set_error("msm_multi: queuing the window sums of result %zu failed: %s", i, hipGetErrorString(e));
+        return CSH_ERR_HIP;
+      }
+    }
+    for (size_t i = 0; i < k; ++i) {
+      const hipError_t e = hipEventSynchronize(evs[i]);
+      if (e != hipSuccess) {
+        set_error("msm_multi: result %zu failed on the device: %s", i, hipGetErrorString(e));
+        return CSH_ERR_HIP;
+      }
+      ops[i]->fold(wins + slice * i, p.W, p.c, p.wide, outs_host[i]);
+    }
+    CSH_HIP(hipStreamSynchronize(st));
+    if (aux) CSH_HIP(hipStreamSynchronize(aux));
+    return CSH_OK;
   };
-  for (size_t i = 0; i < k; ++i) {
-    hipError_t e = hipMemcpyAsync(wins + slice * i, win_dev[i], ops[i].xyzz_bytes * p.W, hipMemcpyDeviceToHost, stage_stream[i]);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&arrived[i], hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventRecord(arrived[i], stage_stream[i]);
-    if (e != hipSuccess) {
-      drop_events();
-      set_error("msm_multi: queuing the window sums of result %zu failed: %s", i, hipGetErrorString(e));
-      return CSH_ERR_HIP;
-    }
+  const int rc = body();
+  if (rc != CSH_OK) {  // nothing queued by a failed call may still read the arenas (or the caller's scalars) once it has returned
+    (void)hipStreamSynchronize(st);
+    if (aux) (void)hipStreamSynchronize(aux);
   }
-  for (size_t i = 0; i < k; ++i) {
-    const hipError_t e = hipEventSynchronize(arrived[i]);
-    if (e != hipSuccess) {
-      (void)hipStreamSynchronize(st);
-      if (aux) (void)hipStreamSynchronize(aux);
-      drop_events();
-      set_error("msm_multi: result %zu failed on the device: %s", i, hipGetErrorString(e));
-      return CSH_ERR_HIP;
-    }
-    ops[i].fold(wins + slice * i, p.W, p.c, p.wide, outs_host[i]);
-  }
-  drop_events();
-  CSH_HIP(hipStreamSynchronize(st));
-  if (aux) CSH_HIP(hipStreamSynchronize(aux));
-  return CSH_OK;
+  return rc;
 }
 
 int csh_msm_plan(csh_curve_t curve, size_t n, uint32_t out[6]) {
   CSH_REQUIRE(out, "out is NULL");
-  CSH_REQUIRE(curve == CSH_BN254 || curve == CSH_BLS12_381 || curve == CSH_GRUMPKIN || curve == CSH_BLS12_377, "unknown curve");
+  const GroupOps* G = group_ops(curve, CSH_G1);
+  if (!G) return CSH_ERR_INVALID;
   CSH_REQUIRE(n >= 1 && n < (size_t(1) << 31), "n out of range");
-  const int bits = scalar_bits_of(curve);
-  uint32_t keep[4];
-  for (int i = 0; i < 4; ++i) keep[i] = tl_msm_params[i];  // planning must not disturb csh_msm_last_params
-  const MsmParams p = msm_plan(n, bits, 1);
-  for (int i = 0; i < 4; ++i) tl_msm_params[i] = keep[i];
+  const MsmParams p = msm_plan(n, G->scalar_bits, 1, 1).srt;
   const uint64_t lanes = (n + p.L - 1) / p.L;
   out[0] = (uint32_t)p.c;
   out[1] = (uint32_t)p.W;

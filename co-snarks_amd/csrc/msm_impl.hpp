@@ -1,11 +1,13 @@
 // Templates of the Pippenger MSM (kernels + host drivers), instantiated once per group configuration in its own
-// translation unit (msm_inst_*.hip) so the five configurations compile in parallel; msm.hip holds the C ABI and dispatch.
+// translation unit (msm_inst_*.hip) so the configurations compile in parallel; msm.hip holds the C ABI, the table of the groups
+// (group_ops) and the multi-handle schedule; the planner is msm_plan.hpp.
 #pragma once
 #include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
 #include <type_traits>
+#include <vector>
 
 #include "common.hpp"
 #include "curve.hpp"
@@ -14,6 +16,7 @@
 #include "curve_pair.hpp"
 #include "host_fp64.hpp"
 #include "msm_digits.hpp"
+#include "msm_plan.hpp"
 #include "msm_sort.hpp"
 #include "msm_sort_wide.hpp"
 
@@ -51,10 +54,6 @@ struct Bases {
 // MsmParams, the digit-code constants and the sort stage live in msm_sort.hpp / msm_sort.hip
 
 constexpr int MSM_BLK = 256;
-#ifndef CSH_ACC_BLK
-#define CSH_ACC_BLK 128
-#endif
-constexpr int ACC_BLK = CSH_ACC_BLK;
 
 // canonical little-endian limbs of scalar i
 template <class Fr>
@@ -632,125 +631,34 @@ __global__ void k_msm_gather_windows(const LazyPt<Cfg>* segres, uint32_t stride,
 // ---- host side -----------------------------------------------------------------------------------------
 extern thread_local float tl_msm_timing[6];    // defined in msm.hip
 extern thread_local uint32_t tl_msm_params[4];  // c, W, L, S of the last MSM
+// called by the code that runs an MSM, with the plan of its sort and bucket stages (the planner itself writes nothing)
+inline void msm_record_params(const MsmParams& srt) {
+  tl_msm_params[0] = (uint32_t)srt.c;
+  tl_msm_params[1] = (uint32_t)srt.W;
+  tl_msm_params[2] = srt.L;
+  tl_msm_params[3] = srt.S;
+}
 
-
-inline int choose_c(size_t n, int bits) {
-  {
-    const int c = tune().msm_c.load(std::memory_order_relaxed);
-    if (c >= 2 && c <= 16) return c;
+// HIP events owned by a scope: destroyed on every way out of it
+struct Events {
+  std::vector<hipEvent_t> ev;
+  Events() = default;
+  Events(const Events&) = delete;
+  Events& operator=(const Events&) = delete;
+  ~Events() {
+    for (hipEvent_t e : ev) (void)hipEventDestroy(e);
   }
-  double best = 1e300;
-  int best_c = 4;
-  for (int c = 3; c <= 16; ++c) {  // digit codes are 15 bits + sign
-    const double nb = double(size_t(1) << (c - 1));
-    // per window: n mixed additions + the bucket stages, ~5 additions' worth per bucket (merge, running sums, segment multiple).
-    // Re-checked after the one-round window reduction (profiles/archive/r02_g_csweep.log, r02_g_c1516.log): at 2^20 c = 15 and 16 tie
-    // within 1-2 % (G1: 15 ahead, G2: 16 ahead), 2^17-2^19: 13 / 13 / 13-15, >= 2^21: 16.
-    const double cost = windows_for(bits, c) * (double(n) + 5.0 * nb);
-    if (cost < best) {
-      best = cost;
-      best_c = c;
+  int create(size_t count, unsigned flags) {
+    ev.reserve(ev.size() + count);
+    for (size_t i = 0; i < count; ++i) {
+      hipEvent_t e;
+      CSH_HIP(hipEventCreateWithFlags(&e, flags));
+      ev.push_back(e);
     }
+    return CSH_OK;
   }
-  return best_c;
-}
-
-// L = sorted entries per accumulate lane. Every lane of every wave performs exactly L mixed additions and one wave of
-// multiply-add code already saturates its SIMD's integer pipe, so the accumulate kernel takes ceil(waves / SIMDs) rounds of L
-// additions: a sawtooth in L (measured, BN254 G1 2^22, 16 windows: L = 128 -> 8192 waves = 8.00 per SIMD, 4.82 ms; L = 112 ->
-// 9.16 per SIMD = 10 rounds, 5.28 ms; L = 144 -> 5.36 ms; profiles/archive/r02_g_lsweep*.log). Longer lanes leave fewer partial sums
-// to merge (n W / L of them, ~4.6e-5 addition rounds each); with few long rounds the last one is balanced less well (+~0.2 round).
-// The plan takes the L in [16, 1024] with the smallest
-//   (rounds(L) + 0.2) * L + 4.6e-5 * n * W / L.
-// With 16 windows at the power-of-two sizes this lands on the former table (2^22 -> 128, 2^24 -> 256); it matters whenever
-// n W / 64 is not a multiple of the SIMD count: 17 windows (BN254 at 2^20: L = 32 meant 8.5 waves per SIMD, 9 rounds of 32
-// where 5 of 55 do, accumulate + merge 1.78 -> 1.73 ms; BN254 G2 5.48 -> 5.2 ms; 2^19: 1.33 -> 1.25 ms) and the arbitrary sizes of
-// real proving keys.
-// Small MSMs (round 4, profiles/archive/r04_zj_plan_sweep.log, r04_zk_short_lanes.log, interleaved): the round-count model above prices a
-// SIMD with ONE wave on it, but a group whose accumulate kernel fits `occ` waves per SIMD (BN254 G1: 144 VGPRs -> 3) runs them
-// interleaved, and with fewer than occ waves per SIMD in the whole launch the shorter lane wins: 2^15 c = 11 L = 16 -> 8 0.440 ->
-// 0.371 ms, 2^16 c = 12 L = 23 -> 12 0.489 -> 0.426, 2^17 c = 13 L = 21 -> 12..16 0.569 -> 0.531..0.534; at 2^18 (L = 27 = exactly
-// three waves per SIMD) and above the model's choice stands. Rule: never longer than the lane that fills occ waves per SIMD, down to 8
-// entries (below ~6 10^5 entries the launch is latency, not throughput: left alone). occ = 1 (the G2 kernels, shared plans): unchanged.
-inline uint32_t choose_lane_length(size_t n, int W, int occ = 1) {
-  if (const int fl = tune().msm_l.load(std::memory_order_relaxed); fl > 0) return (uint32_t)fl;
-  const double simds = (double)device_simds();
-  const int wpb = ACC_BLK / 64;
-  double best = 1e300;
-  uint32_t best_L = 16;
-  for (uint32_t L = 16; L <= 1024; ++L) {
-    const uint64_t lanes = (n + L - 1) / L;
-    const uint64_t waves = (uint64_t)W * ((lanes + ACC_BLK - 1) / ACC_BLK) * wpb;
-    const double rounds = ceil((double)waves / simds);
-    const double cost = (rounds + 0.2) * L + 4.6e-5 * (double)n * W / L;
-    if (cost < best) {
-      best = cost;
-      best_L = L;
-    }
-    if (rounds <= 1) break;  // one round already: longer lanes only cost
-  }
-  // Round 5 (after balanced windows; profiles/archive/r05_f_ab_lane_floor.log, r05_g_ab_narrow_lane_length.log, r05_h_ab_lane_lengths_large.log,
-  // interleaved, BN254 G1 / BLS12-381 G1 / Grumpkin): the lane that fills THREE waves per SIMD is the best or within 1 % of it on every G1
-  // group at 2^15 .. 2^18, also where the kernel's registers only admit two (BLS12-381 G1 2^17: 14 against the former 20, -9.7 %; more,
-  // shorter waves beat one full round), and from ~10^6 entries on a lane shorter than 12 entries loses to the partial sums it leaves the
-  // merge kernel (2^16: 12 against 8, -4.3 % BN254 G1, -8.6 % BLS12-381 G1 against its former 11, -4.0 % Grumpkin); 2^15 stays at 8.
-  const double entries = (double)n * W;
-  if (occ >= 2 && entries >= 6e5) {
-    uint32_t fill = (uint32_t)ceil(entries / (64.0 * simds * 3.0));
-    const uint32_t floor_l = entries >= 1e6 ? 12 : 8;
-    if (fill < floor_l) fill = floor_l;
-    if (fill < best_L) best_L = fill;
-  }
-  return best_L;
-}
-
-// Window reduction: S segments of `per` consecutive buckets per window, `lanes_per_segment` lanes each (1, or 2 for the lane-pair
-// form), a dependent chain of 2 per + ~21 point operations. One wave saturates its SIMD, so the stage takes
-// ceil(W S lanes / 64 / SIMDs) rounds of that chain: as many segments as still fit ONE round (BN254 2^20: 17 windows x 3277
-// segments of 5 buckets = 870 waves, chain 31 instead of 37 with the former 2048 x 8; a finer 4096 x 4 would need two rounds).
-// tune "msm_seg_buckets" forces `per`.
-inline uint32_t reduce_segments(uint32_t NB, int W, int lanes_per_segment) {
-  int per = tune().msm_seg_buckets.load(std::memory_order_relaxed);
-  if (per < 1 || per > 64) {
-    const uint64_t s_max = (uint64_t)device_simds() * 64 / ((uint64_t)W * lanes_per_segment);
-    per = (int)((NB + s_max - 1) / s_max);
-    if (per < 2) per = 2;
-  }
-  const uint32_t S = (NB + per - 1) / per;
-  return S < 1 ? 1 : S;
-}
-
-// Balanced windows (round 5). Uniform c-bit windows leave the top window whatever bits remain: 3 of 12 at 2^16 (c = 12, W = 22), 2 of 11 at
-// 2^15, 8 of 13 at 2^17 / 2^18 -- a window that costs its n additions like every other, whose few buckets hold n / 4 .. n / 128 entries
-// each (the oversized-bucket path: k_msm_giant_slices + k_msm_merge_giant 48 us of a 417 us MSM at 2^16, profiles/archive/r04_zp_msm_2p16_kernel_stats.csv)
-// and whose bucket stage is sized like a full one. Here W windows share the bits + 1 bits evenly: c = ceil((bits + 1) / W), the low
-// `wide` = bits + 1 - W (c - 1) windows take c bits, the others c - 1. c stays <= 16 (15-bit digit magnitudes). tune "msm_c" forces the
-// uniform form (tests, A/B), "msm_balanced" = 0 turns this off, "msm_w" forces W.
-struct WindowPlan {
-  int c, W, wide;
+  hipEvent_t operator[](size_t i) const { return ev[i]; }
 };
-inline WindowPlan choose_windows(size_t n, int bits) {
-  const int forced_c = tune().msm_c.load(std::memory_order_relaxed);
-  if ((forced_c >= 2 && forced_c <= 16) || tune().msm_balanced.load(std::memory_order_relaxed) == 0) {
-    const int c = choose_c(n, bits);
-    const int W = windows_for(bits, c);
-    return {c, W, W};
-  }
-  const int total = bits + 1;  // one spare bit absorbs the final carry of the signed recoding
-  auto balanced = [total](int W) {
-    const int c = (total + W - 1) / W;
-    return WindowPlan{c, W, total - W * (c - 1)};
-  };
-  const int forced_w = tune().msm_w.load(std::memory_order_relaxed);
-  if (forced_w >= (total + 15) / 16 && forced_w <= MAX_WINDOWS && (total + forced_w - 1) / forced_w >= 3) return balanced(forced_w);
-  // The number of windows is the one the uniform plan's width gives (choose_c: a cost model re-fitted by sweeps in rounds 2-4); the bits
-  // are then spread evenly over them. Letting the cost model pick W freely was measured first and is worse where the model is least
-  // exact: 2^19 took W = 18 (c = 15, 3 wide windows) for a modelled tie with the uniform W = 17 and ran 16 % slower, 2^18 W = 19 +1 %
-  // (profiles/archive/r05_b_ab_balanced.log).
-  return balanced(windows_for(bits, choose_c(n, bits)));
-}
-// width of window w / bit offset of window w in a plan
-CSH_HD int window_bits(int c, int wide, int w) { return w < wide ? c : c - 1; }
 
 struct PartialHeader {
   uint32_t magic, c, W, wide;  // wide == 0 (buffers of earlier builds) means W: uniform windows
@@ -758,94 +666,7 @@ struct PartialHeader {
 };
 constexpr uint32_t PARTIAL_MAGIC = 0x4d534d50u;  // "PMSM"
 
-// ---- the pipeline in three pieces: plan, sort stage (depends on the scalars only), bucket stage (per set of bases) ----
-inline MsmParams msm_plan(size_t n, int scalar_bits, int mont, int occ = 1) {
-  MsmParams p;
-  p.n = (uint32_t)n;
-  const WindowPlan wp = choose_windows(n, scalar_bits);
-  p.c = wp.c;
-  p.W = wp.W;
-  p.wide = wp.wide;
-  p.NB = 1u << (p.c - 1);
-  p.L = choose_lane_length(n, p.W, occ);
-  // Narrow windows (balanced plan) hold twice the entries per bucket; giving their lanes 2 L entries would leave k_msm_merge the same
-  // number of partial sums per bucket as in a wide window. Measured (profiles/archive/r05_g_ab_narrow_lane_length.log, interleaved, 2^14 .. 2^18,
-  // three groups): +6 .. +26 % -- at these sizes the accumulate launch is a dependent chain per lane, and doubling it costs more than the
-  // merge saves. One length is the default; tune "msm_variant" bit 6 (64) selects the doubled form (kept parity-tested for A/B).
-  p.Ln = (p.wide < p.W && p.L <= 32 && (tune().msm_variant.load(std::memory_order_relaxed) & 64) != 0) ? 2 * p.L : p.L;
-  const uint32_t max_lanes = (uint32_t)((n + p.L - 1) / p.L);
-  p.tmax = p.NB + max_lanes + 2;  // partial slots per window: slot = bucket + lane
-  p.S = reduce_segments(p.NB, p.W, 1);
-  p.mont = mont;
-  uint64_t ch = 512 / (uint64_t)p.W;
-  const uint64_t by_size = n / (2ull * p.NB);
-  if (ch > by_size) ch = by_size;
-  if (ch < 1) ch = 1;
-  p.CH = (uint32_t)ch;
-  p.chunk_len = (uint32_t)((n + ch - 1) / ch);
-  p.remap_n = p.remap_stride = p.remap_off = 0;
-  p.dig_g = p.dig_wp = 0;
-  tl_msm_params[0] = (uint32_t)p.c;
-  tl_msm_params[1] = (uint32_t)p.W;
-  tl_msm_params[2] = p.L;
-  tl_msm_params[3] = p.S;
-  return p;
-}
-
-// Merged-window mode (bases with fixed-base tables of g rows, table[k] = 2^(c W' k) P with W' = ceil(W / g)): the digit kernel
-// still produces W windows of n codes, but window w is filed as row k = w / W' of sort window w' = w % W', every entry pointing
-// at the precomputed multiple 2^(c W' k) P_i: the sort and bucket stages see W' windows of n g entries. g = W (one window, no
-// Horner over windows afterwards) is the full merge; g = 2..4 keeps the sort in its efficient regime and halves / quarters the
-// window reductions and the host Horner for g times the key memory.
-struct MergedPlan {
-  MsmParams dig;  // n points, W windows: digit kernel
-  MsmParams srt;  // n g entries per window, W' windows: sort + bucket stages
-};
-inline MergedPlan msm_plan_merged(size_t n, int scalar_bits, int mont, int c, int groups, size_t table_stride, size_t offset, int occ = 1) {
-  MergedPlan m;
-  MsmParams& d = m.dig;
-  d.n = (uint32_t)n;
-  d.c = c;
-  d.W = windows_for(scalar_bits, c);
-  d.NB = 1u << (c - 1);
-  d.L = d.tmax = d.S = d.CH = d.chunk_len = 0;
-  d.mont = mont;
-  d.remap_n = d.remap_stride = d.remap_off = 0;
-  const int g = groups < 1 ? 1 : (groups > d.W ? d.W : groups);
-  const int wp = (d.W + g - 1) / g;
-  d.dig_g = (uint32_t)g;
-  d.dig_wp = (uint32_t)wp;
-  d.wide = d.W;  // table rows are 2^(c W' k) P: uniform windows
-  d.Ln = 0;
-  MsmParams& p = m.srt;
-  const uint64_t n2 = (uint64_t)n * g;
-  p.n = (uint32_t)n2;
-  p.c = c;
-  p.W = wp;
-  p.NB = d.NB;
-  p.L = choose_lane_length((size_t)n2, p.W, occ);
-  const uint32_t max_lanes = (uint32_t)((n2 + p.L - 1) / p.L);
-  p.tmax = p.NB + max_lanes + 2;
-  p.S = reduce_segments(p.NB, p.W, 1);
-  p.mont = mont;
-  uint64_t ch = 512 / (uint64_t)p.W;
-  const uint64_t by_size = n2 / (2ull * p.NB);
-  if (ch > by_size) ch = by_size;
-  if (ch < 1) ch = 1;
-  p.CH = (uint32_t)ch;
-  p.chunk_len = (uint32_t)((n2 + ch - 1) / ch);
-  p.remap_n = (uint32_t)n;
-  p.remap_stride = (uint32_t)table_stride;
-  p.remap_off = (uint32_t)offset;
-  p.dig_g = p.dig_wp = 0;
-  p.wide = p.W;
-  p.Ln = p.L;
-  tl_msm_params[0] = (uint32_t)c;
-  tl_msm_params[1] = (uint32_t)p.W;
-  tl_msm_params[2] = p.L;
-  tl_msm_params[3] = p.S;
-  return m;
-}
+// ---- the pipeline in three pieces: plan (msm_plan.hpp), sort stage (depends on the scalars only), bucket stage (per set of bases) ----
 
 struct SortOut {  // what the bucket stage consumes
   uint32_t *start, *nlanes, *sorted;
@@ -1104,35 +925,28 @@ int msm_windows_dev(const Bases* B, size_t offset, size_t n, const uint64_t* sca
                     XYZZ<typename Cfg::Fq>* win_out_dev /* W entries, device */, MsmParams* p_out) {
   using Fr = typename Cfg::Fr;
   using Fq = typename Cfg::Fq;
-  const bool merged = msm_use_table(B, n);
-  MsmParams p, pdig;
-  const void* points;
-  if (merged) {
-    const MergedPlan m = msm_plan_merged(n, Fr::Params::BITS, mont, B->table_c, B->table_W, B->n, offset, accum_occupancy<Cfg>());
-    p = m.srt;
-    pdig = m.dig;
-    points = B->table;
-  } else {
-    p = pdig = msm_plan(n, Fr::Params::BITS, mont, accum_occupancy<Cfg>());
-    points = reinterpret_cast<const Affine<Fq>*>(B->points) + offset;
-  }
+  const MsmTable table{B->table_c, B->table_W, B->n, offset};
+  const MsmPlan plan = msm_plan(n, Fr::Params::BITS, mont, accum_occupancy<Cfg>(), msm_use_table(B, n) ? &table : nullptr);
+  const MsmParams &p = plan.srt, &pdig = plan.dig;
+  const void* points = plan.merged ? B->table : reinterpret_cast<const Affine<Fq>*>(B->points) + offset;
+  msm_record_params(p);
   *p_out = p;  // merged: W = 1 (the single window sum is the result)
   Arena& ar = arena_for(st);
   CSH_TRY(ar.reserve(msm_sort_bytes(p, pdig) + msm_bucket_bytes<Cfg>(&p)));
   const bool timing = tune().msm_timing.load(std::memory_order_relaxed) != 0;
-  hipEvent_t ev[7];
+  Events timed;  // [0] start, [1..3] sort stage, [4..5] bucket stage
   if (timing) {
-    for (auto& e : ev) CSH_HIP(hipEventCreate(&e));
-    CSH_HIP(hipEventRecord(ev[0], st));
+    CSH_TRY(timed.create(7, hipEventDefault));
+    CSH_HIP(hipEventRecord(timed[0], st));
   }
+  hipEvent_t* ev = timing ? timed.ev.data() : nullptr;
   SortOut so;
-  CSH_TRY(msm_sort_stage<Fr>(p, pdig, scalars_dev, st, ar, &so, timing ? ev : nullptr));
-  CSH_TRY(msm_bucket_stage<Cfg>(points, &p, &so, st, &ar, win_out_dev, timing ? ev : nullptr));
+  CSH_TRY(msm_sort_stage<Fr>(p, pdig, scalars_dev, st, ar, &so, ev));
+  CSH_TRY(msm_bucket_stage<Cfg>(points, &p, &so, st, &ar, win_out_dev, ev));
   if (timing) {
     CSH_HIP(hipEventSynchronize(ev[5]));
     for (int i = 0; i < 5; ++i) CSH_HIP(hipEventElapsedTime(&tl_msm_timing[i], ev[i], ev[i + 1]));
     CSH_HIP(hipEventElapsedTime(&tl_msm_timing[5], ev[0], ev[5]));
-    for (auto& e : ev) (void)hipEventDestroy(e);
   }
   return CSH_OK;
 }
@@ -1468,17 +1282,26 @@ int msm_tail_selftest_t(const void* dense_host, uint32_t NB, uint32_t S, int for
     if ((curve) == CSH_GRUMPKIN && (group) == CSH_G1) { using Cfg = csh::GrumpkinG1Cfg; return CALL; }  \
     if ((curve) == CSH_BLS12_377 && (group) == CSH_G1) { using Cfg = csh::Bls377G1Cfg; return CALL; } \
     if ((curve) == CSH_BLS12_377 && (group) == CSH_G2) { using Cfg = csh::Bls377G2Cfg; return CALL; } \
-    csh::set_error("unknown curve/group %d/%d", (int)(curve), (int)(group));                     \
+    (void)csh::group_ops(curve, group); /* not one of the seven: sets the error */              \
     return CSH_ERR_INVALID;                                                                     \
   } while (0)
 
-inline int scalar_bits_of(csh_curve_t c) {
-  return c == CSH_BLS12_381 ? Bls381FrParams::BITS : c == CSH_GRUMPKIN ? Bn254FqParams::BITS : c == CSH_BLS12_377 ? Bls377FrParams::BITS : Bn254FrParams::BITS;
-}
-inline size_t point_bytes_of(csh_curve_t c, csh_group_t g) {
-  const size_t fq = (c == CSH_BLS12_381 || c == CSH_BLS12_377) ? 48 : 32;
-  return 2 * fq * (g == CSH_G2 ? 2 : 1);
-}
-inline size_t partial_bytes_of(csh_curve_t c, csh_group_t g) { return sizeof(PartialHeader) + 2 * point_bytes_of(c, g) * MAX_WINDOWS; }
+// What the run-time dispatch needs to know about one of the seven groups, without Cfg as a type: one table, built from the Cfg types in
+// msm.hip (the one unit that names every instantiation, so taking these addresses gives no kernel a second home).
+struct GroupOps {
+  csh_curve_t curve;
+  csh_group_t group;
+  int scalar_bits;     // of Cfg::Fr
+  size_t point_bytes;  // a packed affine point
+  size_t xyzz_bytes;   // a window sum
+  int (*sort)(const MsmParams&, const MsmParams&, const uint64_t*, hipStream_t, Arena&, SortOut*, hipEvent_t*);  // msm_sort_stage<Cfg::Fr>
+  size_t (*bucket_bytes)(const MsmParams*);
+  int (*bucket)(const void*, const MsmParams*, const SortOut*, hipStream_t, Arena*, void*, hipEvent_t*);
+  void (*fold)(const void*, int, int, int, void*);
+  int (*occ)();  // accumulate waves of the group's kernel that fit one SIMD
+};
+// nullptr (and the error set) for a pair that is not one of the seven: the one place where "unknown curve/group" is decided
+const GroupOps* group_ops(csh_curve_t curve, csh_group_t group);
+inline size_t partial_bytes_of(csh_curve_t c, csh_group_t g) { return sizeof(PartialHeader) + 2 * group_ops(c, g)->point_bytes * MAX_WINDOWS; }
 
 }  // namespace csh

@@ -217,7 +217,7 @@ def test_msm_closed_form_full_size(gpu, curve, group, logn):
 @pytest.mark.parametrize("curve,group,logn", [("bn254", 0, 13), ("bn254", 0, 15), ("bn254", 0, 16), ("bn254", 0, 17), ("bn254", 0, 18), ("bn254", 0, 19),
                                                ("bls12_381", 0, 16), ("bn254", 1, 15), ("bls12_381", 1, 14), ("grumpkin", 0, 16)])
 def test_msm_balanced_windows_at_proving_key_sizes(gpu, curve, group, logn):
-    """Balanced windows (round 5; msm_impl.hpp choose_windows): W windows share the bits + 1 bits evenly -- widths c and c - 1 -- instead of
+    """Balanced windows (round 5; msm_plan.hpp choose_windows): W windows share the bits + 1 bits evenly -- widths c and c - 1 -- instead of
     c-bit windows with whatever is left on top (3 bits of 12 at 2^16). Known-dlog bases, uniform Montgomery scalars: the default plan, the
     uniform plan of rounds 1-4 (msm_balanced = 0) and every forced W around the model's choice give (sum s_i k_i) G, bit-identical to each
     other; odd lengths and an offset into the handle ride along."""
@@ -389,7 +389,8 @@ def test_concurrent_host_scalar_calls_share_one_upload(gpu, tables, share):
 @pytest.mark.parametrize("curve", ["bn254", "bls12_381"])
 def test_msm_multi_shares_one_sort(gpu, curve):
     """csh_msm_multi_dev: several MSMs (G1 and G2 mixed, different offsets) over one scalar vector, one digit sort;
-    every result equals the separate MSM / the oracle. Includes a skewed scalar set and n = 0."""
+    every result equals the separate MSM / the oracle. Includes a skewed scalar set and n = 0. Both schedules: bucket stages
+    alternating between two streams (msm_multi_overlap = 1, the default) and all on the caller's stream (0)."""
     import ctypes as C
     G1, G2 = cv.CURVES[curve]
     F = H.FR[curve]
@@ -403,13 +404,16 @@ def test_msm_multi_shares_one_sort(gpu, curve):
     for sc in (H.rand_elems(F, n, r), [1] * 200 + [F.p - 1] * 200 + H.rand_elems(F, 200, r), []):
         m = len(sc)
         dsc = gpu.DeviceBuffer.from_host(H.pack(F, sc) if m else np.zeros(4, dtype=np.uint64))
-        outs = [np.zeros(3 * gpu.point_bytes(cid, g) // 16, dtype=np.uint64) for _, g, _, _ in sets]
-        hs = (C.c_void_p * 4)(*[h.h.value for h in handles])
-        offs = (C.c_size_t * 4)(*[o for *_, o in sets])
-        po = (C.c_void_p * 4)(*[o.ctypes.data for o in outs])
-        gpu.bindings._check(L.csh_msm_multi_dev(hs, offs, C.c_size_t(4), C.c_size_t(m), dsc.ptr, 1, po, None))
-        for (G, g, pts, off), out in zip(sets, outs):
-            assert G.eq(H.jac_to_affine(G, out), G.msm(pts[off:off + m], sc)), (g, off, m)
+        want = [G.msm(pts[off:off + m], sc) for G, _, pts, off in sets]
+        for overlap in (1, 0):
+            outs = [np.zeros(3 * gpu.point_bytes(cid, g) // 16, dtype=np.uint64) for _, g, _, _ in sets]
+            hs = (C.c_void_p * 4)(*[h.h.value for h in handles])
+            offs = (C.c_size_t * 4)(*[o for *_, o in sets])
+            po = (C.c_void_p * 4)(*[o.ctypes.data for o in outs])
+            with gpu.tuned(msm_multi_overlap=overlap):
+                gpu.bindings._check(L.csh_msm_multi_dev(hs, offs, C.c_size_t(4), C.c_size_t(m), dsc.ptr, 1, po, None))
+            for (G, g, pts, off), out, w in zip(sets, outs, want):
+                assert G.eq(H.jac_to_affine(G, out), w), (g, off, m, overlap)
         dsc.free()
     for h in handles:
         h.free()
@@ -478,7 +482,7 @@ def test_msm_wide_window_tables(gpu, curve, group):
 
 def test_msm_fixed_base_tables_closed_form_and_multi(gpu):
     """2^19 known-dlog bases with tables (2^20 on table handles: tests/test_gpu_fullsize.py, the bench line): closed form; the shared-sort multi-MSM over handles with tables (mixed G1 / G2,
-    different offsets) equals the oracle."""
+    different offsets) equals the oracle, with the bucket stages on two streams (msm_multi_overlap = 1, the default) and on one (0)."""
     import ctypes as C
     from tests.check_closed_form import closed_form_point
     G = cv.BN254_G1
@@ -510,26 +514,176 @@ def test_msm_fixed_base_tables_closed_form_and_multi(gpu):
     sets = [(G1, 0, H.rand_points(G1, m + 3, r), 3), (G1, 0, H.rand_points(G1, m + 3, r), 3), (G2, 1, H.rand_points(G2, m + 3, r), 3),
             (G1, 0, H.rand_points(G1, m, r), 0)]
     sc = H.rand_elems(F, m, r)
+    want = [Gx.msm(pts[off:off + m], sc) for Gx, _, pts, off in sets]
+    dsc = gpu.DeviceBuffer.from_host(H.pack(F, sc))
     for c, groups in ((0, 2), (0, 0), (18, 0)):   # (18, 0): one bucket set of 2^17 buckets, the wide sort stage shared by the four MSMs
         handles = [gpu.Bases(0, g, cv.pack_points(Gx, pts)).precompute(c, groups) for Gx, g, pts, _ in sets]
-        _multi_over_tables(gpu, sets, handles, sc, m)
+        for overlap in (1, 0):
+            with gpu.tuned(msm_multi_overlap=overlap):
+                outs = _multi_dev(gpu, handles, [o for *_, o in sets], dsc, m)
+            for (Gx, g, _, off), o, w in zip(sets, outs, want):
+                assert Gx.eq(H.jac_to_affine(Gx, o), w), (c, groups, overlap, g, off)
+        for x in handles:
+            x.free()
+    dsc.free()
+
+
+def _multi_dev(gpu, handles, offsets, dsc, m):
+    """One csh_msm_multi_dev over the handles (Montgomery scalars on the device); -> the k Jacobian results."""
+    import ctypes as C
+    k = len(handles)
+    outs = [x._out() for x in handles]
+    hs = (C.c_void_p * k)(*[x.h.value for x in handles])
+    offs = (C.c_size_t * k)(*offsets)
+    po = (C.c_void_p * k)(*[o.ctypes.data for o in outs])
+    gpu.bindings._check(gpu.lib().csh_msm_multi_dev(hs, offs, C.c_size_t(k), C.c_size_t(m), dsc.ptr, 1, po, None))
+    return outs
+
+
+_RESORT = {}
+
+
+def _resort_case():
+    """m = 1500 BN254 scalars and four sets of bases with (length, offset) = (m + 3, 3), (m, 0), (m, 0), (m + 3, 3), the third in G2, and
+    the oracle's four results: computed once for the tests below, which only read it. On handles with tables the multi-MSM sorts
+    again at handles 0, 1 and 3 (the pair (length, offset) changes), at handle 3 while the second stream still holds readers of the
+    previous list (handle 1 ran there)."""
+    if not _RESORT:
+        G1, G2 = cv.CURVES["bn254"]
+        F = H.FR["bn254"]
+        r = H.rng(4242)
+        m = 1500
+        sets = [(G1, 0, H.rand_points(G1, m + 3, r, with_inf=True), 3), (G1, 0, H.rand_points(G1, m, r), 0),
+                (G2, 1, H.rand_points(G2, m, r), 0), (G1, 0, H.rand_points(G1, m + 3, r), 3)]
+        sc = H.rand_elems(F, m, r)
+        _RESORT.update(m=m, sets=sets, sc=sc, packed=[cv.pack_points(Gx, pts) for Gx, _, pts, _ in sets], scalars=H.pack(F, sc),
+                       want=[Gx.msm(pts[off:off + m], sc) for Gx, _, pts, off in sets])
+    return _RESORT
+
+
+def _resort_handles(gpu, layouts):
+    """Handles of _resort_case(); layouts[i] = (c, groups) of handle i's tables, None: no tables."""
+    case = _resort_case()
+    hs = [gpu.Bases(0, g, packed) for (_, g, _, _), packed in zip(case["sets"], case["packed"])]
+    for x, lay in zip(hs, layouts):
+        if lay is not None:
+            x.precompute(*lay)
+    return hs
+
+
+def _assert_resort_results(case, outs, which=range(4), tag=None):
+    for i, o in zip(which, outs):
+        Gx = case["sets"][i][0]
+        assert Gx.eq(H.jac_to_affine(Gx, o), case["want"][i]), (i, tag)
+
+
+@pytest.mark.parametrize("c,groups", [(0, 0), (18, 0)])
+def test_msm_multi_resorts_when_length_or_offset_changes(gpu, c, groups):
+    """Merged mode (every handle carries tables of one layout): see _resort_case -- three sorts for four handles, one of them behind
+    the second stream's readers. Both schedules (msm_multi_overlap 1 / 0) equal the oracle."""
+    case = _resort_case()
+    handles = _resort_handles(gpu, [(c, groups)] * 4)
+    dsc = gpu.DeviceBuffer.from_host(case["scalars"])
+    try:
+        for overlap in (1, 0):
+            with gpu.tuned(msm_multi_overlap=overlap):
+                outs = _multi_dev(gpu, handles, [o for *_, o in case["sets"]], dsc, case["m"])
+            _assert_resort_results(case, outs, tag=overlap)
+            assert gpu.bindings.msm_last_params()[1] == 1, "one row per window: the merged plan has one bucket set"
+    finally:
+        dsc.free()
         for x in handles:
             x.free()
 
 
-def _multi_over_tables(gpu, sets, handles, sc, m):
-    import ctypes as C
-    L = gpu.lib()
+def test_msm_multi_mixed_handles_take_the_plain_path(gpu):
+    """The handles of _resort_case with tables on all but one: the shared digit codes need one table layout on EVERY handle, so the call
+    runs the plain plan (the one it runs with tables ignored, msm_no_table = 1) and equals the oracle."""
+    case = _resort_case()
+    handles = _resort_handles(gpu, [(0, 0), None, (0, 0), (0, 0)])
+    dsc = gpu.DeviceBuffer.from_host(case["scalars"])
+    offsets = [o for *_, o in case["sets"]]
+    try:
+        outs = _multi_dev(gpu, handles, offsets, dsc, case["m"])
+        _assert_resort_results(case, outs, tag="mixed")
+        ran = gpu.bindings.msm_last_params()
+        with gpu.tuned(msm_no_table=1):
+            _assert_resort_results(case, _multi_dev(gpu, handles, offsets, dsc, case["m"]), tag="no_table")
+            assert gpu.bindings.msm_last_params() == ran and ran[1] > 1
+    finally:
+        dsc.free()
+        for x in handles:
+            x.free()
+
+
+@pytest.mark.parametrize("layout", [None, (0, 0), (18, 0)])
+def test_msm_multi_of_one_handle_equals_msm_dev(gpu, layout):
+    """k = 1: csh_msm_multi_dev over one handle (a G1 handle read from an offset, the G2 handle), without and with tables, returns the
+    bytes of csh_msm_dev on that handle, and both equal the oracle."""
+    case = _resort_case()
+    handles = _resort_handles(gpu, [layout] * 4)
+    dsc = gpu.DeviceBuffer.from_host(case["scalars"])
+    try:
+        for i in (0, 2):
+            off = case["sets"][i][3]
+            multi = _multi_dev(gpu, [handles[i]], [off], dsc, case["m"])[0]
+            single = handles[i].msm_dev(dsc, case["m"], offset=off)
+            assert np.array_equal(multi, single), (layout, i)
+            _assert_resort_results(case, [multi], which=[i], tag=layout)
+    finally:
+        dsc.free()
+        for x in handles:
+            x.free()
+
+
+@pytest.mark.parametrize("layout", [None, (13, 0)])
+def test_msm_multi_plans_like_its_g2_handle_alone(gpu, layout):
+    """One plan for the whole multi call, sized for the group with the fewest co-resident accumulate waves: with a G2 handle among them
+    (occupancy 1) csh_msm_last_params after the call equals the value after csh_msm_dev on that G2 handle alone with the same n --
+    plain handles and merged ones (tables of c = 13)."""
+    case = _resort_case()
+    handles = _resort_handles(gpu, [layout] * 4)
+    dsc = gpu.DeviceBuffer.from_host(case["scalars"])
+    try:
+        outs = _multi_dev(gpu, handles, [o for *_, o in case["sets"]], dsc, case["m"])
+        multi_params = gpu.bindings.msm_last_params()
+        _assert_resort_results(case, outs, tag=layout)
+        alone = handles[2].msm_dev(dsc, case["m"], offset=case["sets"][2][3])
+        assert gpu.bindings.msm_last_params() == multi_params, layout
+        _assert_resort_results(case, [alone], which=[2], tag=layout)
+        if layout:
+            assert multi_params[0] == layout[0]
+    finally:
+        dsc.free()
+        for x in handles:
+            x.free()
+
+
+def test_msm_timed_path(gpu):
+    """msm_timing = 1 (per-stage HIP events, csh_msm_last_timing): a plain MSM at n = 600 and a wide-table one (c = 17, one bucket set) at
+    n = 1300 equal the oracle; the six times (digits + histogram, scan, scatter, accumulate, tail, total) are finite and not negative, the
+    total positive."""
+    import math
+    G = cv.BN254_G1
     F = H.FR["bn254"]
-    dsc = gpu.DeviceBuffer.from_host(H.pack(F, sc))
-    outs = [np.zeros(3 * gpu.point_bytes(0, g) // 16, dtype=np.uint64) for _, g, _, _ in sets]
-    hs = (C.c_void_p * 4)(*[x.h.value for x in handles])
-    offs = (C.c_size_t * 4)(*[o for *_, o in sets])
-    po = (C.c_void_p * 4)(*[o.ctypes.data for o in outs])
-    gpu.bindings._check(L.csh_msm_multi_dev(hs, offs, C.c_size_t(4), C.c_size_t(m), dsc.ptr, 1, po, None))
-    for (Gx, g, pts, off), o in zip(sets, outs):
-        assert Gx.eq(H.jac_to_affine(Gx, o), Gx.msm(pts[off:off + m], sc)), (g, off)
-    dsc.free()
+    r = H.rng(606)
+    pts = H.rand_points(G, 1300, r, with_inf=True)
+    sc = H.rand_elems(F, 1300, r)
+    gpu.bindings.tune_set("msm_timing", 1)
+    try:
+        for n, c in ((600, None), (1300, 17)):
+            bases = gpu.Bases(0, 0, cv.pack_points(G, pts[:n]))
+            if c:
+                bases.precompute(c, 0)
+            got = bases.msm(H.pack(F, sc[:n]))
+            t = gpu.bindings.msm_last_timing()
+            bases.free()
+            assert G.eq(H.jac_to_affine(G, got), G.msm(pts[:n], sc[:n])), (n, c)
+            assert len(t) == 6 and all(math.isfinite(x) and x >= 0 for x in t) and t[5] > 0, (n, c, t)
+            if c:
+                assert gpu.bindings.msm_last_params()[:2] == [c, 1]
+    finally:
+        gpu.bindings.tune_set("msm_timing", 0)
 
 
 def test_plain_c_caller_of_the_boundary(gpu, tmp_path):

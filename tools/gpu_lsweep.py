@@ -2,7 +2,7 @@
 """Lane-length sweep of the MSM accumulate stage: for each job curve:group:logn (or curve:group:n=<points>) times csh_msm_dev with msm_l
 forced to every value of --ls (default: the planner's choice first, then a grid) and prints accumulate / tail / total per L.
 The accumulate kernel runs ceil(waves / SIMDs) rounds of L additions, so its time is a sawtooth in L; this is the measurement the
-planner's cost model (csrc/msm_impl.hpp msm_plan) is calibrated and checked against."""
+planner's cost model (csrc/msm_plan.hpp msm_plan) is calibrated and checked against."""
 import ctypes as C
 import json
 import os

@@ -63,7 +63,7 @@ def main():
     if args:
         rows = [r for r in rows if any(a in r["kernel"] for a in args)]
     rows.sort(key=lambda r: (r["object"], r["kernel"]))
-    cols = ["kernel", "vgpr", "vgpr_spill", "sgpr_spill", "scratch_bytes", "lds_bytes", "max_flat_workgroup_size", "object"]
+    cols = ["kernel", "vgpr", "vgpr_spill", "sgpr", "sgpr_spill", "scratch_bytes", "lds_bytes", "max_flat_workgroup_size", "object"]
     lines = [",".join(cols)] + [",".join('"%s"' % r[c] if c == "kernel" else str(r[c]) for c in cols) for r in rows]
     if csv:
         open(csv, "w").write("# code-object metadata (llvm-readelf --notes of the gfx950 code objects in co-snarks_amd/build/*.o), tools/kernel_meta.py\n" + "\n".join(lines) + "\n")

@@ -3,7 +3,8 @@
 Every round runs every variant once, alternating the order; a measurement = REPS back-to-back synchronous csh_msm_dev calls (wall
 clock, host fold included). Reported: median / min per variant and the median of the PAIRED differences against the first variant;
 every variant's result is compared bit for bit with the first variant's.
-    python tools/msm_ab.py --job 0:0:20 --rounds 12 --reps 10 c15=msm_c=15 c16=msm_c=16"""
+    python tools/msm_ab.py --job 0:0:20 --rounds 12 --reps 10 c15=msm_c=15 c16=msm_c=16
+A single variant (base=msm_c=0) times one build: two BUILDS are compared by alternating such runs from their two trees."""
 import argparse
 import ctypes as C
 import json
@@ -23,6 +24,7 @@ ap.add_argument("variants", nargs="+", help="name=key=value[,key=value...]")
 ap.add_argument("--job", default="0:0:20")
 ap.add_argument("--rounds", type=int, default=12)
 ap.add_argument("--reps", type=int, default=10)
+ap.add_argument("--precompute", type=int, default=None, metavar="C", help="csh_bases_precompute(C) on the handle first (fixed-base tables; 0 = automatic width)")
 args = ap.parse_args()
 variants = []
 for v in args.variants:
@@ -38,6 +40,8 @@ B.sync()
 h = C.c_void_p()
 B._check(L.csh_bases_upload_dev(curve, group, buf.ptr, C.c_size_t(n), C.c_size_t(0), None, C.byref(h)))
 buf.free()
+if args.precompute is not None:
+    B._check(L.csh_bases_precompute(h, args.precompute))
 rs = np.random.RandomState(1)
 limbs = rs.randint(0, 1 << 63, size=(n, 4), dtype=np.uint64)
 limbs[:, 3] >>= np.uint64(3)
@@ -80,7 +84,7 @@ apply({})
 base = variants[0][0]
 for name, kv in variants:
     t = times[name]
-    row = {"variant": name, "tune": kv, "job": args.job, "params_c_W_L_S": params[name], "rounds": args.rounds, "reps": args.reps,
+    row = {"variant": name, "tune": kv, "job": args.job, "precompute": args.precompute, "params_c_W_L_S": params[name], "rounds": args.rounds, "reps": args.reps,
            "ms_median": round(statistics.median(t), 4), "ms_min": round(min(t), 4), "Mpts_s_median": round(n / statistics.median(t) / 1e3, 1)}
     if name != base:
         d = [(a - b) / b for a, b in zip(t, times[base])]
