@@ -26,6 +26,7 @@ from .bindings import (  # noqa: F401
     Domain,
     device_count,
     eval_poly,
+    poly_div_linear,
     fr_bytes,
     groth16_h,
     have_device,

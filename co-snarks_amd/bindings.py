@@ -459,6 +459,33 @@ def eval_poly(curve: int, coeffs, point, ncomp: int = 1, n: int | None = None, o
     return res
 
 
+def poly_div_linear(curve: int, coeffs, root, ncomp: int = 1, sub0=None, n: int | None = None, out=None, rem=None, scale=None,
+                    accumulate: bool = False, stream=None):
+    """csh_poly_div_linear: division by (X - root) in the reference's direction, b_i = (-root)^-1 (coeffs[i] - b_(i-1)) -> (quotient
+    b_0 .. b_(n-2), rem = b_(n-1), ncomp elements: 0 exactly when the division is exact). `root`, `sub0` (ncomp elements taken off
+    coefficient 0 as it is loaded) and `scale` are host elements. A host array gives host arrays. DeviceBuffer coefficients (with n): the
+    stream-ordered form; out (default: in place) receives scale * b, or with accumulate has it added to what it holds (out must then be
+    another buffer); rem = a DeviceBuffer of 32 * ncomp bytes or None (NULL). Returns (out, rem) as given."""
+    rt = _u64(root)
+    assert rt.size == 4
+    s0 = _u64(sub0) if sub0 is not None else None
+    assert s0 is None or s0.size == 4 * ncomp
+    if isinstance(coeffs, DeviceBuffer):
+        out = coeffs if out is None else out
+        sc = _u64(scale) if scale is not None else None
+        assert sc is None or sc.size == 4
+        _check(lib().csh_poly_div_linear_dev(curve, _devptr(coeffs), C.c_size_t(n), C.c_uint32(ncomp), _p(rt), _p(s0), _p(sc), int(bool(accumulate)),
+                                             _devptr(out), _devptr(rem), _stream(stream)))
+        return out, rem
+    assert scale is None and not accumulate, "scale / accumulate: the device form only"
+    a = _u64(coeffs)
+    cnt = a.size // (4 * ncomp)
+    res = np.empty(4 * ncomp * max(cnt - 1, 0), dtype=np.uint64)
+    r = np.empty(4 * ncomp, dtype=np.uint64)
+    _check(lib().csh_poly_div_linear(curve, _p(a) if a.size else None, C.c_size_t(cnt), C.c_uint32(ncomp), _p(rt), _p(s0), _p(res) if res.size else None, _p(r)))
+    return res, r
+
+
 def rep3_local_mul_vec(curve: int, lhs_ab, rhs_ab, mask=None):
     l, r = _u64(lhs_ab), _u64(rhs_ab)
     n = l.size // 8

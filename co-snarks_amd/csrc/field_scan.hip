@@ -1,8 +1,8 @@
-// Whole-vector field arithmetic that is a scan or a reduction: running product, batch inverse, polynomial evaluation.
+// Whole-vector field arithmetic that is a scan or a reduction: running product, batch inverse, polynomial evaluation, division by (X - r).
 // Reference call sites: array_prod_mul (co-plonk/src/round2.rs:164-165), inv_vec / inv_many (co-noir-common/src/mpc/rep3.rs:208-257),
-// evaluate_poly_public (co-plonk/src/round4.rs:126-132), eval_poly (rep3/poly.rs:39-68).
+// evaluate_poly_public (co-plonk/src/round4.rs:126-132), eval_poly (rep3/poly.rs:39-68), factor_roots / div_by_zerofier (further down).
 //
-// One decomposition for all three: a lane takes a contiguous run of E elements (tune "scan_lane_run"), a tile is one workgroup of
+// One decomposition for all four: a lane takes a contiguous run of E elements (tune "scan_lane_run"), a tile is one workgroup of
 // "scan_tile_lanes" lanes, and every operation is  per-tile totals -> a spine run by ONE workgroup that walks the totals "scan_spine_step"
 // at a time with a running carry (any tile count, no recursion) -> a per-tile downsweep (the evaluation has none: its spine's carry is the
 // result). Products run in the signed lazy field; field_scan.hpp says which scale every value has.
@@ -185,12 +185,7 @@ __global__ __launch_bounds__(SCAN_TILE_MAX) void k_inverse_down(const F* in, F* 
 }
 
 // ---- polynomial evaluation --------------------------------------------------------------------------------------------------------------
-// pw.p[j] = x^(2^j), R' domain, canonical and packed: every length in the decomposition is a power of two, so these are all the powers.
-constexpr int SCAN_POWERS = 32;
-template <class F>
-struct PowTable {
-  F p[SCAN_POWERS];
-};
+// pw (field_scan.hpp): pw.p[j] = x^(2^j), R' domain, canonical and packed.
 // lo + x^(len 2^k) hi with len = 2^base positions per lane. Values are R scale; one carry step per level keeps the limbs inside the
 // product's operand bound, fold_top() after the lane and the wave levels keeps the value below 8 p.
 template <class F>
@@ -239,6 +234,109 @@ __global__ __launch_bounds__(SCAN_SPINE_MAX) void k_eval_spine(const LzOf<F>* to
     acc = LZ::add(step, LZ::mul(acc, xs)).fold_top();
   }
   if (threadIdx.x == 0) out[blockIdx.x] = acc.canonical_wide().pack();
+}
+
+// ---- division by (X - r) ------------------------------------------------------------------------------------------------------------------
+// factor_roots (co-noir-common polynomial.rs:183, shared_polynomial.rs:92-140) and div_by_zerofier(.., 1, beta) (co-plonk round5.rs:78-91),
+// in the reference's direction: c = (-r)^-1, b_(-1) = 0, b_i = c (a_i - b_(i-1)). With w = 1 / r = -c this is s_i = a_i + w s_(i-1),
+// b_i = c s_i: an inclusive scan under wsum_combine (field_scan.hpp) -- EvalOp's algebra as a scan, in the other direction. Coefficients
+// and every s and b are R scale; w's powers and c are R'-domain operands, so no product needs times32().
+template <class F>
+struct DivOp {
+  using LZ = LzOf<F>;
+  const PowTable<F>* pw;
+  int base;
+  __device__ __forceinline__ LZ operator()(const LZ& lo, const LZ& hi, int k) const { return wsum_combine(lo, hi, LZ::unpack(pw->p[base + k])); }
+  __device__ __forceinline__ LZ settle(const LZ& v) const { return v.fold_top(); }
+  __device__ __forceinline__ LZ identity() const { return LZ::zero(); }
+};
+// what one call carries besides its vectors: c and the output scale (R' domain, canonical and packed), the value taken off coefficient 0
+template <class F>
+struct DivArgs {
+  F c, scale, sub0[2];
+  int scaled, accumulate;
+};
+// coefficient i of component comp as it enters the recurrence: 0 past the end, sub0 off the constant term
+template <class F>
+__device__ __forceinline__ LzOf<F> div_coeff(const F* in, size_t n, uint32_t ncomp, uint32_t comp, size_t i, const DivArgs<F>& a) {
+  using LZ = LzOf<F>;
+  LZ v = i < n ? LZ::unpack(in[i * ncomp + comp]) : LZ::zero();
+  if (i == 0) v = LZ::sub(v, LZ::unpack(a.sub0[comp]));
+  return v;
+}
+
+// Launch 1: tot[comp][tile] = the s the tile ends with when it starts from 0; blockIdx.y = component
+template <class F>
+__global__ __launch_bounds__(SCAN_TILE_MAX) void k_div_totals(const F* in, size_t n, uint32_t ncomp, int E, int lg_e, PowTable<F> pw,
+                                                               DivArgs<F> a, LzOf<F>* tot) {
+  using LZ = LzOf<F>;
+  __shared__ LZ lds[16];
+  const size_t base = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * (size_t)E;
+  const uint32_t comp = blockIdx.y;
+  const LZ w = LZ::unpack(pw.p[0]);
+  LZ s = LZ::zero();
+#pragma unroll 1
+  for (int e = 0; e < E; ++e) s = LZ::add(div_coeff(in, n, ncomp, comp, base + e, a), LZ::mul(s, w));
+  const LZ total = block_reduce(s, lds, DivOp<F>{&pw, lg_e});
+  if (threadIdx.x == 0) tot[(size_t)comp * gridDim.x + blockIdx.x] = total;
+}
+// Launch 2: pre[comp][t] = the s in front of tile t; blockIdx.x = component. The spine also leaves lane_w[l] = w^(E l), l < 64, for
+// the downsweep: there every lane would otherwise pay the 6 products of lane_powers itself.
+template <class F>
+__global__ __launch_bounds__(SCAN_SPINE_MAX) void k_div_spine(const LzOf<F>* tot, size_t tiles, int lg_e, int lg_tile, PowTable<F> pw,
+                                                               LzOf<F>* pre, LzOf<F>* lane_w) {
+  using LZ = LzOf<F>;
+  __shared__ ScanLds<LZ> s;
+  const LZ* t = tot + (size_t)blockIdx.x * tiles;
+  LZ* p = pre + (size_t)blockIdx.x * tiles;
+  if (blockIdx.x == 0) {
+    const LZ lw = lane_powers(LZ::unpack(pw.p[lg_e]));
+    if (threadIdx.x < 64) lane_w[threadIdx.x] = lw;
+  }
+  const LZ tile_w = lane_powers(LZ::unpack(pw.p[lg_tile]));
+  const size_t S = blockDim.x;
+  LZ carry = LZ::zero(), total;
+  for (size_t c0 = 0; c0 < tiles; c0 += S) {
+    const size_t i = c0 + threadIdx.x;
+    const LZ before = block_excl_scan_wsum(i < tiles ? t[i] : LZ::zero(), carry, tile_w, pw, lg_tile, s, &total);
+    if (i < tiles) p[i] = before;
+    carry = total;
+  }
+}
+// Launch 3: out[i] = b_i for i < n - 1 (times scale, added to what is there: DivArgs), rem[comp] = b_(n-1). A lane reads its whole
+// run before it writes any of it, and no lane touches another's: out may equal in. The last tile is padded with zeros, which keep
+// multiplying s by w, so b_(n-1) is taken where it appears, not from the spine's last carry.
+template <class F, int E>
+__global__ __launch_bounds__(SCAN_TILE_MAX) void k_div_down(const F* in, F* out, size_t n, uint32_t ncomp, int lg_e, PowTable<F> pw,
+                                                             DivArgs<F> a, const LzOf<F>* pre, const LzOf<F>* lane_w, F* rem) {
+  using LZ = LzOf<F>;
+  __shared__ ScanLds<LZ> s;
+  const size_t base = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * (size_t)E;
+  const uint32_t comp = blockIdx.y;
+  const LZ w = LZ::unpack(pw.p[0]), c = LZ::unpack(a.c);
+  LZ x[E];
+  LZ run = LZ::zero();
+  run_for<0, E>([&](auto ic) CSH_LAMBDA_INLINE {
+    constexpr int e = decltype(ic)::value;
+    x[e] = div_coeff(in, n, ncomp, comp, base + e, a);
+    run = LZ::add(x[e], LZ::mul(run, w));
+  });
+  LZ total;
+  const LZ before = block_excl_scan_wsum(run, pre[(size_t)comp * gridDim.x + blockIdx.x], lane_w[threadIdx.x & 63], pw, lg_e, s, &total);
+  LZ b = LZ::mul(before, c);  // b at (run start - 1)
+  run_for<0, E>([&](auto ic) CSH_LAMBDA_INLINE {
+    constexpr int e = decltype(ic)::value;
+    const size_t i = base + e;
+    b = LZ::mul(LZ::sub(x[e], b), c);
+    if (i + 1 < n) {
+      F* o = out + i * ncomp + comp;
+      LZ r = a.scaled ? LZ::mul(b, LZ::unpack(a.scale)) : b;
+      if (a.accumulate) r = LZ::add(LZ::unpack(*o), r);
+      *o = r.canonical_wide().pack();
+    } else if (i + 1 == n && rem) {
+      rem[comp] = b.canonical_wide().pack();
+    }
+  });
 }
 
 // ---- typed launchers ------------------------------------------------------------------------------------------------------------------
@@ -316,6 +414,43 @@ static int eval_poly_t(const uint64_t* coeffs, size_t n, uint32_t ncomp, const u
   return CSH_OK;
 }
 
+template <class F>
+static int poly_div_linear_t(const uint64_t* in, size_t n, uint32_t ncomp, const uint64_t root[4], const uint64_t* sub0, const uint64_t* scale,
+                             int accumulate, uint64_t* out, uint64_t* rem, hipStream_t st) {
+  using LZ = LzOf<F>;
+  if (n == 0) {
+    if (rem) CSH_HIP(hipMemsetAsync(rem, 0, sizeof(F) * ncomp, st));
+    return CSH_OK;
+  }
+  if (n == 1 && !rem) return CSH_OK;  // no quotient coefficient, and nobody asks for b_0
+  F r, sc;
+  memcpy(&r, root, sizeof(F));
+  const F w = F::inv(r);  // the one inversion, on the host
+  const PowTable<F> pw = pow_table<LZ, F>(LZ::from_fp(w));
+  DivArgs<F> a;
+  a.c = LZ::from_fp(F::neg(w)).canonical().pack();
+  a.scaled = scale != nullptr;
+  a.accumulate = accumulate;
+  if (scale) memcpy(&sc, scale, sizeof(F));
+  a.scale = scale ? LZ::from_fp(sc).canonical().pack() : F::zero();
+  memset(a.sub0, 0, sizeof a.sub0);
+  if (sub0) memcpy(a.sub0, sub0, sizeof(F) * ncomp);
+  const ScanPlan p = scan_plan(n);
+  Arena& ar = arena_for(st);
+  const size_t count = p.tiles * ncomp;
+  CSH_TRY(ar.reserve(2 * Arena::padded(count * sizeof(LZ)) + Arena::padded(64 * sizeof(LZ))));
+  LZ* tot = ar.take<LZ>(count);
+  LZ* pre = ar.take<LZ>(count);
+  LZ* lane_w = ar.take<LZ>(64);
+  const dim3 grid((unsigned)p.tiles, ncomp), blk(p.lanes);
+  hipLaunchKernelGGL(k_div_totals<F>, grid, blk, 0, st, (const F*)in, n, ncomp, p.E, p.lg_e, pw, a, tot);
+  hipLaunchKernelGGL(k_div_spine<F>, dim3(ncomp), dim3(p.spine), 0, st, tot, p.tiles, p.lg_e, p.lg_e + p.lg_lanes, pw, pre, lane_w);
+  if (p.E == 4) hipLaunchKernelGGL((k_div_down<F, 4>), grid, blk, 0, st, (const F*)in, (F*)out, n, ncomp, p.lg_e, pw, a, pre, lane_w, (F*)rem);
+  else hipLaunchKernelGGL((k_div_down<F, 8>), grid, blk, 0, st, (const F*)in, (F*)out, n, ncomp, p.lg_e, pw, a, pre, lane_w, (F*)rem);
+  CSH_HIP(hipGetLastError());
+  return CSH_OK;
+}
+
 }  // namespace csh
 
 using namespace csh;
@@ -357,6 +492,25 @@ int csh_eval_poly_dev(csh_curve_t f, const uint64_t* coeffs, size_t n, uint32_t 
   CSH_TRY(ensure_device());
   hipStream_t st = resolve_stream(stream);
   FR_DISPATCH(f, eval_poly_t<F>(coeffs, n, ncomp, point, out, st));
+}
+
+// the checks both forms of the division make before they ask for a device
+static int poly_div_linear_check(csh_curve_t f, const uint64_t* in, size_t n, uint32_t ncomp, const uint64_t* root, int accumulate,
+                                 const uint64_t* out) {
+  SCAN_REQUIRE_FIELD(f);
+  SCAN_REQUIRE_N(n);
+  CSH_REQUIRE(ncomp >= 1 && ncomp <= 2, "ncomp must be 1 or 2");
+  CSH_REQUIRE(root && (n == 0 || in) && (n <= 1 || out), "poly_div_linear: NULL argument");
+  CSH_REQUIRE(root[0] | root[1] | root[2] | root[3], "poly_div_linear: root is 0 -- the quotient by X is a shift of the coefficients, do that instead");
+  CSH_REQUIRE(!(accumulate && out == in), "poly_div_linear: accumulate needs out != in");
+  return CSH_OK;
+}
+int csh_poly_div_linear_dev(csh_curve_t f, const uint64_t* in, size_t n, uint32_t ncomp, const uint64_t root[4], const uint64_t* sub0,
+                            const uint64_t* scale, int accumulate, uint64_t* out, uint64_t* rem, void* stream) {
+  CSH_TRY(poly_div_linear_check(f, in, n, ncomp, root, accumulate, out));
+  CSH_TRY(ensure_device());
+  hipStream_t st = resolve_stream(stream);
+  FR_DISPATCH(f, poly_div_linear_t<F>(in, n, ncomp, root, sub0, scale, accumulate, out, rem, st));
 }
 
 // ---- host-pointer forms: H2D, compute, D2H on the thread's stream ------------------------------------------------------------------------
@@ -406,6 +560,22 @@ int csh_eval_poly(csh_curve_t f, const uint64_t* coeffs, size_t n, uint32_t ncom
   CSH_TRY(h.up(dout, nullptr, ob));
   CSH_TRY(csh_eval_poly_dev(f, dc, n, ncomp, point, dout, h.st));
   return h.down(out, dout, ob);
+}
+
+int csh_poly_div_linear(csh_curve_t f, const uint64_t* in, size_t n, uint32_t ncomp, const uint64_t root[4], const uint64_t* sub0, uint64_t* out,
+                        uint64_t* rem) {
+  CSH_TRY(poly_div_linear_check(f, in, n, ncomp, root, 0, out));
+  HostStage h;
+  const size_t cb = 32 * n * ncomp, ob = n ? 32 * (n - 1) * ncomp : 0, rb = 32 * ncomp;
+  CSH_TRY(h.begin(Arena::padded(cb) + Arena::padded(rb)));
+  uint64_t *d, *drem;
+  CSH_TRY(h.up(d, in, cb));
+  CSH_TRY(h.up(drem, nullptr, rb));
+  CSH_TRY(csh_poly_div_linear_dev(f, d, n, ncomp, root, sub0, nullptr, 0, d, rem ? drem : nullptr, h.st));  // in place on the staged copy
+  if (rem) CSH_HIP(hipMemcpyAsync(rem, drem, rb, hipMemcpyDeviceToHost, h.st));
+  if (ob) CSH_TRY(h.down(out, d, ob));
+  CSH_HIP(hipStreamSynchronize(h.st));
+  return CSH_OK;
 }
 
 }  // extern "C"

@@ -82,6 +82,36 @@ CSH_HD FpS<LP, F32> lazy_inv(const FpS<LP, F32>& a, InvScratch<FpS<LP, F32>>& s)
   return acc;
 }
 
+// ---- weighted sums: the algebra of a first-order linear recurrence s_i = a_i + w s_(i-1) ---------------------------------------------------
+// pw.p[j] = w^(2^j), R' domain, canonical and packed: every length in the decomposition is a power of two, so these are all the powers
+// (polynomial evaluation: w = the point; division by (X - r): w = 1 / r).
+constexpr int SCAN_POWERS = 32;
+template <class F>
+struct PowTable {
+  F p[SCAN_POWERS];
+};
+template <class LZ, class F>
+CSH_HD PowTable<F> pow_table(LZ sq) {  // sq: R' domain; about 30 squarings, on the host: cheaper than a launch
+  PowTable<F> pw;
+  for (int j = 0; j < SCAN_POWERS; ++j) {
+    pw.p[j] = sq.canonical().pack();
+    sq = LZ::sqr(sq);
+  }
+  return pw;
+}
+// Two adjacent segments of the recurrence, `lo` the earlier one, each summarised by the s it ends with when it starts from 0: the pair
+// ends with hi + w^(length of hi) lo. wpow: that power, R' domain, a loaded (canonical) value or a product; lo, hi: R scale.
+// Bounds. Limbs: lo is a product's first operand, so it may be one two-term sum (LIM2); the sum has three terms' limbs at most
+// (hi may itself be a two-term sum: 3 x 2^B < 2^31) and leaves with one carry step as a normalised value. Value: a product of a
+// first operand within (-8 p, 8 p) and a wpow below 1.04 p lies in (-0.13 p, 1.13 p) (p / R' < 1 / 67 for the three scalar fields), so
+// every level adds at most 1.13 p to |hi|. A lane's run ends within (-2.13 p, 2.13 p); after the 6 levels of a wave the operands of the
+// products have stayed below 2.13 + 5 x 1.13 = 7.8 p and the result is below 8.9 p, where fold_top() (good to 64 p) brings it back into
+// (-p, 2 p) before the at most 4 levels across waves (2 + 4 x 1.13 p). The callers below fold where this paragraph says.
+template <class LZ>
+CSH_HD LZ wsum_combine(const LZ& lo, const LZ& hi, const LZ& wpow) {
+  return LZ::add(hi, LZ::mul(lo, wpow)).normalized();
+}
+
 #if defined(__HIPCC__)
 template <class LZ>
 __device__ __forceinline__ LZ lz_shfl_up(const LZ& v, int d) {
@@ -165,6 +195,61 @@ __device__ __forceinline__ LZ block_excl_scan_mul(const LZ& v, const LZ& carry, 
   *total = s.wpre[nw];
   return ll == 0 ? base : m;
 }
+// ---- block scan under the weighted sum ------------------------------------------------------------------------------------------------
+// step^(lane), R' domain, in every wave: what a lane's value is weighted with when something from before its wave is added to it
+template <class LZ>
+__device__ __forceinline__ LZ lane_powers(const LZ& step) {
+  const int lane = threadIdx.x & 63;
+  LZ x = step;
+#pragma unroll 1
+  for (int d = 1; d < 64; d <<= 1) {
+    const LZ m = LZ::mul(x, lz_shfl_up(x, d));
+    if (lane >= d) x = m;
+  }
+  const LZ up = lz_shfl_up(x, 1);
+  return lane == 0 ? LZ::one() : up;
+}
+// Exclusive prefix over the block's threads in thread order, the shape of block_excl_scan_mul: lane totals by shuffles (9 per step),
+// wave totals through LDS, a second shuffle scan in wave 0. Every thread holds the summary v of 2^base positions (R scale, limbs of
+// at most one two-term sum, |v| < 2.13 p); carry: the s that precedes the block (the same limits, |carry| < 3.2 p). The result is
+// the s in front of the thread's positions and *total the s the block ends with; lane_w = w^(2^base lane) (lane_powers, or a table of
+// them). Bounds as derived above wsum_combine: the carry enters wave 0's total as one more level (2 + 1.13 + 4 x 1.13 < 7.7 p), and
+// the result is a folded prefix plus one product: within (-1.2 p, 3.2 p), limbs of one two-term sum -- a product's first operand.
+// Every thread of the block calls it; three barriers inside.
+template <class LZ, class Pw>
+__device__ __forceinline__ LZ block_excl_scan_wsum(const LZ& v, const LZ& carry, const LZ& lane_w, const Pw& pw, int base, ScanLds<LZ>& s,
+                                                   LZ* total) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  LZ incl = v;
+#pragma unroll 1
+  for (int k = 0; k < 6; ++k) {
+    const LZ m = wsum_combine(lz_shfl_up(incl, 1 << k), incl, LZ::unpack(pw.p[base + k]));
+    if (lane >= (1 << k)) incl = m;
+  }
+  incl = incl.fold_top();
+  __syncthreads();  // the previous call's readers are done with s
+  if (lane == 63) s.wtot[wv] = incl;
+  __syncthreads();
+  if (wv == 0) {
+    LZ x = lane < nw ? s.wtot[lane] : LZ::zero();
+    const LZ first = wsum_combine(carry, x, LZ::unpack(pw.p[base + 6]));  // the carry is a wave in front of wave 0
+    if (lane == 0) x = first;
+#pragma unroll 1
+    for (int k = 0; k < 4; ++k) {
+      const LZ m = wsum_combine(lz_shfl_up(x, 1 << k), x, LZ::unpack(pw.p[base + 6 + k]));
+      if (lane >= (1 << k)) x = m;
+    }
+    x = x.fold_top();
+    if (lane < nw) s.wpre[lane + 1] = x;
+    if (lane == 0) s.wpre[0] = carry;
+  }
+  __syncthreads();
+  const LZ before = s.wpre[wv];
+  const LZ m = LZ::add(lz_shfl_up(incl, 1), LZ::mul(before, lane_w));
+  *total = s.wpre[nw];
+  return lane == 0 ? before : m;
+}
 #endif
+
 
 }  // namespace csh

@@ -4,6 +4,7 @@
 #define CSH_CHECK_BOUNDS 1  // host-side limb-bound contract checks in field29.hpp
 #include <string.h>
 
+#include <functional>
 #include <vector>
 
 #include "common.hpp"
@@ -350,8 +351,83 @@ static int scan_host_t(int op, const uint64_t* in, size_t n, int run, uint64_t* 
   }
   return CSH_OK;
 }
+// Host run of the division by (X - r) (field_scan.hip: k_div_totals, block_excl_scan_wsum, k_div_down) with the limb-bound checks on:
+// the same routines, the same levels and the same folds, lane after lane instead of side by side. One block of 64-lane waves (at most
+// 16) after another, the carry handed on as the spine hands it to a tile. run = elements per lane, a power of two. out: b_0 .. b_(n-1)
+// per component, the popped b_(n-1) included. All arkworks-Montgomery in and out.
+template <class LZ>
+static void hillis_steele(std::vector<LZ>& v, int levels, const std::function<LZ(const LZ& lo, const LZ& hi, int k)>& op) {
+  for (int k = 0; k < levels; ++k) {
+    const std::vector<LZ> old(v);
+    for (size_t l = 0; l < v.size(); ++l) {
+      const LZ m = op(old[l >= (size_t(1) << k) ? l - (size_t(1) << k) : l], old[l], k);  // a lane without a partner shuffles itself in
+      if (l >= (size_t(1) << k)) v[l] = m;
+    }
+  }
+}
+template <class LZ, class F>
+static int divlin_host_t(const uint64_t* in, size_t n, uint32_t ncomp, int run, const uint64_t* root, const uint64_t* sub0, uint64_t* out) {
+  F r;
+  memcpy(&r, root, sizeof(F));
+  const F w = F::inv(r);
+  const PowTable<F> pw = pow_table<LZ, F>(LZ::from_fp(w));
+  const LZ wz = LZ::unpack(pw.p[0]), c = LZ::unpack(LZ::from_fp(F::neg(w)).canonical().pack());
+  int base = 0;
+  while ((1 << base) < run) ++base;
+  const size_t lanes = (n + run - 1) / run, block = 1024;
+  for (uint32_t comp = 0; comp < ncomp; ++comp) {
+    auto coeff = [&](size_t i) {
+      F x = F::zero(), s0 = F::zero();
+      if (i < n) memcpy(&x, in + 4 * (i * ncomp + comp), sizeof(F));
+      if (i == 0 && sub0) memcpy(&s0, sub0 + 4 * comp, sizeof(F));
+      return i == 0 ? LZ::sub(LZ::unpack(x), LZ::unpack(s0)) : LZ::unpack(x);
+    };
+    LZ carry = LZ::zero();
+    for (size_t b0 = 0; b0 < lanes; b0 += block) {
+      const size_t nl = ((lanes - b0 < block ? lanes - b0 : block) + 63) / 64 * 64, nw = nl / 64;
+      std::vector<LZ> incl(nl), lane_w(64, LZ::unpack(pw.p[base])), wtot(16, LZ::zero());
+      for (size_t l = 0; l < nl; ++l) {  // the lane runs
+        LZ s = LZ::zero();
+        for (int e = 0; e < run; ++e) s = LZ::add(coeff((b0 + l) * run + e), LZ::mul(s, wz));
+        incl[l] = s;
+      }
+      hillis_steele<LZ>(lane_w, 6, [](const LZ& lo, const LZ& hi, int) { return LZ::mul(hi, lo); });  // lane_powers
+      lane_w.insert(lane_w.begin(), LZ::one());
+      for (size_t wv = 0; wv < nw; ++wv) {  // block_excl_scan_wsum
+        std::vector<LZ> wave(incl.begin() + 64 * wv, incl.begin() + 64 * (wv + 1));
+        hillis_steele<LZ>(wave, 6, [&](const LZ& lo, const LZ& hi, int k) { return wsum_combine(lo, hi, LZ::unpack(pw.p[base + k])); });
+        for (size_t l = 0; l < 64; ++l) incl[64 * wv + l] = wave[l].fold_top();
+        wtot[wv] = incl[64 * wv + 63];
+      }
+      wtot[0] = wsum_combine(carry, wtot[0], LZ::unpack(pw.p[base + 6]));
+      hillis_steele<LZ>(wtot, 4, [&](const LZ& lo, const LZ& hi, int k) { return wsum_combine(lo, hi, LZ::unpack(pw.p[base + 6 + k])); });
+      for (size_t l = 0; l < nl && (b0 + l) * run < n; ++l) {  // k_div_down
+        const size_t wv = l / 64, ln = l % 64;
+        const LZ before = wv ? wtot[wv - 1].fold_top() : carry;
+        const LZ excl = ln ? LZ::add(incl[l - 1], LZ::mul(before, lane_w[ln])) : before;
+        LZ b = LZ::mul(excl, c);
+        for (size_t i = (b0 + l) * run; i < n && i < (b0 + l + 1) * run; ++i) {
+          b = LZ::mul(LZ::sub(coeff(i), b), c);
+          const F o = b.canonical_wide().pack();
+          memcpy(out + 4 * (i * ncomp + comp), &o, sizeof(F));
+        }
+      }
+      carry = wtot[nw - 1].fold_top();
+    }
+  }
+  return CSH_OK;
+}
 
 extern "C" {
+
+int csh_selftest_divlin_host(int field_of, const uint64_t* in, size_t n, uint32_t ncomp, int run, const uint64_t* root, const uint64_t* sub0,
+                             uint64_t* out) {
+  if (run < 1 || (run & (run - 1)) || ncomp < 1 || ncomp > 2 || !root || !(root[0] | root[1] | root[2] | root[3])) return CSH_ERR_INVALID;
+  if (field_of == CSH_BN254) return divlin_host_t<Fr29s, Bn254Fr>(in, n, ncomp, run, root, sub0, out);
+  if (field_of == CSH_BLS12_381) return divlin_host_t<Bls381Fr29s, Bls381Fr>(in, n, ncomp, run, root, sub0, out);
+  if (field_of == CSH_BLS12_377) return divlin_host_t<Bls377Fr29s, Bls377Fr>(in, n, ncomp, run, root, sub0, out);
+  return CSH_ERR_INVALID;
+}
 
 int csh_selftest_scan_host(int field_of, int op, const uint64_t* in, size_t n, int run, uint64_t* out) {
   if (op < 0 || op > 2 || run < 1) return CSH_ERR_INVALID;

@@ -375,6 +375,44 @@ def driver_eval_poly(curve: int, driver: int, coeffs_mont, point_mont, seed: int
     return out.reshape(3, 2, 4) if driver == REP3 else out
 
 
+def driver_factor_roots(curve: int, driver: int, coeffs_mont, root_mont, seed: int = 1, zerofier: bool = False):
+    """::factor_roots, or Round5::div_by_zerofier(inout, 1, root) (zerofier). Plain: (n - 1, 4); Rep3: (3, n - 1, 2, 4); Shamir (three
+    parties, threshold 1): (3, n - 1, 4). Root 0 is the shift (factor_roots only). The coefficients are shared inside with `seed`."""
+    c = np.ascontiguousarray(coeffs_mont, dtype=np.uint64).reshape(-1, 4)
+    rt = np.ascontiguousarray(root_mont, dtype=np.uint64).reshape(4)
+    n = len(c)
+    per = {PLAIN: 1, REP3: 6, SHAMIR: 3}[driver]
+    out = np.zeros(per * max(n, 1) * 4, dtype=np.uint64)
+    m = glib().cog16_driver_factor_roots(curve, driver, int(zerofier), c.ctypes.data_as(C.c_void_p), C.c_size_t(n), rt.ctypes.data_as(C.c_void_p),
+                                         C.c_uint64(seed), out.ctypes.data_as(C.c_void_p))
+    if m < 0:
+        raise CoSnarksHipError(glib().cog16_last_error().decode())
+    out = out[:per * m * 4]
+    return out.reshape(3, m, 2, 4) if driver == REP3 else out.reshape(3, m, 4) if driver == SHAMIR else out.reshape(m, 4)
+
+
+def driver_batched_quotient(curve: int, driver: int, polys_mont, points_mont, evals_mont, nu_mont, seed: int = 1):
+    """shplonk_batched_quotient: Q = sum_j nu^j (f_j - v_j) / (X - x_j) over the claims (f_j = polys_mont[j], x_j, v_j), as long as the
+    longest f_j. Layouts as driver_factor_roots; polynomials and evaluations are shared inside with `seed`."""
+    polys = [np.ascontiguousarray(f, dtype=np.uint64).reshape(-1, 4) for f in polys_mont]
+    k = len(polys)
+    lens = (C.c_size_t * k)(*[len(f) for f in polys])
+    flat = np.concatenate(polys) if k else np.zeros((0, 4), dtype=np.uint64)
+    pts = np.ascontiguousarray(points_mont, dtype=np.uint64).reshape(k, 4)
+    evs = np.ascontiguousarray(evals_mont, dtype=np.uint64).reshape(k, 4)
+    nu = np.ascontiguousarray(nu_mont, dtype=np.uint64).reshape(4)
+    n = max([len(f) for f in polys], default=0)
+    per = {PLAIN: 1, REP3: 6, SHAMIR: 3}[driver]
+    out = np.zeros(per * max(n, 1) * 4, dtype=np.uint64)
+    m = glib().cog16_driver_batched_quotient(curve, driver, flat.ctypes.data_as(C.c_void_p), lens, C.c_size_t(k), pts.ctypes.data_as(C.c_void_p),
+                                             evs.ctypes.data_as(C.c_void_p), nu.ctypes.data_as(C.c_void_p), C.c_uint64(seed),
+                                             out.ctypes.data_as(C.c_void_p))
+    if m < 0:
+        raise CoSnarksHipError(glib().cog16_last_error().decode())
+    out = out[:per * m * 4]
+    return out.reshape(3, m, 2, 4) if driver == REP3 else out.reshape(3, m, 4) if driver == SHAMIR else out.reshape(m, 4)
+
+
 def driver_inv_vec(curve: int, driver: int, a_mont, seed: int = 1, leaking_zeros=False, in_place=False):
     """::inv_vec, ::inv_many_in_place (in_place) or ::inv_many_in_place_leaking_zeros (leaking_zeros). Plain: (n, 4); Rep3:
     (3, n, 2, 4); Shamir (three parties, threshold 1): (3, n, 4). The strict forms raise the reference's message on a zero."""

@@ -1047,6 +1047,106 @@ int driver_eval_poly_t(int driver, const uint64_t* coeffs, size_t n, const uint6
   return 0;
 }
 
+// ::factor_roots (zerofier = 0) / Round5::div_by_zerofier(inout, 1, root) (zerofier = 1). Plain: (n - 1, 4); Rep3: [party][n - 1][component][limb];
+// Shamir (3 parties, threshold 1): [party][n - 1][limb]. The coefficients are shared inside with `seed`. Returns the length that is left.
+template <class P>
+int driver_factor_roots_t(int driver, int zerofier, const uint64_t* coeffs, size_t n, const uint64_t* root, uint64_t seed, uint64_t* out) {
+  using Fr = typename P::Fr;
+  std::vector<Fr> v(n);
+  if (n) memcpy((void*)v.data(), coeffs, 32 * n);
+  Fr x;
+  memcpy((void*)&x, root, 32);
+  auto divide = [&](auto driver_tag, auto& poly) {
+    using D = decltype(driver_tag);
+    if (zerofier) D::div_by_zerofier(poly, 1, x);
+    else D::factor_roots(poly, x);
+  };
+  if (driver == 0) {
+    divide(PlainPlonkDriver<P>(), v);
+    if (!v.empty()) memcpy(out, v.data(), 32 * v.size());
+    return (int)v.size();
+  }
+  if (driver == 1) {
+    std::vector<Rep3PrimeFieldShare<Fr>> sh[3];
+    Rep3Sharer<Fr>(seed).share(v, sh);
+    for (int p = 0; p < 3; ++p) {  // local operation: no network, no randomness
+      divide(Rep3PlonkDriver<P>(), sh[p]);
+      if (!sh[p].empty()) memcpy(out + 8 * sh[p].size() * p, sh[p].data(), 64 * sh[p].size());
+    }
+    return (int)sh[0].size();
+  }
+  const int np = 3;
+  SeededShamirSharer<Fr> sharer(seed, np);
+  std::vector<std::vector<Fr>> sh(np, std::vector<Fr>(n));
+  for (size_t i = 0; i < n; ++i) {
+    const auto s = sharer.share(v[i], 1);
+    for (int p = 0; p < np; ++p) sh[p][i] = s[p];
+  }
+  for (int p = 0; p < np; ++p) {
+    divide(ShamirPlonkDriver<P>(), sh[p]);
+    if (!sh[p].empty()) memcpy(out + 4 * sh[p].size() * p, sh[p].data(), 32 * sh[p].size());
+  }
+  return (int)sh[0].size();
+}
+
+// shplonk_batched_quotient over k claims: polys = the claim polynomials one after the other (lens[j] coefficients each), points and
+// evals k elements, nu the batching challenge. Output layouts as driver_factor_roots_t with the longest polynomial's length, which is returned;
+// polynomials and evaluations are shared inside with `seed`.
+template <class P>
+int driver_batched_quotient_t(int driver, const uint64_t* polys, const size_t* lens, size_t k, const uint64_t* points, const uint64_t* evals,
+                              const uint64_t* nu, uint64_t seed, uint64_t* out) {
+  using Fr = typename P::Fr;
+  using R3 = Rep3PrimeFieldShare<Fr>;
+  Fr nu_f;
+  memcpy((void*)&nu_f, nu, 32);
+  std::vector<OpeningClaim<Fr, Fr>> plain(k);
+  for (size_t j = 0, at = 0; j < k; at += lens[j], ++j) {
+    plain[j].polynomial.resize(lens[j]);
+    if (lens[j]) memcpy((void*)plain[j].polynomial.data(), polys + 4 * at, 32 * lens[j]);
+    memcpy((void*)&plain[j].challenge, points + 4 * j, 32);
+    memcpy((void*)&plain[j].evaluation, evals + 4 * j, 32);
+  }
+  if (driver == 0) {
+    const std::vector<Fr> q = shplonk_batched_quotient<P, Fr>(plain, nu_f);
+    if (!q.empty()) memcpy(out, q.data(), 32 * q.size());
+    return (int)q.size();
+  }
+  if (driver == 1) {
+    std::vector<OpeningClaim<Fr, R3>> cl[3];
+    Rep3Sharer<Fr> sharer(seed);
+    for (size_t j = 0; j < k; ++j) {
+      std::vector<R3> f[3], e[3];
+      sharer.share(plain[j].polynomial, f);
+      sharer.share({plain[j].evaluation}, e);
+      for (int p = 0; p < 3; ++p) cl[p].push_back({std::move(f[p]), plain[j].challenge, e[p][0]});
+    }
+    size_t len = 0;
+    for (int p = 0; p < 3; ++p) {
+      const std::vector<R3> q = shplonk_batched_quotient<P, R3>(cl[p], nu_f);
+      len = q.size();
+      if (len) memcpy(out + 8 * len * p, q.data(), 64 * len);
+    }
+    return (int)len;
+  }
+  const int np = 3;
+  SeededShamirSharer<Fr> sharer(seed, np);
+  std::vector<OpeningClaim<Fr, Fr>> cl[3];
+  for (size_t j = 0; j < k; ++j) {
+    for (int p = 0; p < np; ++p) cl[p].push_back({std::vector<Fr>(lens[j]), plain[j].challenge, Fr::zero()});
+    for (size_t i = 0; i <= lens[j]; ++i) {  // the last round shares the evaluation
+      const auto s = sharer.share(i < lens[j] ? plain[j].polynomial[i] : plain[j].evaluation, 1);
+      for (int p = 0; p < np; ++p) (i < lens[j] ? cl[p][j].polynomial[i] : cl[p][j].evaluation) = s[p];
+    }
+  }
+  size_t len = 0;
+  for (int p = 0; p < np; ++p) {
+    const std::vector<Fr> q = shplonk_batched_quotient<P, Fr>(cl[p], nu_f);
+    len = q.size();
+    if (len) memcpy(out + 4 * len * p, q.data(), 32 * len);
+  }
+  return (int)len;
+}
+
 // ::inv_vec (leaking_zeros = 0), ::inv_many_in_place_leaking_zeros (1) and ::inv_many_in_place (2: inv_vec's protocol, the noir
 // drivers' name and message). Plain: (n, 4); Rep3: [party][n][component][limb]; Shamir (3 parties, threshold 1):
 // [party][n][limb]. The values are shared inside with `seed`; a dealer hands the Shamir parties their double sharings.
@@ -1460,6 +1560,29 @@ int cog16_driver_eval_poly(int curve, int driver, const uint64_t* coeffs, size_t
   try {
     if (curve == 0) return driver_eval_poly_t<Bn254>(driver, coeffs, n, point, seed, out);
     if (curve == 1) return driver_eval_poly_t<Bls12_381>(driver, coeffs, n, point, seed, out);
+    g_err = "unknown curve";
+    return -1;
+  } catch (const std::exception& e) {
+    g_err = e.what();
+    return -1;
+  }
+}
+int cog16_driver_factor_roots(int curve, int driver, int zerofier, const uint64_t* coeffs, size_t n, const uint64_t* root, uint64_t seed, uint64_t* out) {
+  try {
+    if (curve == 0) return driver_factor_roots_t<Bn254>(driver, zerofier, coeffs, n, root, seed, out);
+    if (curve == 1) return driver_factor_roots_t<Bls12_381>(driver, zerofier, coeffs, n, root, seed, out);
+    g_err = "unknown curve";
+    return -1;
+  } catch (const std::exception& e) {
+    g_err = e.what();
+    return -1;
+  }
+}
+int cog16_driver_batched_quotient(int curve, int driver, const uint64_t* polys, const size_t* lens, size_t k, const uint64_t* points,
+                                  const uint64_t* evals, const uint64_t* nu, uint64_t seed, uint64_t* out) {
+  try {
+    if (curve == 0) return driver_batched_quotient_t<Bn254>(driver, polys, lens, k, points, evals, nu, seed, out);
+    if (curve == 1) return driver_batched_quotient_t<Bls12_381>(driver, polys, lens, k, points, evals, nu, seed, out);
     g_err = "unknown curve";
     return -1;
   } catch (const std::exception& e) {

@@ -6,8 +6,10 @@
 //       impls mpc/{plain.rs:271, rep3.rs:258-288, shamir.rs:255}, HonkCurve::fast_msm (honk_curve.rs:35, 81-83, 175-177)
 //   CircomPlonkProver::{evaluate_poly_public, inv_vec, array_prod_mul (plain driver)}   co-plonk/src/mpc.rs, round2.rs:164-165, round4.rs:126-132
 //   NoirUltraHonkProver::{eval_poly, inv_many_in_place, inv_many_in_place_leaking_zeros}  co-noir-common/src/mpc/rep3.rs:208-257, rep3/poly.rs:39-68
+//   Polynomial / SharedPolynomial::factor_roots, compute_batched_quotient, Round5::div_by_zerofier(.., 1, beta)
+//       co-noir-common/src/polynomials/polynomial.rs:183, shared_polynomial.rs:92-140, co_shplemini_prover.rs:661-737, co-plonk/src/round5.rs:78-91
 // These data-parallel methods are mirrored, the whole-vector scans among them (running product, batch inverse, polynomial
-// evaluation: csh_vec_prefix_prod / csh_vec_batch_inverse / csh_eval_poly). The PLONK rounds / sumcheck / relations above them are
+// evaluation, division by (X - z): csh_vec_prefix_prod / csh_vec_batch_inverse / csh_eval_poly / csh_poly_div_linear). The PLONK rounds / sumcheck / relations above them are
 // control logic and stay in the Rust host (SURVEY.md 8 "out of scope"). NOT mirrored: the Rep3 / Shamir array_prod_mul
 // (co-plonk/src/mpc/rep3.rs:187-260), which is four network multiplication rounds around the same running product -- its opened
 // vector would go through csh_vec_prefix_prod exactly as the plain driver's does below.
@@ -114,6 +116,34 @@ inline Share eval_poly(const std::vector<Share>& coeffs, const typename P::Fr& p
   check(csh_eval_poly(P::ID, (const uint64_t*)coeffs.data(), coeffs.size(), ncomp, (const uint64_t*)&point, (uint64_t*)&out), "csh_eval_poly");
   return out;
 }
+// p(X) / (X - root) in place, the popped last element dropped as the reference drops it (Polynomial::factor_roots, polynomial.rs:183;
+// SharedPolynomial::factor_roots, shared_polynomial.rs:92-140: linear, so every component of a share alike). root == 0: remove(0).
+template <class P, class Share>
+inline void factor_roots(std::vector<Share>& coeffs, const typename P::Fr& root) {
+  if (coeffs.empty()) throw Error("factor_roots: empty polynomial");
+  if (root.is_zero()) {
+    coeffs.erase(coeffs.begin());
+    return;
+  }
+  constexpr uint32_t ncomp = sizeof(Share) / sizeof(typename P::Fr);
+  uint64_t* v = (uint64_t*)coeffs.data();
+  check(csh_poly_div_linear(P::ID, v, coeffs.size(), ncomp, (const uint64_t*)&root, nullptr, v, nullptr), "csh_poly_div_linear");
+  coeffs.pop_back();
+}
+// Round5::div_by_zerofier (co-plonk/src/round5.rs:78-91): the same recurrence with c = -beta^-1; the reference calls it with n = 1 only
+template <class P, class Share>
+inline void div_by_zerofier(std::vector<Share>& inout, size_t n, const typename P::Fr& beta) {
+  if (n != 1) throw Error("div_by_zerofier: only n = 1 (X - beta) is built");
+  if (beta.is_zero()) throw Error("Highly unlikely to be zero");
+  factor_roots<P, Share>(inout, beta);
+}
+struct DeviceMem {  // csh_malloc / csh_free
+  void* p = nullptr;
+  explicit DeviceMem(size_t bytes) { check(csh_malloc(&p, bytes ? bytes : 1), "csh_malloc"); }
+  DeviceMem(const DeviceMem&) = delete;
+  DeviceMem& operator=(const DeviceMem&) = delete;
+  ~DeviceMem() { csh_free(p); }
+};
 // y[i] <- y[i]^-1 with ONE field inversion (zeros stay zero); returns how many zeros there were
 template <class P>
 inline size_t batch_inverse(std::vector<typename P::Fr>& y) {
@@ -133,6 +163,41 @@ inline std::vector<Share> unmask_inverse(std::vector<Share> r, std::vector<typen
   return r;
 }
 }  // namespace detail
+
+// ShpleminiOpeningClaim as compute_batched_quotient reads it: f_j(X), the point x_j and (the share of) the evaluation v_j
+template <class Fr, class Share>
+struct OpeningClaim {
+  std::vector<Share> polynomial;
+  Fr challenge;
+  Share evaluation;
+};
+// Q(X) = sum_j nu^j (f_j(X) - v_j) / (X - x_j) (compute_batched_quotient, co_shplemini_prover.rs:661-737; shplemini_prover.rs:594):
+// every claim polynomial goes up once, its quotient is accumulated into the device-resident Q as it is formed (q.add_scaled(&tmp, &nu)
+// without tmp), and Q comes back once. As long as the longest polynomial, like the reference's new_zero(max_poly_size).
+template <class P, class Share>
+inline std::vector<Share> shplonk_batched_quotient(const std::vector<OpeningClaim<typename P::Fr, Share>>& claims, const typename P::Fr& nu) {
+  using Fr = typename P::Fr;
+  constexpr uint32_t ncomp = sizeof(Share) / sizeof(Fr);
+  size_t max_poly_size = 0;
+  for (const auto& c : claims) max_poly_size = std::max(max_poly_size, c.polynomial.size());
+  std::vector<Share> q(max_poly_size);  // value-initialised: zero
+  if (max_poly_size == 0) return q;
+  const size_t bytes = sizeof(Share) * max_poly_size;
+  detail::DeviceMem dq(bytes), df(bytes);
+  check(csh_memcpy_h2d(dq.p, q.data(), bytes), "csh_memcpy_h2d");
+  Fr current_nu = Fr::one();
+  for (const auto& c : claims) {
+    if (c.challenge.is_zero()) throw Error("shplonk_batched_quotient: opening point 0");
+    check(csh_sync(nullptr), "csh_sync");  // the previous claim's kernels are done with df
+    check(csh_memcpy_h2d(df.p, c.polynomial.data(), sizeof(Share) * c.polynomial.size()), "csh_memcpy_h2d");
+    check(csh_poly_div_linear_dev(P::ID, (const uint64_t*)df.p, c.polynomial.size(), ncomp, (const uint64_t*)&c.challenge,
+                                  (const uint64_t*)&c.evaluation, (const uint64_t*)&current_nu, 1, (uint64_t*)dq.p, nullptr, nullptr),
+          "csh_poly_div_linear_dev");
+    current_nu = Fr::mul(current_nu, nu);
+  }
+  check(csh_memcpy_d2h(q.data(), dq.p, bytes), "csh_memcpy_d2h");
+  return q;
+}
 
 template <class F>
 struct Rep3PointShare {  // mpc-core/src/protocols/rep3/pointshare/types.rs:5-11
@@ -185,6 +250,9 @@ struct PlainPlonkDriver {
     return {e, std::move(coeffs)};
   }
   static Fr eval_poly(const std::vector<Fr>& coeffs, const Fr& point) { return detail::eval_poly<P, Fr>(coeffs, point); }
+  // Polynomial::factor_roots (polynomial.rs:183) and Round5::div_by_zerofier(inout, 1, beta) (co-plonk round5.rs:78-91)
+  static void factor_roots(std::vector<Fr>& coeffs, const Fr& root) { detail::factor_roots<P, Fr>(coeffs, root); }
+  static void div_by_zerofier(std::vector<Fr>& inout, size_t n, const Fr& beta) { detail::div_by_zerofier<P, Fr>(inout, n, beta); }
   // co-plonk plain.rs:127-140 / co-noir plain.rs:240-252: every element's own inverse() there
   static std::vector<Fr> inv_vec(std::vector<Fr> a) {
     if (detail::batch_inverse<P>(a)) throw Error("Cannot invert zero");
@@ -252,6 +320,9 @@ struct Rep3PlonkDriver {
     return {e, std::move(coeffs)};
   }
   static ArithmeticShare eval_poly(const std::vector<ArithmeticShare>& coeffs, const Fr& point) { return detail::eval_poly<P, ArithmeticShare>(coeffs, point); }
+  // SharedPolynomial::factor_roots (shared_polynomial.rs:92-140) / div_by_zerofier on {a, b} shares: linear, no network
+  static void factor_roots(std::vector<ArithmeticShare>& coeffs, const Fr& root) { detail::factor_roots<P, ArithmeticShare>(coeffs, root); }
+  static void div_by_zerofier(std::vector<ArithmeticShare>& inout, size_t n, const Fr& beta) { detail::div_by_zerofier<P, ArithmeticShare>(inout, n, beta); }
   // arithmetic::mul_open_vec (rep3/arithmetic.rs:342-354): masked local products, broadcast, sum of the three
   static std::vector<Fr> mul_open_vec(const std::vector<ArithmeticShare>& a, const std::vector<ArithmeticShare>& b, const LocalNetwork& net, State& st) {
     const std::vector<Fr> mine = local_mul_vec(a, b, st);
@@ -312,6 +383,9 @@ struct ShamirPlonkDriver {
     return {e, std::move(coeffs)};
   }
   static Fr eval_poly(const std::vector<Fr>& coeffs, const Fr& point) { return detail::eval_poly<P, Fr>(coeffs, point); }
+  // SharedPolynomial::factor_roots (shared_polynomial.rs:92-140) / div_by_zerofier on Shamir shares: linear, no network
+  static void factor_roots(std::vector<Fr>& coeffs, const Fr& root) { detail::factor_roots<P, Fr>(coeffs, root); }
+  static void div_by_zerofier(std::vector<Fr>& inout, size_t n, const Fr& beta) { detail::div_by_zerofier<P, Fr>(inout, n, beta); }
   // arithmetic::mul_open_vec (shamir/arithmetic.rs:262-290): degree-2t products, broadcast_next(n, 2t + 1) (network.rs:96-126),
   // reconstruction with open_lagrange_2t
   static std::vector<Fr> mul_open_vec(const std::vector<Fr>& a, const std::vector<Fr>& b, const LocalNetwork& net, ShamirState<Fr>& st) {

@@ -310,7 +310,7 @@ int csh_rep3_to_shamir_vec(csh_curve_t field_of, const uint64_t* in_ab, const ui
 int csh_lincomb(csh_curve_t field_of, const uint64_t* const* shares, const uint64_t* coeffs /* k*4 */,
                 size_t k, uint64_t* out, size_t n);
 
-/* ---- field scans: running product, batch inverse, polynomial evaluation -------------------------------
+/* ---- field scans: running product, batch inverse, polynomial evaluation, division by (X - z) -------------
  * The whole-vector steps between two transforms of a PLONK / UltraHonk proof that are a scan or a reduction, not element-wise.
  * `field_of`, the limbs, `ncomp` and `stream` as above; n = 0 .. 2^28 (the reference's largest domain). The _dev forms are
  * stream-ordered: no host synchronisation, scratch from the stream's workspace. Outputs are canonical. tune keys "scan_lane_run"
@@ -333,6 +333,24 @@ int csh_vec_batch_inverse(csh_curve_t field_of, const uint64_t* in, uint64_t* ou
  * n == 0 gives 0, point == 0 gives coeffs[0]. `point` is read on the host during the call. */
 int csh_eval_poly_dev(csh_curve_t field_of, const uint64_t* coeffs_dev, size_t n, uint32_t ncomp, const uint64_t point[4], uint64_t* out_dev, void* stream);
 int csh_eval_poly(csh_curve_t field_of, const uint64_t* coeffs, size_t n, uint32_t ncomp, const uint64_t point[4], uint64_t* out);
+/* Division by (X - root), the reference's recurrence from the low coefficients up: c = (-root)^-1, b_(-1) = 0, b_i = c (in[i] - b_(i-1));
+ * out = b_0 .. b_(n-2) (n - 1 coefficients x ncomp), rem[c] = b_(n-1) = -root^-n p(root), the element the reference pops: 0 exactly when
+ * the division is exact (the reference never checks; Horner from the top agrees with this only then). Polynomial::factor_roots
+ * (co-noir/co-noir-common/src/polynomials/polynomial.rs:183) and SharedPolynomial::factor_roots (shared_polynomial.rs:92-140) as the KZG
+ * opening (co-noir-common/src/lib.rs:43-47, 68-73) and the Shplonk batched quotient (co_shplemini_prover.rs:661-737,
+ * shplemini_prover.rs:594) call them; Round5::div_by_zerofier(inout, 1, beta) for W_xi and W_xiw (co-circom/co-plonk/src/round5.rs:78-91,
+ * called at :255 and :274), the same recurrence with c = -beta^-1. Linear, so it acts on every component of a share with no network
+ * round. `root` and `sub0` are read on the host during the call. sub0 (ncomp elements, may be NULL) is taken off coefficient 0 as it
+ * is loaded -- every call site does quotient[0] -= evaluation first --, `in` itself is not modified. scale (one element, NULL = 1) and
+ * accumulate: out[i] = scale b_i, or out[i] += scale b_i (Shplonk's q.add_scaled(&tmp, &nu) without the quotient ever being stored);
+ * only out[0 .. n-1) is touched. out may equal in unless accumulating (CSH_ERR_INVALID). rem(_dev) may be NULL. n == 0: nothing, rem =
+ * 0; n == 1: no out, rem = c (in[0] - sub0). root == 0 is CSH_ERR_INVALID: that quotient is a shift of the coefficients
+ * (factor_roots does remove(0)), which the caller does itself. NOT built: div_by_zerofier with a stride n > 1 (X^n - beta); the
+ * reference only ever passes 1. */
+int csh_poly_div_linear_dev(csh_curve_t field_of, const uint64_t* in_dev, size_t n, uint32_t ncomp, const uint64_t root[4], const uint64_t* sub0,
+                            const uint64_t* scale, int accumulate, uint64_t* out_dev, uint64_t* rem_dev, void* stream);
+int csh_poly_div_linear(csh_curve_t field_of, const uint64_t* in, size_t n, uint32_t ncomp, const uint64_t root[4], const uint64_t* sub0,
+                        uint64_t* out, uint64_t* rem);
 
 /* Rep3 correlated masks generated on the device ("next" row f2): out[i] = from_be_bytes_mod_order(a_i) -
  * from_be_bytes_mod_order(b_i), a_i / b_i = the 32-byte chunks number elem_offset{1,2} + i of the ChaCha12 keystreams

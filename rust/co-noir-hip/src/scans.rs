@@ -33,3 +33,20 @@ pub fn hip_prefix_product<F: PrimeField>(field: i32, v: &mut [F]) {
     let p = limbs_mut(v);
     hip_ok(unsafe { sys::csh_vec_prefix_prod(field, p as *const u64, p, n) });
 }
+
+/// `Polynomial::factor_roots` / `SharedPolynomial::factor_roots` (co-noir-common/src/polynomials/polynomial.rs:183,
+/// shared_polynomial.rs:92-140): p(X) / (X - root) in place, in the reference's direction -- b_i = (-root)^-1 (a_i - b_(i-1)), the last
+/// element popped -- on every component of the share. `sub0`, when given, is taken off coefficient 0 on the way in (every call site
+/// does `tmp[0] -= evaluation` first: lib.rs:43-47, co_shplemini_prover.rs:661-737). Root 0 is the shift, as there.
+pub fn hip_factor_roots<F: PrimeField, S: Copy + Default>(field: i32, coeffs: &mut Vec<S>, root: F, sub0: Option<S>) {
+    if root.is_zero() {
+        coeffs.remove(0);
+        return;
+    }
+    let n = coeffs.len();
+    let rt: *const F = &root;
+    let s0: *const u64 = sub0.as_ref().map_or(std::ptr::null(), |s| (s as *const S).cast());
+    let p = limbs_mut(coeffs);
+    hip_ok(unsafe { sys::csh_poly_div_linear(field, p as *const u64, n, ncomp::<S>(), rt.cast(), s0, p, std::ptr::null_mut()) });
+    coeffs.pop();
+}

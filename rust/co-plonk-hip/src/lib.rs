@@ -11,4 +11,4 @@ mod cold;
 pub mod drivers;
 pub use drivers::{HipPlainPlonkDriver, HipRep3PlonkDriver, HipShamirPlonkDriver};
 pub mod scans;
-pub use scans::{hip_batch_inverse, hip_eval_poly, hip_prefix_product};
+pub use scans::{hip_batch_inverse, hip_eval_poly, hip_prefix_product, hip_div_by_zerofier};

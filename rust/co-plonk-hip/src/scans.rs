@@ -33,3 +33,13 @@ pub fn hip_prefix_product<F: PrimeField>(field: i32, v: &mut [F]) {
     let p = limbs_mut(v);
     hip_ok(unsafe { sys::csh_vec_prefix_prod(field, p as *const u64, p, n) });
 }
+
+/// `Round5::div_by_zerofier(inout, 1, beta)` (co-plonk/src/round5.rs:78-91, called for W_xi and W_xiw at :255 and :274): the serial
+/// `inout[i] = (inout[i - 1] - inout[i]) / beta` loop and the final resize, on every component of the share. Only n = 1 exists.
+pub fn hip_div_by_zerofier<F: PrimeField, S: Copy + Default>(field: i32, inout: &mut Vec<S>, beta: F) {
+    let n = inout.len();
+    let rt: *const F = &beta;
+    let p = limbs_mut(inout);
+    hip_ok(unsafe { sys::csh_poly_div_linear(field, p as *const u64, n, ncomp::<S>(), rt.cast(), std::ptr::null(), p, std::ptr::null_mut()) });
+    inout.pop();
+}

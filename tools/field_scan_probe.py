@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Device times of the field scans (csrc/field_scan.hip) on BN254 Fr: running product, batch inverse, polynomial evaluation (one and two
-components), with csh_vec_mul_dev at the same size in the same process as the yardstick (one multiplication, 96 B per element), and the
+"""Device times of the field scans (csrc/field_scan.hip) on BN254 Fr: running product, batch inverse, polynomial evaluation and division
+by (X - r) (one and two components each), with csh_vec_mul_dev at the same size in the same process as the yardstick (one multiplication, 96 B per element), and the
 batch inverse at n = 1, which is the latency of its single inversion plus three launches.
 
     python tools/field_scan_probe.py [--log FILE]
@@ -82,6 +82,7 @@ for lg in [int(x) for x in args.sizes.split(",")]:
     a = hip.DeviceBuffer.from_host(limbs(rs, 2 * n))     # 2 n: the two-component polynomial
     b = hip.DeviceBuffer.from_host(limbs(rs, n))
     o = hip.DeviceBuffer(32 * n)
+    q = hip.DeviceBuffer(64 * n)                         # the two-component quotient, out of place: `a` stays what it is
     e = hip.DeviceBuffer(64)
     cn = C.c_size_t(n)
     ops = [
@@ -90,10 +91,12 @@ for lg in [int(x) for x in args.sizes.split(",")]:
         ("vec_batch_inverse", lambda: B._check(L.csh_vec_batch_inverse_dev(0, a.ptr, o.ptr, cn, None, None))),
         ("eval_poly ncomp=1", lambda: B._check(L.csh_eval_poly_dev(0, a.ptr, cn, 1, point.ctypes.data_as(C.c_void_p), e.ptr, None))),
         ("eval_poly ncomp=2", lambda: B._check(L.csh_eval_poly_dev(0, a.ptr, cn, 2, point.ctypes.data_as(C.c_void_p), e.ptr, None))),
+        ("poly_div_linear ncomp=1", lambda: B._check(L.csh_poly_div_linear_dev(0, a.ptr, cn, 1, point.ctypes.data_as(C.c_void_p), None, None, 0, q.ptr, e.ptr, None))),
+        ("poly_div_linear ncomp=2", lambda: B._check(L.csh_poly_div_linear_dev(0, a.ptr, cn, 2, point.ctypes.data_as(C.c_void_p), None, None, 0, q.ptr, e.ptr, None))),
     ]
     for name, fn in ops:
         emit(name, n, measure(fn, reps))
-    for buf in (a, b, o, e):
+    for buf in (a, b, o, q, e):
         buf.free()
 one = hip.DeviceBuffer.from_host(limbs(rs, 1))
 out1 = hip.DeviceBuffer(32)
@@ -101,6 +104,12 @@ emit("vec_batch_inverse", 1, measure(lambda: B._check(L.csh_vec_batch_inverse_de
      note="one inversion (a chain of ~330 dependent multiplications on one lane) + three launches")
 emit("vec_prefix_prod", 1, measure(lambda: B._check(L.csh_vec_prefix_prod_dev(0, one.ptr, out1.ptr, C.c_size_t(1), None)), 50),
      note="three launches, no inversion: the difference to the line above is the inversion")
+two = hip.DeviceBuffer.from_host(limbs(rs, 2))
+rem1 = hip.DeviceBuffer(64)
+for ncomp in (1, 2):
+    emit("poly_div_linear ncomp=%d" % ncomp, 1, measure(lambda: B._check(L.csh_poly_div_linear_dev(
+        0, two.ptr, C.c_size_t(1), ncomp, point.ctypes.data_as(C.c_void_p), None, None, 0, None, rem1.ptr, None)), 50),
+        note="one host inversion and ~30 host squarings + three launches")
 if args.log:
     with open(args.log, "a") as f:
         for line in lines:
