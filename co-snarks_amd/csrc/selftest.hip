@@ -14,6 +14,7 @@
 #include "field29.hpp"
 #include "field_scan.hpp"
 #include "msm_digits.hpp"
+#include "vec_elem.hpp"
 
 using namespace csh;
 
@@ -225,24 +226,27 @@ static int lazy_fr_chain_t(const uint64_t a[4], const uint64_t b[4], const uint6
   return CSH_OK;
 }
 
-// Host run of the share-vector kernels' lazy products (vec_ops.hip): op 0: a*b; op 1: a*(c+d) + b*c + m (Rep3 local
-// multiplication with la = a, lb = b, ra = c, rb = d, mask m). All arkworks-Montgomery in and out.
-template <class LZ, class F>
-static int lazy_vec_t(int op, const uint64_t* a, const uint64_t* b, const uint64_t* c, const uint64_t* d, const uint64_t* m, uint64_t* out) {
-  F fa, fb, fc, fd, fm;
+// Host run of the share-vector kernels' per-element expressions: the functions of vec_elem.hpp that the kernels of vec_ops.hip call, with
+// the limb-bound contract checked. op 0: a*b; 1: a*(c+d) + b*c + m (Rep3 local multiplication with la = a, lb = b, ra = c, rb = d, mask m);
+// 2: a*b - c; 3: as 1 with the mask optional (m may be NULL) minus s (may be NULL); 4: a*c + b*d (Rep3 share {a, b} to Shamir with the
+// translation points x = c, y = d). All arkworks-Montgomery in and out.
+template <class F>
+static int lazy_vec_t(int op, const uint64_t* a, const uint64_t* b, const uint64_t* c, const uint64_t* d, const uint64_t* m, const uint64_t* s, uint64_t* out) {
+  if (op < 0 || op > 4 || !a || !b || !c || !out || (op != 0 && op != 2 && !d) || (op == 1 && !m)) return CSH_ERR_INVALID;
+  F fa, fb, fc, fd = F::zero(), fm = F::zero(), fs = F::zero();
   memcpy(&fa, a, 32);
   memcpy(&fb, b, 32);
   memcpy(&fc, c, 32);
-  memcpy(&fd, d, 32);
-  memcpy(&fm, m, 32);
+  if (d) memcpy(&fd, d, 32);
+  if (m) memcpy(&fm, m, 32);
+  if (op == 3 && s) memcpy(&fs, s, 32);
   F r;
-  if (op == 0) {
-    r = LZ::mul(LZ::unpack(fa), LZ::unpack(fb).times32()).canonical_wide().pack();
-  } else {
-    const LZ xa = LZ::unpack(fa), xb = LZ::unpack(fb), ya = LZ::unpack(fc), yb = LZ::unpack(fd);
-    LZ t = LZ::reduce(LZ::mul_add_wide(xa, LZ::add(ya, yb).times32(), xb, ya.times32()));
-    t = LZ::add(t, LZ::unpack(fm));
-    r = t.canonical_wide().pack();
+  switch (op) {
+    case 0: r = elem_mul(fa, fb); break;
+    case 1: r = elem_rep3_local_mul(fa, fb, fc, fd, &fm, (const F*)nullptr, 0); break;
+    case 2: r = elem_mul_sub(fa, fb, fc); break;
+    case 3: r = elem_rep3_local_mul(fa, fb, fc, fd, m ? &fm : nullptr, s ? &fs : nullptr, 0); break;
+    default: r = elem_rep3_to_shamir(fa, fb, fc, fd); break;
   }
   memcpy(out, &r, 32);
   return CSH_OK;
@@ -527,11 +531,12 @@ int csh_selftest_lazy_fr_chain(int field_of, const uint64_t a[4], const uint64_t
   return CSH_ERR_INVALID;
 }
 
+// s (the `sub` operand of op 3) comes last: ops 0 and 1 keep their numbers, their meaning and their arguments
 int csh_selftest_lazy_vec(int field_of, int op, const uint64_t* a, const uint64_t* b, const uint64_t* c, const uint64_t* d, const uint64_t* m,
-                          uint64_t* out) {
-  if (field_of == CSH_BN254) return lazy_vec_t<Fr29s, Bn254Fr>(op, a, b, c, d, m, out);
-  if (field_of == CSH_BLS12_381) return lazy_vec_t<Bls381Fr29s, Bls381Fr>(op, a, b, c, d, m, out);
-  if (field_of == CSH_BLS12_377) return lazy_vec_t<Bls377Fr29s, Bls377Fr>(op, a, b, c, d, m, out);
+                          uint64_t* out, const uint64_t* s) {
+  if (field_of == CSH_BN254) return lazy_vec_t<Bn254Fr>(op, a, b, c, d, m, s, out);
+  if (field_of == CSH_BLS12_381) return lazy_vec_t<Bls381Fr>(op, a, b, c, d, m, s, out);
+  if (field_of == CSH_BLS12_377) return lazy_vec_t<Bls377Fr>(op, a, b, c, d, m, s, out);
   return CSH_ERR_INVALID;
 }
 

@@ -1,6 +1,7 @@
 // Device-executed self-test hooks for the arithmetic that exists on the device only: curve_quad.hpp (one XYZZ point over a DPP
 // quad) and curve_pair.hpp (one Fp2 value over a lane pair), plus a launcher of the real window-reduction and fold-tree kernels
-// on bucket arrays the caller chooses. The kernels here are compiled with the device form of the limb-bound contract
+// on bucket arrays the caller chooses, and host-pointer entry points around the two fused launchers that end a witness map
+// (vec_ops.hip), which the C ABI reaches only through csh_groth16_h_dev. The kernels here are compiled with the device form of the limb-bound contract
 // (field29.hpp, CSH_CHECK_BOUNDS_DEVICE): a violated operand bound is counted in g_bound_record, never trapped; every entry
 // point hands the record back and clears it. Test infrastructure; not declared in include/cosnarks_hip.h.
 #define CSH_CHECK_BOUNDS_DEVICE 1
@@ -354,6 +355,38 @@ int msm_tail_t(int form, const void* affine_pts, const uint8_t* neg, size_t npts
   return msm_tail_selftest_t<Cfg>(dense.data(), NB, S, form, out_xyzz);
 }
 
+// ---- the two fused forms a witness map ends with (vec_ops.hip: vec_mul_sub_dev, rep3_local_mul_sub_dev) ----------------------------------
+// Host pointers in and out around the product launcher `launch(subtrahend, out, stream)`: no kernel of its own. alias: the subtrahend is
+// uploaded into the output buffer and the launcher is handed that buffer for both, as csh_groth16_h_dev does; otherwise the output
+// buffer starts as 0xFF bytes (no field element), so an element the kernel skips shows.
+template <class Launch>
+int fused_form(const uint64_t* subtrahend, uint64_t* out, size_t n, int alias, Launch launch) {
+  if (n == 0) return CSH_OK;
+  const size_t eb = 32 * n;
+  DevMem dsub, dout;
+  CSH_TRY(dout.alloc(eb));
+  if (alias) {
+    CSH_HIP(hipMemcpy(dout.p, subtrahend, eb, hipMemcpyHostToDevice));
+  } else {
+    CSH_HIP(hipMemset(dout.p, 0xFF, eb));
+    if (subtrahend) {
+      CSH_TRY(dsub.alloc(eb));
+      CSH_HIP(hipMemcpy(dsub.p, subtrahend, eb, hipMemcpyHostToDevice));
+    }
+  }
+  CSH_HIP(hipDeviceSynchronize());  // the fill above ran on the null stream, the launcher runs on the thread's own
+  hipStream_t st = resolve_stream(nullptr);
+  CSH_TRY(launch(alias ? dout.as<uint64_t>() : dsub.as<uint64_t>(), dout.as<uint64_t>(), st));
+  CSH_HIP(hipStreamSynchronize(st));
+  CSH_HIP(hipMemcpy(out, dout.p, eb, hipMemcpyDeviceToHost));
+  return CSH_OK;
+}
+int upload_operand(DevMem& d, const uint64_t* host, size_t bytes) {
+  CSH_TRY(d.alloc(bytes));
+  CSH_HIP(hipMemcpy(d.p, host, bytes, hipMemcpyHostToDevice));
+  return CSH_OK;
+}
+
 }  // namespace
 
 #define ST_GROUP_DISPATCH(curve, group, CALL)                                                                                                   \
@@ -413,6 +446,38 @@ int csh_selftest_msm_tail_dev(int curve, int group, int form, const void* affine
                               const uint32_t* bucket_off, size_t nocc, uint32_t NB, uint32_t S, void* out_xyzz) {
   CSH_TRY(ensure_device());
   ST_GROUP_DISPATCH(curve, group, (msm_tail_t<Cfg>(form, affine_pts, neg, npts, bucket_ids, bucket_off, nocc, NB, S, out_xyzz)));
+}
+
+// out = a * b - c through csh::vec_mul_sub_dev (k_vec_mul_sub), n elements, host pointers. c_aliases_out: c travels in the output buffer.
+int csh_selftest_vec_mul_sub_dev(int curve, const uint64_t* a, const uint64_t* b, const uint64_t* c, uint64_t* out, size_t n, int c_aliases_out) {
+  CSH_REQUIRE((a && b && c && out) || n == 0, "selftest_vec_mul_sub: NULL argument");
+  CSH_TRY(ensure_device());
+  DevMem da, db;
+  if (n) {
+    CSH_TRY(upload_operand(da, a, 32 * n));
+    CSH_TRY(upload_operand(db, b, 32 * n));
+  }
+  return fused_form(c, out, n, c_aliases_out, [&](const uint64_t* dc, uint64_t* dout, hipStream_t st) {
+    return vec_mul_sub_dev((csh_curve_t)curve, da.as<uint64_t>(), db.as<uint64_t>(), dc, dout, n, st);
+  });
+}
+
+// out = rep3_local_mul(lhs, rhs) + mask - sub through csh::rep3_local_mul_sub_dev (k_rep3_local_mul), n shares {a, b} per side, host
+// pointers. mask and sub may be NULL (the kernel takes either as absent); sub_aliases_out: sub travels in the output buffer.
+int csh_selftest_rep3_local_mul_sub_dev(int curve, const uint64_t* lhs, const uint64_t* rhs, const uint64_t* mask, const uint64_t* sub, uint64_t* out, size_t n,
+                                        int sub_aliases_out) {
+  CSH_REQUIRE((lhs && rhs && out) || n == 0, "selftest_rep3_local_mul_sub: NULL argument");
+  CSH_REQUIRE(sub || !sub_aliases_out, "selftest_rep3_local_mul_sub: no sub operand to put into the output buffer");
+  CSH_TRY(ensure_device());
+  DevMem dl, dr, dm;
+  if (n) {
+    CSH_TRY(upload_operand(dl, lhs, 64 * n));
+    CSH_TRY(upload_operand(dr, rhs, 64 * n));
+    if (mask) CSH_TRY(upload_operand(dm, mask, 32 * n));
+  }
+  return fused_form(sub, out, n, sub_aliases_out, [&](const uint64_t* ds, uint64_t* dout, hipStream_t st) {
+    return rep3_local_mul_sub_dev((csh_curve_t)curve, dl.as<uint64_t>(), dr.as<uint64_t>(), dm.as<uint64_t>(), ds, dout, n, st);
+  });
 }
 
 }  // extern "C"

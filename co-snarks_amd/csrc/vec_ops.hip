@@ -1,12 +1,14 @@
 // Element-wise secret-shared field arithmetic (Rep3 / Shamir / plain) on gfx950.
 // HBM-bound streaming kernels: one 32-byte field element per lane per step, 2 x 16-byte accesses,
 // grid-stride over <= 65536 workgroups of 256 threads. See DESIGN.md section "share-vector kernels".
+// The per-element expressions live in vec_elem.hpp, shared with the host self-test.
 // Products run in the signed lazy 9 x 29-bit field (field29.hpp): operands are re-sliced as they are, one of them is
 // scaled by 2^5 = R'/2^256 so the lazy Montgomery product is the arkworks one; 162 multiply-adds instead of a 32-bit CIOS
 // product with its carry chains, which keeps these kernels on the HBM side of the roofline.
 #include "common.hpp"
 #include "field.hpp"
 #include "field29.hpp"
+#include "vec_elem.hpp"
 #include "chacha.hpp"
 #include <stdlib.h>
 #include <string.h>
@@ -23,16 +25,14 @@ static int vec_grid(size_t n) {
 template <class F>
 __global__ __launch_bounds__(VB) void k_vec_mul(const F* __restrict__ a, const F* __restrict__ b, F* out, size_t n) {
   for (size_t i = blockIdx.x * (size_t)VB + threadIdx.x; i < n; i += (size_t)gridDim.x * VB) {
-    using LZ = typename LazyOf<F>::type;
-    out[i] = LZ::mul(LZ::unpack(a[i]), LZ::unpack(b[i]).times32()).canonical_wide().pack();
+    out[i] = elem_mul(a[i], b[i]);
   }
 }
-// out = a * b - c in one sweep (h = a b - c, reduction.rs:176-190): the difference is limb-wise on the reduced product
+// out = a * b - c in one sweep (h = a b - c, reduction.rs:176-190)
 template <class F>
 __global__ __launch_bounds__(VB) void k_vec_mul_sub(const F* __restrict__ a, const F* __restrict__ b, const F* c /* may alias out */, F* out, size_t n) {
   for (size_t i = blockIdx.x * (size_t)VB + threadIdx.x; i < n; i += (size_t)gridDim.x * VB) {
-    using LZ = typename LazyOf<F>::type;
-    out[i] = LZ::sub(LZ::mul(LZ::unpack(a[i]), LZ::unpack(b[i]).times32()), LZ::unpack(c[i])).canonical_wide().pack();
+    out[i] = elem_mul_sub(a[i], b[i], c[i]);
   }
 }
 
@@ -48,8 +48,7 @@ template <class F>
 __global__ __launch_bounds__(VB) void k_vec_mul_table(F* v, const F* __restrict__ table, size_t n_elems, uint32_t ncomp) {
   for (size_t e = blockIdx.x * (size_t)VB + threadIdx.x; e < n_elems; e += (size_t)gridDim.x * VB) {
     size_t i = ncomp == 1 ? e : e / ncomp;
-    using LZ = typename LazyOf<F>::type;
-    v[e] = LZ::mul(LZ::unpack(v[e]), LZ::unpack(table[i]).times32()).canonical_wide().pack();
+    v[e] = elem_mul(v[e], table[i]);
   }
 }
 
@@ -60,23 +59,14 @@ __global__ __launch_bounds__(VB) void k_rep3_local_mul(const F* __restrict__ lhs
   for (size_t i = blockIdx.x * (size_t)VB + threadIdx.x; i < n; i += (size_t)gridDim.x * VB) {
     F la = lhs[2 * i], lb = lhs[2 * i + 1];
     F ra = rhs[2 * i], rb = rhs[2 * i + 1];
-    // a*a' + a*b' + b*a' = la*(ra+rb) + lb*ra  (2 multiplications instead of 3; same field element)
-    //   both products accumulate double-width before ONE reduction
-    using LZ = typename LazyOf<F>::type;
-    const LZ xa = LZ::unpack(la), xb = LZ::unpack(lb), ya = LZ::unpack(ra), yb = LZ::unpack(rb);
-    LZ r = LZ::reduce(LZ::mul_add_wide(xa, LZ::add(ya, yb).times32(), xb, ya.times32()));
-    if (mask) r = LZ::add(r, LZ::unpack(mask[i]));
-    if (sub) r = LZ::sub(r, LZ::unpack(sub[i]));
-    out[i] = r.canonical_wide().pack();
+    out[i] = elem_rep3_local_mul(la, lb, ra, rb, mask, sub, i);
   }
 }
 
 template <class F>
 __global__ __launch_bounds__(VB) void k_rep3_to_shamir(const F* __restrict__ in, F x, F y, F* out, size_t n) {
   for (size_t i = blockIdx.x * (size_t)VB + threadIdx.x; i < n; i += (size_t)gridDim.x * VB) {
-    using LZ = typename LazyOf<F>::type;
-    const LZ lx = LZ::unpack(x).times32(), ly = LZ::unpack(y).times32();
-    out[i] = LZ::reduce(LZ::mul_add_wide(LZ::unpack(in[2 * i]), lx, LZ::unpack(in[2 * i + 1]), ly)).canonical_wide().pack();
+    out[i] = elem_rep3_to_shamir(in[2 * i], in[2 * i + 1], x, y);
   }
 }
 

@@ -242,3 +242,44 @@ def check_zero_flags(flags, comps, ctx):
     assert both == zero, ("is_zero()", kinds, ctx)
     if all(k in ("zero", "limb0") for k in kinds):
         assert maybe, ("maybe_zero() misses a multiple of p in its window (or a value with the same limb 0)", kinds, ctx)
+
+
+# ---- edge-value case lists of the element-wise kernels (vec_ops.hip), shared by the host self-test and the device tests -------------
+def elementwise_edge_set(F):
+    """edge_elems(F) reduced mod p, plus (p + 1) / 2 and p - 3."""
+    return [v % F.p for v in edge_elems(F)] + [(F.p + 1) // 2, F.p - 3]
+
+
+def elementwise_cases(F):
+    """Operands and expected values (Python integers) of every per-element expression of vec_ops.hip at the edges of the field:
+    'pairs'      (a, b): all pairs of the edge set E;
+    'mul_sub'    (a, b, c, a b - c): every pair with c cycling through E, and with c = a b - t for t in {0, 1, p - 1} (result exactly t);
+    'rep3'       (la, lb, ra, rb, mask, sub, la (ra + rb) + lb ra + mask - sub): every pair (la, ra), (lb, rb, mask, sub) cycling through 13
+                 fixed tuples of E, then with the mask solved for a result of exactly 0, 1, p - 1; the same with sub = None (absent); the
+                 same with mask = None, where sub is the operand that is solved;
+    'to_shamir'  (a, b, x, y, a x + b y): every pair as the share, (x, y) = the three parties' translation points and (0, 0), (1, p - 1),
+                 (p - 1, p - 1)."""
+    from oracle import mpc
+    p = F.p
+    E = elementwise_edge_set(F)
+    ne = len(E)
+    pairs = [(a, b) for a in E for b in E]
+    tuples = [(E[(5 * k + 1) % ne], E[(7 * k + 3) % ne], E[(3 * k + 5) % ne], E[(11 * k + 7) % ne]) for k in range(13)]
+    targets = (0, 1, p - 1)
+    mul_sub, rep3 = [], []
+    for k, (a, b) in enumerate(pairs):
+        for c in [E[(k + k // ne) % ne]] + [(a * b - t) % p for t in targets]:
+            mul_sub.append((a, b, c, (a * b - c) % p))
+    for with_mask, with_sub in ((True, True), (True, False), (False, True)):
+        for k, (la, ra) in enumerate(pairs):
+            lb, rb, m, s = tuples[k % len(tuples)]
+            prod = la * (ra + rb) + lb * ra
+            s_ = s if with_sub else 0
+            variants = [(m if with_mask else None, s if with_sub else None)]
+            for t in targets:
+                variants.append(((t - prod + s_) % p, s if with_sub else None) if with_mask else (None, (prod - t) % p))
+            for mm, ss in variants:
+                rep3.append((la, lb, ra, rb, mm, ss, (prod + (mm or 0) - (ss or 0)) % p))
+    points = [mpc.rep3_to_shamir_points(F, party) for party in range(3)] + [(0, 0), (1, p - 1), (p - 1, p - 1)]
+    to_shamir = [(a, b, x, y, (a * x + b * y) % p) for x, y in points for a, b in pairs]
+    return {"pairs": pairs, "mul_sub": mul_sub, "rep3": rep3, "to_shamir": to_shamir}

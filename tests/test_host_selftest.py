@@ -365,11 +365,63 @@ def test_lazy_share_vector_products(hip, curve):
         for j, b in enumerate(vals):
             c, d, m = vals[(i + 2 * j + 1) % len(vals)], vals[(3 * i + j + 2) % len(vals)], vals[(i * j + 3) % len(vals)]
             out = np.zeros(4, dtype=np.uint64)
-            assert L.csh_selftest_lazy_vec(cid, 0, pk(a), pk(b), pk(c), pk(d), pk(m), out.ctypes.data_as(C.c_void_p)) == 0
+            assert L.csh_selftest_lazy_vec(cid, 0, pk(a), pk(b), pk(c), pk(d), pk(m), out.ctypes.data_as(C.c_void_p), None) == 0
             assert H.unpack(F, out) == [a * b % F.p]
-            assert L.csh_selftest_lazy_vec(cid, 1, pk(a), pk(b), pk(c), pk(d), pk(m), out.ctypes.data_as(C.c_void_p)) == 0
+            assert L.csh_selftest_lazy_vec(cid, 1, pk(a), pk(b), pk(c), pk(d), pk(m), out.ctypes.data_as(C.c_void_p), None) == 0
             assert H.unpack(F, out) == [(a * (c + d) + b * c + m) % F.p]
 
+
+@pytest.mark.parametrize("curve", ["bn254", "bls12_381", "bls12_377"])
+def test_share_vector_expressions_at_the_edges_of_the_field(hip, curve):
+    """Every op of csh_selftest_lazy_vec -- the per-element functions of vec_elem.hpp that the kernels of vec_ops.hip call, run on the host
+    with the limb-bound contract asserted -- against Python integers on the case lists of helpers.elementwise_cases: all pairs of the edge
+    set; a b - c with results of exactly 0, 1 and p - 1; the Rep3 product plus mask minus sub with each of the two absent and results of
+    exactly 0, 1 and p - 1; the Rep3-to-Shamir combination at the parties' translation points and at (0, 0), (1, p - 1), (p - 1, p - 1).
+    Every output must be the canonical Montgomery encoding of the expected value, not merely decode to it."""
+    F = H.FR[curve]
+    cid = H.CURVE_IDS[curve]
+    p = F.p
+    L = hip.lib()
+    packed = {}
+
+    def pk(v):
+        if v is None:
+            return None
+        if v not in packed:
+            packed[v] = H.pack(F, [v])
+        return packed[v].ctypes.data_as(C.c_void_p)
+
+    out = np.zeros(4, dtype=np.uint64)
+
+    def run(op, want, a, b, c, d=None, m=None, s=None):
+        out[:] = 0xFFFFFFFFFFFFFFFF
+        assert L.csh_selftest_lazy_vec(cid, op, pk(a), pk(b), pk(c), pk(d), pk(m), out.ctypes.data_as(C.c_void_p), pk(s)) == 0
+        assert int.from_bytes(out.tobytes(), "little") == F.to_mont(want), (op, a, b, c, d, m, s)
+
+    cases = H.elementwise_cases(F)
+    E = H.elementwise_edge_set(F)
+    assert len(cases["pairs"]) == len(E) ** 2 and {0, 1, 2, p - 1, p - 2, p - 3, (p - 1) // 2, (p + 1) // 2} <= set(E)
+    for a, b in cases["pairs"]:
+        run(0, a * b % p, a, b, 0)
+    for a, b, c, want in cases["mul_sub"]:
+        assert want == (a * b - c) % p
+        run(2, want, a, b, c)
+    assert sorted(set(t[3] for t in cases["mul_sub"]) & {0, 1, p - 1}) == [0, 1, p - 1]
+    seen = set()
+    for la, lb, ra, rb, m, s, want in cases["rep3"]:
+        assert want == (la * (ra + rb) + lb * ra + (m or 0) - (s or 0)) % p
+        run(3, want, la, lb, ra, rb, m, s)
+        if s is None:   # op 1 is the same expression without a sub operand (its mask is not optional)
+            run(1, want, la, lb, ra, rb, m)
+        if want in (0, 1, p - 1):
+            seen.add((m is not None, s is not None, want))
+    assert len(seen) == 9   # mask and sub, mask alone, sub alone: each driven to exactly 0, 1 and p - 1
+    for a, b, x, y, want in cases["to_shamir"]:
+        assert want == (a * x + b * y) % p
+        run(4, want, a, b, x, y)
+    # ops outside the list and missing operands are refused, not guessed
+    assert L.csh_selftest_lazy_vec(cid, 5, pk(1), pk(1), pk(1), pk(1), pk(1), out.ctypes.data_as(C.c_void_p), None) != 0
+    assert L.csh_selftest_lazy_vec(cid, 1, pk(1), pk(1), pk(1), pk(1), None, out.ctypes.data_as(C.c_void_p), None) != 0
 
 
 @pytest.mark.parametrize("curve", ["bn254", "bls12_381", "bls12_377"])
