@@ -174,6 +174,35 @@ __device__ __forceinline__ QPt<L> qmul_small(const QPt<L>& p, uint32_t k, int ro
   return r;
 }
 
+// k * P for a small unsigned k (quad-uniform), two bits at a time: 2 P and 3 P first, then two doublings and one addition per digit,
+// the addend picked from {P, 2 P, 3 P} by a data select. The 16 quads of a wave hold different k: a branch per BIT is taken by
+// some quad at nearly every position, so the wave runs an addition per bit (14 doublings + ~11 additions for 14-bit k, where a quad
+// alone needs ~7); here the schedule depends on the number of digits only, and a wave skips an addition only where every quad's digit
+// is zero. Each quad starts at its own top digit (the doublings of an empty sum return at once); a wave runs the digit count of its widest quad.
+template <class L>
+__device__ __forceinline__ QPt<L> qmul_small_w2(const QPt<L>& p, uint32_t k, int role) {
+  QPt<L> r = qpt_inf<L>();
+  if (k == 0 || p.empty) return r;
+  QPt<L> p2 = p;
+  qdbl<L>(p2, role);
+  QPt<L> p3 = p2;
+  qadd<L>(p3, p, role);
+  int top = 30;
+  while (!((k >> top) & 3)) top -= 2;
+  for (int s = top; s >= 0; s -= 2) {
+    qdbl<L>(r, role);
+    qdbl<L>(r, role);
+    const uint32_t d = (k >> s) & 3;
+    if (d) {
+      QPt<L> o;
+      o.v = lane_select(d == 1, p.v, lane_select(d == 2, p2.v, p3.v));
+      o.empty = d == 1 ? p.empty : (d == 2 ? p2.empty : p3.empty);
+      qadd<L>(r, o, role);
+    }
+  }
+  return r;
+}
+
 #endif  // device
 
 }  // namespace csh

@@ -257,10 +257,10 @@ __global__ __launch_bounds__(ACC_BLK) void k_msm_accum_pair(const Affine<typenam
 }
 
 // ---- the latency-bound tail: merge -> reduce -> fold, four lanes per point (curve_quad.hpp) ---------------------------
-// A "logical lane" (one bucket / one segment / one tree node) is a DPP quad; blocks of TAIL_BLK threads hold TAIL_BLK / 4 of
-// them. Control flow depends on the logical index and on quad-broadcast flags only, so the four lanes stay converged.
-constexpr int TAIL_BLK = 64;
-constexpr int TAIL_Q = TAIL_BLK / 4;
+// A "logical lane" (one bucket / one segment / one tree node) is a DPP quad; the merge runs blocks of MERGE_BLK threads = MERGE_Q
+// buckets. Control flow depends on the logical index and on quad-broadcast flags only, so the four lanes stay converged.
+constexpr int MERGE_BLK = 256;
+constexpr int MERGE_Q = MERGE_BLK / 4;
 
 // Bucket merge: the partials of bucket b sit in consecutive slots b + k0 .. b + k1 (k0, k1 = first / last lane that
 // touched it). One quad per bucket folds them into the dense array dense[w][b]; buckets with more than MERGE_CAP
@@ -289,30 +289,51 @@ __device__ __forceinline__ void giant_enqueue(uint32_t* giant_count, uint32_t* g
   giant_list[2 * g] = tag;
   giant_list[2 * g + 1] = b;
 }
+// Two phases. A wave executes the longest trip count of its 16 quads, and with uniform scalars most buckets have one or two partials
+// and a few have three (2^20, L = 55: 84 % one addition, 15 % two): a plain loop per quad runs the second addition in 94 % of the waves
+// for 15 % of the buckets. Phase 1: every quad folds at most the first two partials and stores dense[b]; a bucket with more goes on a
+// block-local list. Phase 2: list entry j is taken by quad j, so what is left packs into the fewest waves (the others fall through); it
+// reloads dense[b] and adds the remaining partials in the same order: every bucket sum keeps its bits.
 template <class Cfg>
-__global__ __launch_bounds__(TAIL_BLK) void k_msm_merge(MsmParams p, const uint32_t* __restrict__ start,
-                                                        const LazyPt<Cfg>* __restrict__ partial, LazyPt<Cfg>* dense,
-                                                        uint32_t* giant_count, uint32_t* giant_list, uint32_t* big_list) {
+__global__ __launch_bounds__(MERGE_BLK) void k_msm_merge(MsmParams p, const uint32_t* __restrict__ start,
+                                                         const LazyPt<Cfg>* __restrict__ partial, LazyPt<Cfg>* dense,
+                                                         uint32_t* giant_count, uint32_t* giant_list, uint32_t* big_list) {
   using L = typename Cfg::L;
+  __shared__ uint32_t list_n;
+  __shared__ uint32_t list[MERGE_Q];
   const int w = blockIdx.y;
   const int role = threadIdx.x & 3;
-  const uint32_t b = blockIdx.x * TAIL_Q + (threadIdx.x >> 2) + 1;
-  if (b > p.NB) return;
+  const uint32_t q = threadIdx.x >> 2;
+  const uint32_t b0 = blockIdx.x * MERGE_Q + 1;
   const uint32_t* st = start + (size_t)w * (p.NB + 2);
-  const uint32_t lo = st[b], hi = st[b + 1];
-  QPt<L> acc = qpt_inf<L>();
-  if (hi > lo) {
-    const uint32_t Lw = lane_len(p, w);
-    const uint32_t k0 = lo / Lw, k1 = (hi - 1) / Lw;
-    const LazyPt<Cfg>* pw = partial + (size_t)w * p.tmax + b;
-    if (k1 - k0 >= MERGE_CAP) {
-      if (role == 0) giant_enqueue(giant_count, giant_list, big_list, (uint32_t)w, b, k1 - k0 + 1);
-    } else {
-      acc = qpt_load<L>(&pw[k0], role);
-      for (uint32_t k = k0 + 1; k <= k1; ++k) qadd<L>(acc, qpt_load<L>(&pw[k], role), role);
+  const uint32_t Lw = lane_len(p, w);
+  const LazyPt<Cfg>* pw = partial + (size_t)w * p.tmax;
+  LazyPt<Cfg>* dw = dense + (size_t)w * (p.NB + 1);
+  if (threadIdx.x == 0) list_n = 0;
+  __syncthreads();
+  if (const uint32_t b = b0 + q; b <= p.NB) {
+    const uint32_t lo = st[b], hi = st[b + 1];
+    QPt<L> acc = qpt_inf<L>();
+    if (hi > lo) {
+      const uint32_t k0 = lo / Lw, k1 = (hi - 1) / Lw;
+      if (k1 - k0 >= MERGE_CAP) {
+        if (role == 0) giant_enqueue(giant_count, giant_list, big_list, (uint32_t)w, b, k1 - k0 + 1);
+      } else {
+        acc = qpt_load<L>(&pw[b + k0], role);
+        if (k1 > k0) qadd<L>(acc, qpt_load<L>(&pw[b + k0 + 1], role), role);
+        if (k1 - k0 >= 2 && role == 0) list[atomicAdd(&list_n, 1u)] = q;
+      }
     }
+    qpt_store<L>(&dw[b], role, acc);
   }
-  qpt_store<L>(&dense[(size_t)w * (p.NB + 1) + b], role, acc);
+  __syncthreads();  // the list is complete, and the dense[] stores of this block are visible to its other waves
+  if (q < list_n) {
+    const uint32_t b = b0 + list[q];
+    const uint32_t k0 = st[b] / Lw, k1 = (st[b + 1] - 1) / Lw;
+    QPt<L> acc = qpt_load<L>(&dw[b], role);
+    for (uint32_t k = k0 + 2; k <= k1; ++k) qadd<L>(acc, qpt_load<L>(&pw[b + k], role), role);
+    qpt_store<L>(&dw[b], role, acc);
+  }
 }
 
 // Tree over the quads of one block through LDS: on return quad 0 holds the sum of all nq quad values (nq a power of two).
@@ -472,7 +493,7 @@ __global__ __launch_bounds__(256) void k_msm_reduce(MsmParams p, const LazyPt<Cf
         if (gap <= 4) {
           while (gap--) qadd<L>(acc, running, role);
         } else {
-          const QPt<L> m = qmul_small<L>(running, gap, role);
+          const QPt<L> m = qmul_small_w2<L>(running, gap, role);
           qadd<L>(acc, m, role);
         }
       }
@@ -480,7 +501,7 @@ __global__ __launch_bounds__(256) void k_msm_reduce(MsmParams p, const LazyPt<Cf
       prev_b = t;
     }
     if (prev_b) {  // acc = sum (b - bmin) B_b ; add bmin * R
-      const QPt<L> m = qmul_small<L>(running, prev_b, role);
+      const QPt<L> m = qmul_small_w2<L>(running, prev_b, role);
       qadd<L>(acc, m, role);
     }
   }
@@ -828,7 +849,7 @@ int bucket_group(const void* points, const MsmParams& p_all, const SortOut& so, 
   if (fused)
     hipLaunchKernelGGL(k_msm_mark_giant<Cfg>, dim3((p.NB + 255) / 256, nw), dim3(256), 0, st, p, start, giant, giant + 2, big);
   else
-    hipLaunchKernelGGL(k_msm_merge<Cfg>, dim3((p.NB + TAIL_Q - 1) / TAIL_Q, nw), dim3(TAIL_BLK), 0, st, p, start, partial, dense, giant, giant + 2, big);
+    hipLaunchKernelGGL(k_msm_merge<Cfg>, dim3((p.NB + MERGE_Q - 1) / MERGE_Q, nw), dim3(MERGE_BLK), 0, st, p, start, partial, dense, giant, giant + 2, big);
   // buckets with > MERGE_CAP partials (heavily repeated scalars): block-wide tree, grid-stride over the queue; the few with >= GIANT_BIG
   // partials (a witness's "1"s, a repeated value) are summed in GIANT_SLICES slices by one block each first (blocks past the count return)
   hipLaunchKernelGGL(k_msm_giant_slices<Cfg>, dim3(GIANT_SLICES, GIANT_ROWS), dim3(256), 0, st, p, start, partial, giant, big, gscratch);
