@@ -33,6 +33,8 @@ from .bindings import (  # noqa: F401
     lib,
     lib_path,
     lincomb,
+    mle_fold,
+    mle_fold_rounds,
     msm_fold_partials,
     msm_partial_bytes,
     msm_split,

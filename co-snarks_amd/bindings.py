@@ -486,6 +486,47 @@ def poly_div_linear(curve: int, coeffs, root, ncomp: int = 1, sub0=None, n: int 
     return res, r
 
 
+def mle_fold(curve: int, vecs, u, ncomp: int = 1, n: int | None = None, outs=None, stream=None):
+    """csh_mle_fold: one multilinear fold round on k vectors, out[v][j] = in[v][2j] + u (in[v][2j+1] - in[v][2j]). `u` is a host element.
+    A list of host arrays gives a list of host arrays. A list of DeviceBuffers (with n): the stream-ordered form into the DeviceBuffers
+    `outs` (n / 2 elements each, never one of the inputs), which are returned."""
+    uu = _u64(u)
+    assert uu.size == 4
+    k = len(vecs)
+    if k and isinstance(vecs[0], DeviceBuffer):
+        ins = (C.c_void_p * k)(*[_devptr(v).value for v in vecs])
+        ous = (C.c_void_p * k)(*[_devptr(o).value for o in outs])
+        _check(lib().csh_mle_fold_dev(curve, ins, ous, C.c_size_t(k), C.c_size_t(n), C.c_uint32(ncomp), _p(uu), _stream(stream)))
+        return outs
+    arrs = [_u64(v) for v in vecs]
+    cnt = arrs[0].size // (4 * ncomp) if k else 0
+    res = [np.empty(4 * ncomp * (cnt // 2), dtype=np.uint64) for _ in arrs]
+    ins = (C.c_void_p * k)(*[a.ctypes.data for a in arrs])
+    ous = (C.c_void_p * k)(*[r.ctypes.data for r in res])
+    _check(lib().csh_mle_fold(curve, ins, ous, C.c_size_t(k), C.c_size_t(cnt), C.c_uint32(ncomp), _p(uu)))
+    return res
+
+
+def mle_fold_rounds(curve: int, vec, us, ncomp: int = 1, n: int | None = None, levels=True, last=True, stream=None):
+    """csh_mle_fold_rounds: m = len(us) / 4 fold rounds on one vector -> (levels, last). levels: levels 1..m back to back (level l at
+    element offset n - n / 2^(l-1)), last: level m alone; with n = 2^m that is the value of evaluate_mle. Host array: `levels` / `last`
+    are flags, host arrays (or None) come back. DeviceBuffer (with n): they are DeviceBuffers or None, handed back as given."""
+    uu = _u64(us)
+    m = uu.size // 4
+    if isinstance(vec, DeviceBuffer):
+        lv = levels if isinstance(levels, DeviceBuffer) else None
+        la = last if isinstance(last, DeviceBuffer) else None
+        _check(lib().csh_mle_fold_rounds_dev(curve, _devptr(vec), C.c_size_t(n), C.c_uint32(ncomp), _p(uu), C.c_size_t(m), _devptr(lv), _devptr(la),
+                                             _stream(stream)))
+        return lv, la
+    a = _u64(vec)
+    cnt = a.size // (4 * ncomp)
+    lv = np.empty(4 * ncomp * (cnt - (cnt >> m)), dtype=np.uint64) if levels else None
+    la = np.empty(4 * ncomp * (cnt >> m), dtype=np.uint64) if last else None
+    _check(lib().csh_mle_fold_rounds(curve, _p(a), C.c_size_t(cnt), C.c_uint32(ncomp), _p(uu), C.c_size_t(m), _p(lv), _p(la)))
+    return lv, la
+
+
 def rep3_local_mul_vec(curve: int, lhs_ab, rhs_ab, mask=None):
     l, r = _u64(lhs_ab), _u64(rhs_ab)
     n = l.size // 8

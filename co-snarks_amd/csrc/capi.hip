@@ -472,6 +472,7 @@ static const TuneEntry kTune[] = {
     {"scan_lane_run", "CSH_SCAN_LANE_RUN", &Tune::scan_lane_run},
     {"scan_tile_lanes", "CSH_SCAN_TILE_LANES", &Tune::scan_tile_lanes},
     {"scan_spine_step", "CSH_SCAN_SPINE_STEP", &Tune::scan_spine_step},
+    {"fold_tile_log", "CSH_FOLD_TILE_LOG", &Tune::fold_tile_log},
 };
 static bool is_scan_knob(std::atomic<int> Tune::*f) { return f == &Tune::scan_lane_run || f == &Tune::scan_tile_lanes || f == &Tune::scan_spine_step; }
 Tune& tune() {
@@ -751,6 +752,10 @@ int csh_tune_set(const char* key, int value) {
       }
       if (is_scan_knob(e.field) && !scan_knob_ok(e.field, value)) {
         set_error("csh_tune_set: '%s' = %d is out of range (scan_lane_run: 4 or 8; scan_tile_lanes: 64, 128, 256; scan_spine_step: a power of two, 64 .. 1024)", key, value);
+        return CSH_ERR_INVALID;
+      }
+      if (e.field == &Tune::fold_tile_log && !fold_tile_log_ok(value)) {
+        set_error("csh_tune_set: '%s' = %d is out of range (fold_tile_log: 3 .. 11)", key, value);
         return CSH_ERR_INVALID;
       }
       (tune().*(e.field)).store(value);

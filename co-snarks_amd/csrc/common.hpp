@@ -192,6 +192,8 @@ struct Tune {
   std::atomic<int> scan_lane_run{8};      // elements a lane reduces / scans serially in registers: 4 or 8
   std::atomic<int> scan_tile_lanes{256};  // lanes of a tile's workgroup: 64, 128 or 256 (tile = scan_lane_run x scan_tile_lanes elements)
   std::atomic<int> scan_spine_step{1024}; // tile totals the one-workgroup spine takes per step (= its lanes): a power of two, 64 .. 1024
+  // multilinear folds (mle_fold.hip): the decomposition only, never a result
+  std::atomic<int> fold_tile_log{10};     // log2 of the elements a workgroup of k_mle_fold_rounds folds on chip (= rounds per launch): 3 .. 11
 };
 Tune& tune();
 // the values csh_tune_set accepts for the field-scan keys (the launchers fall back to the defaults for anything else)
@@ -200,6 +202,9 @@ inline bool scan_knob_ok(std::atomic<int> Tune::*key, int v) {
   const int hi = key == &Tune::scan_tile_lanes ? 256 : 1024;
   return v >= 64 && v <= hi && (v & (v - 1)) == 0;
 }
+
+constexpr int FOLD_TILE_LOG_MIN = 3, FOLD_TILE_LOG_MAX = 11, FOLD_TILE_LOG_DEFAULT = 10;
+inline bool fold_tile_log_ok(int v) { return v >= FOLD_TILE_LOG_MIN && v <= FOLD_TILE_LOG_MAX; }
 
 // A Rep3 local multiplication without its correlated mask is not a valid sharing step: once opened, the products leak
 // cross terms (rep3/arithmetic.rs:132-146 always adds masking_field_elements_vec). NULL masks / seeds are therefore an

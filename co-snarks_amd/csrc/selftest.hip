@@ -13,6 +13,7 @@
 #include "chacha.hpp"
 #include "field29.hpp"
 #include "field_scan.hpp"
+#include "mle_fold.hpp"
 #include "msm_digits.hpp"
 #include "vec_elem.hpp"
 
@@ -422,7 +423,98 @@ static int divlin_host_t(const uint64_t* in, size_t n, uint32_t ncomp, int run, 
   return CSH_OK;
 }
 
+// Host run of the multilinear folds (mle_fold.hip) with the limb-bound checks on: the launches, tiles and rounds of k_mle_fold_rounds with
+// every level kept, fold_tile_round lane after lane instead of side by side, the limb planes in a vector instead of LDS -- and the same
+// chain once more as m sweeps of k_mle_fold's elem_fold. The two must agree word for word (CSH_ERR_HIP otherwise: the decomposition changed
+// a result). levels_out: levels 1..m back to back as csh_mle_fold_rounds lays them out. All arkworks-Montgomery in and out.
+template <class F>
+static int mle_fold_host_t(const uint64_t* in, size_t n, uint32_t ncomp, int T, const uint64_t* u, size_t m, uint64_t* levels_out) {
+  using LZ = typename LazyOf<F>::type;
+  std::vector<F> src(n * ncomp), lev((n - (n >> m)) * ncomp);
+  memcpy(src.data(), in, sizeof(F) * src.size());
+  std::vector<int32_t> planes(LZ::NL * (fold_plane_a(T, ncomp) + fold_plane_b(T, ncomp)));
+  const size_t launches = (m + T - 1) / T;
+  for (size_t p = 0; p < launches; ++p) {
+    FoldRoundsArgs<F> a;
+    memset(&a, 0, sizeof a);
+    a.rounds = (int)(m - p * T < (size_t)T ? m - p * T : (size_t)T);
+    for (int r = 0; r < a.rounds; ++r) {
+      F uf;
+      memcpy(&uf, u + 4 * (p * T + r), sizeof(F));
+      a.ud[r] = fold_challenge(uf);
+    }
+    a.in = p ? lev.data() + fold_level_offset(n, (int)(p * T)) * ncomp : src.data();
+    a.n_in = n >> (p * T);
+    a.ncomp = ncomp;
+    a.tile_log = T;
+    a.levels = lev.data() + fold_level_offset(n, (int)(p * T) + 1) * ncomp;
+    a.last = nullptr;
+    const size_t tiles = (a.n_in + ((size_t)1 << T) - 1) >> T;
+    for (size_t tile = 0; tile < tiles; ++tile)
+      for (int r = 1; r <= a.rounds; ++r)
+        for (size_t lane = 0; lane < (size_t)FOLD_WG; ++lane) fold_tile_round(a, tile, r, lane, FOLD_WG, planes.data());
+  }
+  std::vector<F> cur(src), nxt;
+  for (size_t l = 1; l <= m; ++l) {  // k_mle_fold, sweep after sweep
+    F uf;
+    memcpy(&uf, u + 4 * (l - 1), sizeof(F));
+    const F ud = fold_challenge(uf);
+    nxt.resize(cur.size() / 2);
+    for (size_t o = 0; o < nxt.size(); ++o) {
+      const size_t s = fold_src(o, ncomp);
+      nxt[o] = elem_fold(cur[s], cur[s + ncomp], ud);
+    }
+    if (memcmp(nxt.data(), lev.data() + fold_level_offset(n, (int)l) * ncomp, sizeof(F) * nxt.size())) return CSH_ERR_HIP;
+    cur.swap(nxt);
+  }
+  memcpy(levels_out, lev.data(), sizeof(F) * lev.size());
+  return CSH_OK;
+}
+
+// fold_step (vec_elem.hpp) applied `rounds` times to a pair of LAZY values with nothing canonical in between, limb-bound checks on: what
+// mle_fold.hpp claims about the bound not depending on the round, for any round count -- through the tiles a chain of R rounds needs 2^R
+// elements. Each round (x, y) <- (x + u (y - x), y + u (x - y)); out receives both values after every round, canonical (copies: the
+// chain goes on from the lazy ones).
+template <class F>
+static int fold_step_chain_t(const uint64_t* a, const uint64_t* b, const uint64_t* u, size_t rounds, uint64_t* out) {
+  using LZ = typename LazyOf<F>::type;
+  F fa, fb, fu;
+  memcpy(&fa, a, sizeof(F));
+  memcpy(&fb, b, sizeof(F));
+  memcpy(&fu, u, sizeof(F));
+  const LZ ud = LZ::unpack(fold_challenge(fu));
+  LZ x = LZ::unpack(fa), y = LZ::unpack(fb);
+  for (size_t r = 0; r < rounds; ++r) {
+    const LZ nx = fold_step(x, y, ud), ny = fold_step(y, x, ud);
+    x = nx;
+    y = ny;
+    const F ox = x.canonical_narrow().pack(), oy = y.canonical_narrow().pack();
+    memcpy(out + 8 * r, &ox, sizeof(F));
+    memcpy(out + 8 * r + 4, &oy, sizeof(F));
+  }
+  return CSH_OK;
+}
+
 extern "C" {
+
+int csh_selftest_mle_fold_host(int field_of, const uint64_t* in, size_t n, uint32_t ncomp, int tile_log, const uint64_t* u, size_t m,
+                               uint64_t* levels_out) {
+  if (!in || !u || !levels_out || ncomp < 1 || ncomp > 2 || !fold_tile_log_ok(tile_log) || m < 1 || m > 28 || n < 2 ||
+      (n & ((size_t(1) << m) - 1)))
+    return CSH_ERR_INVALID;
+  if (field_of == CSH_BN254) return mle_fold_host_t<Bn254Fr>(in, n, ncomp, tile_log, u, m, levels_out);
+  if (field_of == CSH_BLS12_381) return mle_fold_host_t<Bls381Fr>(in, n, ncomp, tile_log, u, m, levels_out);
+  if (field_of == CSH_BLS12_377) return mle_fold_host_t<Bls377Fr>(in, n, ncomp, tile_log, u, m, levels_out);
+  return CSH_ERR_INVALID;
+}
+
+int csh_selftest_fold_step_chain_host(int field_of, const uint64_t* a, const uint64_t* b, const uint64_t* u, size_t rounds, uint64_t* out) {
+  if (!a || !b || !u || !out) return CSH_ERR_INVALID;
+  if (field_of == CSH_BN254) return fold_step_chain_t<Bn254Fr>(a, b, u, rounds, out);
+  if (field_of == CSH_BLS12_381) return fold_step_chain_t<Bls381Fr>(a, b, u, rounds, out);
+  if (field_of == CSH_BLS12_377) return fold_step_chain_t<Bls377Fr>(a, b, u, rounds, out);
+  return CSH_ERR_INVALID;
+}
 
 int csh_selftest_divlin_host(int field_of, const uint64_t* in, size_t n, uint32_t ncomp, int run, const uint64_t* root, const uint64_t* sub0,
                              uint64_t* out) {

@@ -44,4 +44,18 @@ CSH_HD F elem_rep3_to_shamir(const F& a, const F& b, const F& x, const F& y) {
   return LZ::reduce(LZ::mul_add_wide(LZ::unpack(a), lx, LZ::unpack(b), ly)).canonical_wide().pack();
 }
 
+// a + u (b - a), the multilinear fold of one pair (k_mle_fold, k_mle_fold_rounds; partially_evaluate, co_sumcheck_prover.rs:34-98).
+// ud: the challenge in the R' domain (u R' mod p, canonical and packed: fold_challenge() of mle_fold.hpp, once per call on the host), so
+// mul(b - a, ud) comes out at the operands' scale and no loaded operand is scaled. fold_step is the same on lazy values, for the rounds that
+// stay on chip: a, b within (-1.1 p, 2.1 p) with limbs 0..NL-2 in [0, 2^B) (loaded, or an earlier fold_step); bounds in mle_fold.hpp.
+template <class LZ>
+CSH_HD LZ fold_step(const LZ& a, const LZ& b, const LZ& ud) {
+  return LZ::add(a, LZ::mul(LZ::sub(b, a), ud)).fold_top();
+}
+template <class F>
+CSH_HD F elem_fold(const F& a, const F& b, const F& ud) {
+  using LZ = typename LazyOf<F>::type;
+  return fold_step(LZ::unpack(a), LZ::unpack(b), LZ::unpack(ud)).canonical_narrow().pack();
+}
+
 }  // namespace csh

@@ -413,6 +413,38 @@ def driver_batched_quotient(curve: int, driver: int, polys_mont, points_mont, ev
     return out.reshape(3, m, 2, 4) if driver == REP3 else out.reshape(3, m, 4) if driver == SHAMIR else out.reshape(m, 4)
 
 
+def driver_mle_fold(curve: int, driver: int, op: str, polys_mont, challenges_mont, npub: int = 0, has_zk: bool = False, seed: int = 1):
+    """The multilinear-fold mirror: op "partially_evaluate" (polys_mont = npub public then the shared polynomials, equally long; the first
+    challenge through partially_evaluate_init, the others in place -> (public (npub, len, 4), shared), "fold_polynomials"
+    (compute_fold_polynomials on polys_mont = [A_0] -> the list flattened) or "evaluate_mle" (polys_mont = [coefficients] -> one share).
+    Shared results: plain (.., 4); Rep3 (3, .., 2, 4); Shamir (three parties, threshold 1) (3, .., 4). Shared inside with `seed`."""
+    polys = [np.ascontiguousarray(f, dtype=np.uint64).reshape(-1, 4) for f in polys_mont]
+    n = len(polys[0])
+    assert all(len(f) == n for f in polys)
+    ch = np.ascontiguousarray(challenges_mont, dtype=np.uint64).reshape(-1, 4)
+    opi = {"partially_evaluate": 0, "fold_polynomials": 1, "evaluate_mle": 2}[op]
+    nsh = len(polys) - npub
+    parties, comps = (1, 1) if driver == PLAIN else (3, 2) if driver == REP3 else (3, 1)
+    cap = parties * (npub + nsh * comps) * (n + len(ch) + 2) * 4
+    out = np.zeros(cap, dtype=np.uint64)
+    flat = np.concatenate(polys)
+    m = glib().cog16_driver_mle_fold(curve, driver, opi, flat.ctypes.data_as(C.c_void_p), C.c_size_t(npub), C.c_size_t(nsh), C.c_size_t(n),
+                                     ch.ctypes.data_as(C.c_void_p), C.c_size_t(len(ch)), int(has_zk), C.c_uint64(seed), out.ctypes.data_as(C.c_void_p))
+    if m < 0:
+        raise CoSnarksHipError(glib().cog16_last_error().decode())
+    shape = lambda a, k: a.reshape(k, m, 2, 4) if driver == REP3 else a.reshape(k, m, 4)
+    if opi == 0:
+        per = (npub + nsh * comps) * m * 4
+        pubs, shs = [], []
+        for p in range(parties):
+            blk = out[p * per:(p + 1) * per]
+            pubs.append(blk[:npub * m * 4].reshape(npub, m, 4))
+            shs.append(shape(blk[npub * m * 4:], nsh))
+        return (pubs[0], shs[0]) if driver == PLAIN else (np.stack(pubs), np.stack(shs))
+    res = out[:parties * comps * m * 4]
+    return res.reshape(m, 4) if driver == PLAIN else res.reshape(3, m, 2, 4) if driver == REP3 else res.reshape(3, m, 4)
+
+
 def driver_inv_vec(curve: int, driver: int, a_mont, seed: int = 1, leaking_zeros=False, in_place=False):
     """::inv_vec, ::inv_many_in_place (in_place) or ::inv_many_in_place_leaking_zeros (leaking_zeros). Plain: (n, 4); Rep3:
     (3, n, 2, 4); Shamir (three parties, threshold 1): (3, n, 4). The strict forms raise the reference's message on a zero."""

@@ -1147,6 +1147,78 @@ int driver_batched_quotient_t(int driver, const uint64_t* polys, const size_t* l
   return (int)len;
 }
 
+// The multilinear-fold mirror (plonk_honk.hpp): op 0 = partially_evaluate over npub public + nshared shared polynomials of n elements each
+// (polys: one after the other, the public ones first), the first challenge through partially_evaluate_init, the others in place; op 1 =
+// compute_fold_polynomials on polys = A_0 (n = 2^log_n elements) with nch = virtual_log_n challenges and has_zk = flags; op 2 = evaluate_mle.
+// Shared values are shared inside with `seed`. out, per party (one for the plain driver, three otherwise): op 0 the public polynomials
+// [npub][len][limb], then the shared ones [nshared][len][component][limb]; op 1 the returned list flattened; op 2 one share. Returns the
+// elements per polynomial (op 0), in the flattened list (op 1), 1 (op 2).
+template <class P, class D, class Share>
+int mle_fold_party_t(int op, const std::vector<std::vector<typename P::Fr>>& pub, const std::vector<std::vector<Share>>& shared, size_t n,
+                     const std::vector<typename P::Fr>& ch, int flags, uint64_t*& out) {
+  using Fr = typename P::Fr;
+  auto put = [&](const void* src, size_t bytes) {
+    if (bytes) memcpy(out, src, bytes);
+    out += bytes / 8;
+  };
+  if (op == 0) {
+    auto pe = D::partially_evaluate(pub, shared, n, ch.at(0));
+    for (size_t r = 1; r < ch.size(); ++r) pe.partially_evaluate_inplace(ch[r]);
+    for (size_t i = 0; i < pub.size(); ++i) put(pe.public_poly(i).data(), sizeof(Fr) * pe.len());
+    for (size_t i = 0; i < shared.size(); ++i) put(pe.shared_poly(i).data(), sizeof(Share) * pe.len());
+    return (int)pe.len();
+  }
+  if (op == 1) {
+    size_t log_n = 0;
+    while ((size_t(1) << log_n) < n) ++log_n;
+    const auto list = D::compute_fold_polynomials(log_n, ch, shared.at(0), flags != 0);
+    size_t total = 0;
+    for (const auto& f : list) {
+      put(f.data(), sizeof(Share) * f.size());
+      total += f.size();
+    }
+    return (int)total;
+  }
+  const Share e = D::evaluate_mle(shared.at(0), ch);
+  put(&e, sizeof(Share));
+  return 1;
+}
+template <class P>
+int driver_mle_fold_t(int driver, int op, const uint64_t* polys, size_t npub, size_t nshared, size_t n, const uint64_t* challenges, size_t nch,
+                      int flags, uint64_t seed, uint64_t* out) {
+  using Fr = typename P::Fr;
+  using R3 = Rep3PrimeFieldShare<Fr>;
+  std::vector<Fr> ch(nch);
+  if (nch) memcpy((void*)ch.data(), challenges, 32 * nch);
+  std::vector<std::vector<Fr>> pub(npub, std::vector<Fr>(n)), sec(nshared, std::vector<Fr>(n));
+  for (size_t i = 0; i < npub + nshared; ++i)
+    if (n) memcpy((void*)(i < npub ? pub[i] : sec[i - npub]).data(), polys + 4 * n * i, 32 * n);
+  int len = 0;
+  if (driver == 0) return mle_fold_party_t<P, PlainPlonkDriver<P>, Fr>(op, pub, sec, n, ch, flags, out);
+  if (driver == 1) {
+    std::vector<std::vector<R3>> sh[3];
+    Rep3Sharer<Fr> sharer(seed);
+    for (const auto& v : sec) {
+      std::vector<R3> parts[3];
+      sharer.share(v, parts);
+      for (int p = 0; p < 3; ++p) sh[p].push_back(std::move(parts[p]));
+    }
+    for (int p = 0; p < 3; ++p) len = mle_fold_party_t<P, Rep3PlonkDriver<P>, R3>(op, pub, sh[p], n, ch, flags, out);  // local: no network
+    return len;
+  }
+  const int np = 3;
+  SeededShamirSharer<Fr> sharer(seed, np);
+  std::vector<std::vector<Fr>> sh[3];
+  for (int p = 0; p < np; ++p) sh[p].assign(nshared, std::vector<Fr>(n));
+  for (size_t i = 0; i < nshared; ++i)
+    for (size_t j = 0; j < n; ++j) {
+      const auto parts = sharer.share(sec[i][j], 1);
+      for (int p = 0; p < np; ++p) sh[p][i][j] = parts[p];
+    }
+  for (int p = 0; p < np; ++p) len = mle_fold_party_t<P, ShamirPlonkDriver<P>, Fr>(op, pub, sh[p], n, ch, flags, out);
+  return len;
+}
+
 // ::inv_vec (leaking_zeros = 0), ::inv_many_in_place_leaking_zeros (1) and ::inv_many_in_place (2: inv_vec's protocol, the noir
 // drivers' name and message). Plain: (n, 4); Rep3: [party][n][component][limb]; Shamir (3 parties, threshold 1):
 // [party][n][limb]. The values are shared inside with `seed`; a dealer hands the Shamir parties their double sharings.
@@ -1583,6 +1655,22 @@ int cog16_driver_batched_quotient(int curve, int driver, const uint64_t* polys, 
   try {
     if (curve == 0) return driver_batched_quotient_t<Bn254>(driver, polys, lens, k, points, evals, nu, seed, out);
     if (curve == 1) return driver_batched_quotient_t<Bls12_381>(driver, polys, lens, k, points, evals, nu, seed, out);
+    g_err = "unknown curve";
+    return -1;
+  } catch (const std::exception& e) {
+    g_err = e.what();
+    return -1;
+  }
+}
+int cog16_driver_mle_fold(int curve, int driver, int op, const uint64_t* polys, size_t npub, size_t nshared, size_t n, const uint64_t* challenges,
+                          size_t nch, int flags, uint64_t seed, uint64_t* out) {
+  try {
+    if (op < 0 || op > 2 || (op != 0 && (npub != 0 || nshared != 1))) {
+      g_err = "mle_fold: op 0 .. 2; ops 1 and 2 take one shared polynomial";
+      return -1;
+    }
+    if (curve == 0) return driver_mle_fold_t<Bn254>(driver, op, polys, npub, nshared, n, challenges, nch, flags, seed, out);
+    if (curve == 1) return driver_mle_fold_t<Bls12_381>(driver, op, polys, npub, nshared, n, challenges, nch, flags, seed, out);
     g_err = "unknown curve";
     return -1;
   } catch (const std::exception& e) {

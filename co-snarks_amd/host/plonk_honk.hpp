@@ -8,6 +8,8 @@
 //   NoirUltraHonkProver::{eval_poly, inv_many_in_place, inv_many_in_place_leaking_zeros}  co-noir-common/src/mpc/rep3.rs:208-257, rep3/poly.rs:39-68
 //   Polynomial / SharedPolynomial::factor_roots, compute_batched_quotient, Round5::div_by_zerofier(.., 1, beta)
 //       co-noir-common/src/polynomials/polynomial.rs:183, shared_polynomial.rs:92-140, co_shplemini_prover.rs:661-737, co-plonk/src/round5.rs:78-91
+//   partially_evaluate_init / partially_evaluate_inplace, compute_fold_polynomials, Polynomial / SharedPolynomial::evaluate_mle
+//       co_sumcheck_prover.rs:34-98, co_shplemini_prover.rs:236-312, polynomial.rs:270-312, shared_polynomial.rs:154-199 (csh_mle_fold / csh_mle_fold_rounds)
 // These data-parallel methods are mirrored, the whole-vector scans among them (running product, batch inverse, polynomial
 // evaluation, division by (X - z): csh_vec_prefix_prod / csh_vec_batch_inverse / csh_eval_poly / csh_poly_div_linear). The PLONK rounds / sumcheck / relations above them are
 // control logic and stay in the Rust host (SURVEY.md 8 "out of scope"). NOT mirrored: the Rep3 / Shamir array_prod_mul
@@ -162,6 +164,142 @@ inline std::vector<Share> unmask_inverse(std::vector<Share> r, std::vector<typen
   check(csh_vec_mul_table(P::ID, (uint64_t*)r.data(), (const uint64_t*)y.data(), r.size(), ncomp), "csh_vec_mul_table");
   return r;
 }
+// ---- multilinear folds (csh_mle_fold / csh_mle_fold_rounds): out[j] = in[2j] + u (in[2j+1] - in[2j]) on every component of the share type ----
+// multiplication of every component of a share by a public value (T::mul_with_public), host arithmetic on single elements
+template <class P, class Share>
+inline Share mul_with_public(const typename P::Fr& k, Share s) {
+  using Fr = typename P::Fr;
+  Fr* c = reinterpret_cast<Fr*>(&s);
+  for (size_t i = 0; i < sizeof(Share) / sizeof(Fr); ++i) c[i] = Fr::mul(c[i], k);
+  return s;
+}
+// PartiallyEvaluatePolys as the sumcheck rounds use it (partially_evaluate_init / partially_evaluate_inplace,
+// co_sumcheck_prover.rs:34-98, sumcheck_prover.rs:20-60): every polynomial, public and shared, stays on the device in two buffers that swap
+// roles each round -- a fold in place would be a race between workgroups -- and one csh_mle_fold_dev call per share width folds them all.
+// All buffers of the set are cut from ONE device allocation. round_size must be a power of two (the prover's is 2^log_n): every length on
+// the way down is then even, which csh_mle_fold requires; the reference's limit % 2 branch for an odd length is NOT mirrored, such a
+// round_size is refused here. The reference's "truncate, then push a zero if shorter than 2" rule is applied here, on the host side:
+// the length is kept here, and the pushed zero is one element written behind the single one that is left.
+template <class P, class Share>
+class PartiallyEvaluatePolys {
+  using Fr = typename P::Fr;
+  struct Poly {
+    size_t off[2];  // byte offsets of the two buffers in mem_
+    uint32_t ncomp;
+  };
+  std::vector<Poly> polys_;  // the public ones first
+  std::unique_ptr<DeviceMem> mem_;
+  size_t n_public_ = 0, len_ = 0;
+  int cur_ = 0;
+  char* at(const Poly& q, int which) const { return (char*)mem_->p + q.off[which]; }
+  void fold(size_t n, const Fr& u) {
+    for (uint32_t ncomp = 1; ncomp <= 2; ++ncomp) {
+      std::vector<const uint64_t*> in;
+      std::vector<uint64_t*> out;
+      for (const Poly& q : polys_)
+        if (q.ncomp == ncomp) {
+          in.push_back((const uint64_t*)at(q, cur_));
+          out.push_back((uint64_t*)at(q, cur_ ^ 1));
+        }
+      if (!in.empty()) check(csh_mle_fold_dev(P::ID, in.data(), out.data(), in.size(), n, ncomp, (const uint64_t*)&u, nullptr), "csh_mle_fold_dev");
+    }
+    cur_ ^= 1;
+    len_ = n / 2;
+    if (len_ < 2) {  // poly.push(zero)
+      check(csh_sync(nullptr), "csh_sync");
+      const Fr zero[2] = {Fr::zero(), Fr::zero()};
+      for (const Poly& q : polys_) check(csh_memcpy_h2d(at(q, cur_) + sizeof(Fr) * q.ncomp * len_, zero, sizeof(Fr) * q.ncomp), "csh_memcpy_h2d");
+      len_ = 2;
+    }
+  }
+  template <class E>
+  std::vector<E> get(size_t i) const {
+    std::vector<E> v(len_);
+    check(csh_memcpy_d2h(v.data(), at(polys_[i], cur_), sizeof(E) * len_), "csh_memcpy_d2h");
+    return v;
+  }
+
+ public:
+  // partially_evaluate_init: the first round_size entries of every polynomial folded by the first round challenge
+  PartiallyEvaluatePolys(const std::vector<std::vector<Fr>>& pub, const std::vector<std::vector<Share>>& shared, size_t round_size, const Fr& u) {
+    if (round_size < 2 || (round_size & (round_size - 1))) throw Error("partially_evaluate: round_size must be a power of two, at least 2");
+    for (const auto& v : pub)
+      if (v.size() < round_size) throw Error("partially_evaluate: polynomial shorter than round_size");
+    for (const auto& v : shared)
+      if (v.size() < round_size) throw Error("partially_evaluate: polynomial shorter than round_size");
+    const size_t half = round_size / 2 < 2 ? 2 : round_size / 2;
+    size_t total = 0;
+    auto place = [&](uint32_t ncomp) {
+      Poly q;
+      q.ncomp = ncomp;
+      q.off[0] = total;
+      total += (sizeof(Fr) * ncomp * round_size + 255) & ~size_t(255);
+      q.off[1] = total;
+      total += (sizeof(Fr) * ncomp * half + 255) & ~size_t(255);
+      polys_.push_back(q);
+    };
+    for (size_t i = 0; i < pub.size(); ++i) place(1);
+    for (size_t i = 0; i < shared.size(); ++i) place(sizeof(Share) / sizeof(Fr));
+    n_public_ = pub.size();
+    mem_.reset(new DeviceMem(total));
+    for (size_t i = 0; i < pub.size(); ++i) check(csh_memcpy_h2d(at(polys_[i], 0), pub[i].data(), sizeof(Fr) * round_size), "csh_memcpy_h2d");
+    for (size_t i = 0; i < shared.size(); ++i)
+      check(csh_memcpy_h2d(at(polys_[n_public_ + i], 0), shared[i].data(), sizeof(Share) * round_size), "csh_memcpy_h2d");
+    fold(round_size, u);
+  }
+  // partially_evaluate_inplace: every polynomial folded by the round challenge, truncated, a zero pushed if one element is left
+  void partially_evaluate_inplace(const Fr& u) { fold(len_, u); }
+  size_t len() const { return len_; }
+  std::vector<Fr> public_poly(size_t i) const { return get<Fr>(i); }
+  std::vector<Share> shared_poly(size_t i) const { return get<Share>(n_public_ + i); }
+};
+// compute_fold_polynomials (co_shplemini_prover.rs:236-312, shplemini_prover.rs:198): the list the reference returns -- A_1 .. A_(log_n-1),
+// then the constant folds of the virtual rounds. ONE csh_mle_fold_rounds call with m = log_n keeps every level; its last level is
+// final_eval, and the constant folds, the ZK zero factor included, are host arithmetic on that one value.
+template <class P, class Share>
+inline std::vector<std::vector<Share>> compute_fold_polynomials(size_t log_n, const std::vector<typename P::Fr>& multilinear_challenge,
+                                                                const std::vector<Share>& a_0, bool has_zk) {
+  using Fr = typename P::Fr;
+  constexpr uint32_t ncomp = sizeof(Share) / sizeof(Fr);
+  const size_t n = size_t(1) << log_n, virtual_log_n = multilinear_challenge.size();
+  if (log_n < 2 || virtual_log_n < log_n || a_0.size() < n) throw Error("compute_fold_polynomials: needs log_n >= 2, log_n challenges and 2^log_n coefficients");
+  std::vector<Share> levels(n - 1);
+  Share final_eval{};
+  check(csh_mle_fold_rounds(P::ID, (const uint64_t*)a_0.data(), n, ncomp, (const uint64_t*)multilinear_challenge.data(), log_n,
+                            (uint64_t*)levels.data(), (uint64_t*)&final_eval),
+        "csh_mle_fold_rounds");
+  std::vector<std::vector<Share>> fold_polynomials;
+  fold_polynomials.reserve(virtual_log_n);
+  for (size_t l = 1; l < log_n; ++l) fold_polynomials.emplace_back(levels.begin() + (n - (n >> (l - 1))), levels.begin() + (n - (n >> l)));
+  const Fr indicator = has_zk ? Fr::zero() : Fr::one();
+  fold_polynomials.push_back({mul_with_public<P, Share>(indicator, final_eval)});
+  Fr tail = Fr::one();
+  for (size_t k = log_n; k + 1 < virtual_log_n; ++k) {
+    tail = Fr::mul(tail, Fr::sub(Fr::one(), multilinear_challenge[k]));  // multiply by (1 - u_k)
+    fold_polynomials.push_back({mul_with_public<P, Share>(indicator, mul_with_public<P, Share>(tail, final_eval))});
+  }
+  return fold_polynomials;
+}
+// Polynomial::evaluate_mle / SharedPolynomial::evaluate_mle (polynomial.rs:270-312, shared_polynomial.rs:154-199): 2^dim coefficients,
+// dim <= the number of points; all dim rounds in one csh_mle_fold_rounds call that hands back the last level only, the (1 - u) factors
+// of the trivial dimensions on the host. (The reference asserts dim == the number of points, which leaves its own trivial-dimension loop
+// idle; the loop is mirrored as written.)
+template <class P, class Share>
+inline Share evaluate_mle(const std::vector<Share>& coefficients, const std::vector<typename P::Fr>& evaluation_points) {
+  using Fr = typename P::Fr;
+  constexpr uint32_t ncomp = sizeof(Share) / sizeof(Fr);
+  if (coefficients.empty()) return Share{};
+  size_t dim = 0;
+  while ((size_t(1) << dim) < coefficients.size()) ++dim;
+  if (dim == 0 || coefficients.size() != size_t(1) << dim || dim > evaluation_points.size())
+    throw Error("evaluate_mle: needs 2^dim coefficients, 1 <= dim <= the number of evaluation points");
+  Share result{};
+  check(csh_mle_fold_rounds(P::ID, (const uint64_t*)coefficients.data(), coefficients.size(), ncomp, (const uint64_t*)evaluation_points.data(), dim,
+                            nullptr, (uint64_t*)&result),
+        "csh_mle_fold_rounds");
+  for (size_t k = dim; k < evaluation_points.size(); ++k) result = mul_with_public<P, Share>(Fr::sub(Fr::one(), evaluation_points[k]), result);
+  return result;
+}
 }  // namespace detail
 
 // ShpleminiOpeningClaim as compute_batched_quotient reads it: f_j(X), the point x_j and (the share of) the evaluation v_j
@@ -253,6 +391,16 @@ struct PlainPlonkDriver {
   // Polynomial::factor_roots (polynomial.rs:183) and Round5::div_by_zerofier(inout, 1, beta) (co-plonk round5.rs:78-91)
   static void factor_roots(std::vector<Fr>& coeffs, const Fr& root) { detail::factor_roots<P, Fr>(coeffs, root); }
   static void div_by_zerofier(std::vector<Fr>& inout, size_t n, const Fr& beta) { detail::div_by_zerofier<P, Fr>(inout, n, beta); }
+  // the multilinear folds: sumcheck's partially_evaluate (co_sumcheck_prover.rs:34-98), Gemini's compute_fold_polynomials
+  // (co_shplemini_prover.rs:236-312) and evaluate_mle (polynomial.rs:270-312, shared_polynomial.rs:154-199); linear, no network
+  using PartiallyEvaluatePolys = detail::PartiallyEvaluatePolys<P, Fr>;
+  static PartiallyEvaluatePolys partially_evaluate(const std::vector<std::vector<Fr>>& pub, const std::vector<std::vector<Fr>>& shared, size_t round_size, const Fr& u) {
+    return PartiallyEvaluatePolys(pub, shared, round_size, u);
+  }
+  static std::vector<std::vector<Fr>> compute_fold_polynomials(size_t log_n, const std::vector<Fr>& multilinear_challenge, const std::vector<Fr>& a_0, bool has_zk) {
+    return detail::compute_fold_polynomials<P, Fr>(log_n, multilinear_challenge, a_0, has_zk);
+  }
+  static Fr evaluate_mle(const std::vector<Fr>& coeffs, const std::vector<Fr>& points) { return detail::evaluate_mle<P, Fr>(coeffs, points); }
   // co-plonk plain.rs:127-140 / co-noir plain.rs:240-252: every element's own inverse() there
   static std::vector<Fr> inv_vec(std::vector<Fr> a) {
     if (detail::batch_inverse<P>(a)) throw Error("Cannot invert zero");
@@ -323,6 +471,16 @@ struct Rep3PlonkDriver {
   // SharedPolynomial::factor_roots (shared_polynomial.rs:92-140) / div_by_zerofier on {a, b} shares: linear, no network
   static void factor_roots(std::vector<ArithmeticShare>& coeffs, const Fr& root) { detail::factor_roots<P, ArithmeticShare>(coeffs, root); }
   static void div_by_zerofier(std::vector<ArithmeticShare>& inout, size_t n, const Fr& beta) { detail::div_by_zerofier<P, ArithmeticShare>(inout, n, beta); }
+  // the multilinear folds: sumcheck's partially_evaluate (co_sumcheck_prover.rs:34-98), Gemini's compute_fold_polynomials
+  // (co_shplemini_prover.rs:236-312) and evaluate_mle (polynomial.rs:270-312, shared_polynomial.rs:154-199); linear, no network
+  using PartiallyEvaluatePolys = detail::PartiallyEvaluatePolys<P, ArithmeticShare>;
+  static PartiallyEvaluatePolys partially_evaluate(const std::vector<std::vector<Fr>>& pub, const std::vector<std::vector<ArithmeticShare>>& shared, size_t round_size, const Fr& u) {
+    return PartiallyEvaluatePolys(pub, shared, round_size, u);
+  }
+  static std::vector<std::vector<ArithmeticShare>> compute_fold_polynomials(size_t log_n, const std::vector<Fr>& multilinear_challenge, const std::vector<ArithmeticShare>& a_0, bool has_zk) {
+    return detail::compute_fold_polynomials<P, ArithmeticShare>(log_n, multilinear_challenge, a_0, has_zk);
+  }
+  static ArithmeticShare evaluate_mle(const std::vector<ArithmeticShare>& coeffs, const std::vector<Fr>& points) { return detail::evaluate_mle<P, ArithmeticShare>(coeffs, points); }
   // arithmetic::mul_open_vec (rep3/arithmetic.rs:342-354): masked local products, broadcast, sum of the three
   static std::vector<Fr> mul_open_vec(const std::vector<ArithmeticShare>& a, const std::vector<ArithmeticShare>& b, const LocalNetwork& net, State& st) {
     const std::vector<Fr> mine = local_mul_vec(a, b, st);
@@ -386,6 +544,16 @@ struct ShamirPlonkDriver {
   // SharedPolynomial::factor_roots (shared_polynomial.rs:92-140) / div_by_zerofier on Shamir shares: linear, no network
   static void factor_roots(std::vector<Fr>& coeffs, const Fr& root) { detail::factor_roots<P, Fr>(coeffs, root); }
   static void div_by_zerofier(std::vector<Fr>& inout, size_t n, const Fr& beta) { detail::div_by_zerofier<P, Fr>(inout, n, beta); }
+  // the multilinear folds: sumcheck's partially_evaluate (co_sumcheck_prover.rs:34-98), Gemini's compute_fold_polynomials
+  // (co_shplemini_prover.rs:236-312) and evaluate_mle (polynomial.rs:270-312, shared_polynomial.rs:154-199); linear, no network
+  using PartiallyEvaluatePolys = detail::PartiallyEvaluatePolys<P, Fr>;
+  static PartiallyEvaluatePolys partially_evaluate(const std::vector<std::vector<Fr>>& pub, const std::vector<std::vector<Fr>>& shared, size_t round_size, const Fr& u) {
+    return PartiallyEvaluatePolys(pub, shared, round_size, u);
+  }
+  static std::vector<std::vector<Fr>> compute_fold_polynomials(size_t log_n, const std::vector<Fr>& multilinear_challenge, const std::vector<Fr>& a_0, bool has_zk) {
+    return detail::compute_fold_polynomials<P, Fr>(log_n, multilinear_challenge, a_0, has_zk);
+  }
+  static Fr evaluate_mle(const std::vector<Fr>& coeffs, const std::vector<Fr>& points) { return detail::evaluate_mle<P, Fr>(coeffs, points); }
   // arithmetic::mul_open_vec (shamir/arithmetic.rs:262-290): degree-2t products, broadcast_next(n, 2t + 1) (network.rs:96-126),
   // reconstruction with open_lagrange_2t
   static std::vector<Fr> mul_open_vec(const std::vector<Fr>& a, const std::vector<Fr>& b, const LocalNetwork& net, ShamirState<Fr>& st) {

@@ -120,7 +120,7 @@ int csh_device_count(int* count);
  * "stat_uploads_shared"), "host_timing" (diagnostics: phase times of the host-facing witness map in "stat_wm_h2d_us" / "_dev_us" / "_d2h_us"),
  * "msm_balanced" (1 = default: the MSM's windows share the scalar bits evenly, widths c and c - 1; 0 = uniform c-bit windows),
  * "msm_w" (balanced windows: forced number of windows, 0 = the tuned count), "scan_lane_run" / "scan_tile_lanes" / "scan_spine_step"
- * (field scans, see there). Read-only counters
+ * (field scans, see there), "fold_tile_log" (multilinear folds, see there). Read-only counters
  * (csh_tune_get): "stat_arena_grows", "stat_lanes", "stat_populate_us", "stat_join_wait_us", "stat_finish_us", "stat_d2h_slow",
  * "stat_d2h_staged". */
 int csh_tune_set(const char* key, int value);
@@ -351,6 +351,39 @@ int csh_poly_div_linear_dev(csh_curve_t field_of, const uint64_t* in_dev, size_t
                             const uint64_t* scale, int accumulate, uint64_t* out_dev, uint64_t* rem_dev, void* stream);
 int csh_poly_div_linear(csh_curve_t field_of, const uint64_t* in, size_t n, uint32_t ncomp, const uint64_t root[4], const uint64_t* sub0,
                         uint64_t* out, uint64_t* rem);
+
+/* ---- multilinear folds: sumcheck and Gemini rounds, MLE evaluation -----------------------------------------
+ * out[j] = in[2j] + u (in[2j+1] - in[2j]), the whole-vector arithmetic under an UltraHonk prover's sumcheck rounds and Gemini folds.
+ * Linear with a public challenge, so it acts on every component of a Rep3 or Shamir share with no network round. `field_of` is one of the
+ * three scalar fields, ncomp 1 or 2, n <= 2^28; challenges are arkworks-Montgomery elements read on the host during the call. An output
+ * range that overlaps an input range of the same call is refused (CSH_ERR_INVALID): a fold in place is a race between workgroups, so the
+ * reference's in-place loop becomes a ping-pong between two buffers in the caller. Inputs of one call may overlap each other. The _dev
+ * forms are stream-ordered: no host synchronisation, scratch from the stream's workspace. Outputs are canonical. tune key "fold_tile_log"
+ * (3 .. 11, default 10: a workgroup of the several-rounds kernel folds 2^this many elements on chip, which is also the rounds one launch
+ * takes) changes the decomposition only, never a result; csh_tune_set refuses other values. The overlap check compares every output
+ * with every input of the call on the host, k^2 comparisons: made for the k = 40 of a sumcheck round, not for thousands of vectors.
+ * Outputs that overlap EACH OTHER are not looked for: that is the caller's race. */
+/* one round on k vectors of n elements x ncomp: out[v][j] = in[v][2j] + u (in[v][2j+1] - in[v][2j]), j < n/2; n even and >= 2, k >= 1.
+ * partially_evaluate_init / partially_evaluate_inplace, every prover polynomial by the round challenge
+ * (co-noir/co-ultrahonk/src/co_decider/co_sumcheck/co_sumcheck_prover.rs:34-98, co-noir/ultrahonk/src/decider/sumcheck/sumcheck_prover.rs:20-60).
+ * The k pointers travel as kernel arguments, 64 vectors per launch: k > 64 is several launches on the stream, nothing is copied to the device. */
+int csh_mle_fold_dev(csh_curve_t field_of, const uint64_t* const* in_dev /* host array of k device ptrs */,
+                     uint64_t* const* out_dev, size_t k, size_t n, uint32_t ncomp, const uint64_t u[4], void* stream);
+int csh_mle_fold(csh_curve_t field_of, const uint64_t* const* in, uint64_t* const* out, size_t k, size_t n,
+                 uint32_t ncomp, const uint64_t u[4]);
+/* m rounds on one vector, challenges u[0..m) in order; m >= 1 and 2^m divides n (n need not be a power of two). Level l (1..m) has
+ * n / 2^l elements.
+ * levels(_dev), may be NULL: levels 1..m back to back, level l at element offset n - n / 2^(l-1), n - n / 2^m elements in all.
+ * last(_dev), may be NULL: level m alone. At least one of the two is given.
+ * Rounds whose input holds more than 2^21 values (n ncomp) run one per launch, the rest of the chain fused; without
+ * levels those leading rounds take n / 2 + n / 4 elements of the stream's workspace.
+ * compute_fold_polynomials keeps every level (co_shplemini_prover.rs:236-312, shplemini_prover.rs:198); Polynomial::evaluate_mle /
+ * SharedPolynomial::evaluate_mle take `last` with n = 2^m (co-noir-common/src/polynomials/polynomial.rs:270-312,
+ * shared_polynomial.rs:154-199; called at co_sumcheck_prover.rs:435 and sumcheck_prover.rs:334). */
+int csh_mle_fold_rounds_dev(csh_curve_t field_of, const uint64_t* in_dev, size_t n, uint32_t ncomp, const uint64_t* u /* m*4 */,
+                            size_t m, uint64_t* levels_dev, uint64_t* last_dev, void* stream);
+int csh_mle_fold_rounds(csh_curve_t field_of, const uint64_t* in, size_t n, uint32_t ncomp, const uint64_t* u,
+                        size_t m, uint64_t* levels, uint64_t* last);
 
 /* Rep3 correlated masks generated on the device ("next" row f2): out[i] = from_be_bytes_mod_order(a_i) -
  * from_be_bytes_mod_order(b_i), a_i / b_i = the 32-byte chunks number elem_offset{1,2} + i of the ChaCha12 keystreams

@@ -50,3 +50,48 @@ pub fn hip_factor_roots<F: PrimeField, S: Copy + Default>(field: i32, coeffs: &m
     hip_ok(unsafe { sys::csh_poly_div_linear(field, p as *const u64, n, ncomp::<S>(), rt.cast(), s0, p, std::ptr::null_mut()) });
     coeffs.pop();
 }
+
+/// `partially_evaluate_init` / `partially_evaluate_inplace` (co-ultrahonk co_sumcheck_prover.rs:34-98, ultrahonk sumcheck_prover.rs:20-60):
+/// one sumcheck round on a set of equally long polynomials, `dst[v][j] = src[v][2j] + u (src[v][2j+1] - src[v][2j])` on every component
+/// of the share. A fold in place is refused by the library (a race between workgroups), so the reference's in-place loop becomes a
+/// ping-pong: the caller swaps `src` and `dst` after the round, truncates, and pushes a zero if fewer than 2 elements are left, as there.
+pub fn hip_partially_evaluate<F: PrimeField, S: Copy + Default>(field: i32, src: &[&[S]], dst: &mut [Vec<S>], round_size: usize, u: F) {
+    let ins: Vec<*const u64> = src.iter().map(|p| limbs_of(&p[..round_size])).collect();
+    let outs: Vec<*mut u64> = dst
+        .iter_mut()
+        .map(|p| {
+            p.resize(round_size / 2, S::default());
+            limbs_mut(p)
+        })
+        .collect();
+    let ch: *const F = &u;
+    hip_ok(unsafe { sys::csh_mle_fold(field, ins.as_ptr(), outs.as_ptr(), ins.len(), round_size, ncomp::<S>(), ch.cast()) });
+}
+
+/// The folds of `compute_fold_polynomials` (co_shplemini_prover.rs:236-312, shplemini_prover.rs:198): A_1 .. A_(log_n - 1) and
+/// `final_eval`, all log_n rounds in one call. The constant folds of the virtual rounds are scalar arithmetic on `final_eval` and stay
+/// with the caller.
+pub fn hip_fold_polynomials<F: PrimeField, S: Copy + Default>(field: i32, log_n: usize, multilinear_challenge: &[F], a_0: &[S]) -> (Vec<Vec<S>>, S) {
+    let n = 1usize << log_n;
+    let mut levels = vec![S::default(); n - 1];
+    let mut final_eval = S::default();
+    let res: *mut S = &mut final_eval;
+    hip_ok(unsafe {
+        sys::csh_mle_fold_rounds(field, limbs_of(&a_0[..n]), n, ncomp::<S>(), limbs_of(&multilinear_challenge[..log_n]), log_n, limbs_mut(&mut levels), res.cast())
+    });
+    let folds = (1..log_n).map(|l| levels[n - (n >> (l - 1))..n - (n >> l)].to_vec()).collect();
+    (folds, final_eval)
+}
+
+/// `Polynomial::evaluate_mle` / `SharedPolynomial::evaluate_mle` (co-noir-common/src/polynomials/polynomial.rs:270-312,
+/// shared_polynomial.rs:154-199): 2^dim coefficients folded dim times, only the last level comes back; the (1 - u) factors of the
+/// trivial dimensions are scalar arithmetic and stay with the caller.
+pub fn hip_evaluate_mle<F: PrimeField, S: Copy + Default>(field: i32, coeffs: &[S], evaluation_points: &[F]) -> S {
+    let dim = coeffs.len().trailing_zeros() as usize;
+    let mut out = S::default();
+    let res: *mut S = &mut out;
+    hip_ok(unsafe {
+        sys::csh_mle_fold_rounds(field, limbs_of(coeffs), coeffs.len(), ncomp::<S>(), limbs_of(&evaluation_points[..dim]), dim, std::ptr::null_mut(), res.cast())
+    });
+    out
+}
