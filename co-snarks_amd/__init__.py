@@ -38,6 +38,10 @@ from .bindings import (  # noqa: F401
     msm_fold_partials,
     msm_partial_bytes,
     msm_split,
+    plonk_quot_blinders,
+    plonk_quot_combine,
+    plonk_quot_finish,
+    plonk_quot_operands,
     point_bytes,
     rep3_local_mul_vec,
     rep3_to_shamir_vec,

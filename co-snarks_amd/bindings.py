@@ -527,6 +527,52 @@ def mle_fold_rounds(curve: int, vec, us, ncomp: int = 1, n: int | None = None, l
     return lv, la
 
 
+def _devptr_array(bufs):
+    return (C.c_void_p * len(bufs))(*[_devptr(b).value for b in bufs]) if len(bufs) else None
+
+
+def plonk_quot_blinders(dom: "Domain", protocol: int, party: int, blinders, outs, stream=None):
+    """csh_plonk_quot_blinders_dev: stage (a) of the PLONK quotient on the extended domain `dom`. blinders: the host shares b0..b8;
+    outs: the DeviceBuffers ap, bp, cp, zp, zwp (N ncomp elements each), which are returned."""
+    b = _u64(blinders)
+    assert b.size == 9 * 4 * (protocol + 1) and len(outs) == 5
+    _check(lib().csh_plonk_quot_blinders_dev(dom.h, C.c_uint32(protocol), C.c_uint32(party), _p(b), _devptr_array(outs), _stream(stream)))
+    return outs
+
+
+def plonk_quot_operands(dom: "Domain", protocol: int, party: int, shares, public, lagrange, buffer_a, challenges, outs, stream=None):
+    """csh_plonk_quot_operands_dev: stage (b). shares: the 11 DeviceBuffers a, b, c, z, a_b, a_bp, ap_b, ap_bp, ap, bp, cp; public: the 8
+    DeviceBuffers qm, ql, qr, qo, qc, s1, s2, s3; lagrange: the n_public DeviceBuffers L_1..L_np; buffer_a: the n_public host shares;
+    challenges: beta, gamma, k1, k2 on the host; outs: the 10 DeviceBuffers pi, e1, e1z, e2a, e2b, e2c, e3a, e3b, e3c, e3d, which are returned."""
+    ba, ch = _u64(buffer_a), _u64(challenges)
+    npub = len(lagrange)
+    assert len(shares) == 11 and len(public) == 8 and len(outs) == 10 and ch.size == 16 and ba.size == npub * 4 * (protocol + 1)
+    _check(lib().csh_plonk_quot_operands_dev(dom.h, C.c_uint32(protocol), C.c_uint32(party), _devptr_array(shares), _devptr_array(public),
+                                             _devptr_array(lagrange), C.c_size_t(npub), _p(ba) if npub else None, _p(ch), _devptr_array(outs),
+                                             _stream(stream)))
+    return outs
+
+
+def plonk_quot_combine(dom: "Domain", protocol: int, party: int, shares, lagrange1, alpha, outs, stream=None):
+    """csh_plonk_quot_combine_dev: stage (c). shares: the 14 DeviceBuffers e1, e1z, z, zp, e2, e2z_0..3, e3, e3z_0..3; lagrange1: L_1;
+    alpha on the host; outs: the DeviceBuffers t, tz, which are returned."""
+    al = _u64(alpha)
+    assert len(shares) == 14 and len(outs) == 2 and al.size == 4
+    _check(lib().csh_plonk_quot_combine_dev(dom.h, C.c_uint32(protocol), C.c_uint32(party), _devptr_array(shares), _devptr(lagrange1), _p(al),
+                                            _devptr_array(outs), _stream(stream)))
+    return outs
+
+
+def plonk_quot_finish(curve: int, n: int, protocol: int, party: int, ct, ctz, b9_b10, t1, t2, t3, stream=None):
+    """csh_plonk_quot_finish_dev: stage (d) on the coefficient forms ct, ctz (4 n shares each) -> the DeviceBuffers t1, t2 (n + 1 shares)
+    and t3 (n + 6 shares), which are returned."""
+    bb = _u64(b9_b10)
+    assert bb.size == 2 * 4 * (protocol + 1)
+    _check(lib().csh_plonk_quot_finish_dev(curve, C.c_size_t(n), C.c_uint32(protocol), C.c_uint32(party), _devptr(ct), _devptr(ctz), _p(bb),
+                                           _devptr(t1), _devptr(t2), _devptr(t3), _stream(stream)))
+    return t1, t2, t3
+
+
 def rep3_local_mul_vec(curve: int, lhs_ab, rhs_ab, mask=None):
     l, r = _u64(lhs_ab), _u64(rhs_ab)
     n = l.size // 8

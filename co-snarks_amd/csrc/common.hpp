@@ -145,6 +145,8 @@ int rep3_local_mul_sub_dev(csh_curve_t f, const uint64_t* a, const uint64_t* b, 
 int ntt_bit_reverse(csh_curve_t c, uint64_t* data, uint32_t log_n, uint32_t ncomp, hipStream_t st);
 size_t domain_size_of(const Domain* d);
 csh_curve_t domain_curve_of(const Domain* d);
+const void* domain_gen_of(const Domain* d);  // the generator, 32 bytes, arkworks-Montgomery
+int domain_device_of(const Domain* d);
 
 // Process-wide tuning knobs (csh_tune_set / csh_tune_get): read once from the environment at load (CSH_MSM_C, ...),
 // changed at run time through the C ABI -- no getenv on any call path.

@@ -1046,6 +1046,8 @@ int ntt_bit_reverse(csh_curve_t c, uint64_t* data, uint32_t log_n, uint32_t ncom
 
 size_t domain_size_of(const Domain* d) { return d->n; }
 csh_curve_t domain_curve_of(const Domain* d) { return d->curve; }
+const void* domain_gen_of(const Domain* d) { return d->gen; }
+int domain_device_of(const Domain* d) { return d->device; }
 
 }  // namespace csh
 

@@ -15,6 +15,7 @@
 #include "field_scan.hpp"
 #include "mle_fold.hpp"
 #include "msm_digits.hpp"
+#include "plonk_quot.hpp"
 #include "vec_elem.hpp"
 
 using namespace csh;
@@ -495,7 +496,123 @@ static int fold_step_chain_t(const uint64_t* a, const uint64_t* b, const uint64_
   return CSH_OK;
 }
 
+// Host run of the PLONK quotient stages (plonk_quot.hip) with the limb-bound checks on: the argument structs are filled in by the same
+// functions the launchers use, the power tables by pq_pow_tables_at, and every flat index goes through the pq_*_at() function its kernel
+// calls -- on host arrays. `in`, `scalars` and `out` are laid out as the C entry point of the stage takes them (include/cosnarks_hip.h):
+//   stage 0 blinders: scalars = b0..b8; out = ap, bp, cp, zp, zwp
+//   stage 1 operands: in = the 11 shares, the 8 public vectors, then n_public Lagrange vectors; scalars = buffer_a (n_public shares), then
+//                     beta, gamma, k1, k2; out = pi, e1, e1z, e2a, e2b, e2c, e3a, e3b, e3c, e3d
+//   stage 2 combine:  in = the 14 shares, then L_1; scalars = alpha; out = t, tz
+//   stage 3 finish:   N = 4 n; in = ct, ctz; scalars = b9, b10; out = t1, t2, t3
+//   stage 4 tables:   out[0] = z1[0..4), z2[0..4), z3[0..4) as the library derives them from the generator (12 elements)
+template <class F>
+static int plonk_quot_host_t(int stage, const uint64_t* gen_w, size_t N, uint32_t protocol, uint32_t party, const uint64_t* const* in, size_t n_public,
+                             const uint64_t* scalars, uint64_t* const* out) {
+  const F gen = pq_word<F>(gen_w);
+  const PqGeom g{N, protocol + 1, pq_pub_comp(protocol, party)};
+  std::vector<F> hi(pq_pow_hi_count(N)), lo(size_t(1) << PQ_POW_LO_LOG);
+  if (stage == 0 || stage == 1) {
+    PqPowArgs<F> p;
+    p.gd = pq_rp(gen);
+    p.hi = hi.data(), p.lo = lo.data(), p.n_hi = hi.size();
+    for (size_t i = 0; i < hi.size() + lo.size(); ++i) pq_pow_tables_at(p, i);
+  }
+  switch (stage) {
+    case 0: {
+      PqBlindArgs<F> a;
+      a.g = g;
+      pq_blinders_consts(a, gen, scalars, g.ncomp);
+      a.hi = hi.data(), a.lo = lo.data();
+      for (int v = 0; v < 5; ++v) a.out[v] = (F*)out[v];
+      for (int v = 0; v < 5; ++v)
+        for (size_t e = 0; e < g.values(); ++e) pq_blinders_at(a, v, e);
+      return CSH_OK;
+    }
+    case 1: {
+      const uint64_t* const* pub = in + 11;
+      const uint64_t* ch = scalars + 4 * g.ncomp * n_public;
+      const F beta = pq_word<F>(ch), gamma = pq_word<F>(ch + 4), k1 = pq_word<F>(ch + 8), k2 = pq_word<F>(ch + 12);
+      for (size_t j0 = 0; j0 == 0 || j0 < n_public; j0 += PQ_PI_CHUNK) {
+        PqPiArgs<F> p;
+        pq_pi_consts(p, in + 19, scalars, j0, n_public, g.ncomp);
+        p.pi = (F*)out[0];
+        p.g = g;
+        for (size_t e = 0; e < g.values(); ++e) pq_pi_at(p, e);
+      }
+      {
+        PqE1Args<F> a;
+        const F** s[] = {&a.a, &a.b, &a.c, nullptr, &a.a_b, &a.a_bp, &a.ap_b, &a.ap_bp, &a.ap, &a.bp, &a.cp};
+        for (int v = 0; v < 11; ++v)
+          if (s[v]) *s[v] = (const F*)in[v];
+        a.pi = (const F*)out[0];
+        a.qm = (const F*)pub[0], a.ql = (const F*)pub[1], a.qr = (const F*)pub[2], a.qo = (const F*)pub[3], a.qc = (const F*)pub[4];
+        a.e1 = (F*)out[1], a.e1z = (F*)out[2];
+        const PqZ<F> z = pq_z_tables(gen, N);
+        for (int m = 0; m < 4; ++m) a.z1d[m] = pq_rp(z.z1[m]);
+        a.g = g;
+        for (size_t e = 0; e < g.values(); ++e) pq_e1_at(a, pq_e1_lane(a, e), e);
+      }
+      {
+        PqE2Args<F> a;
+        for (int v = 0; v < 3; ++v) a.in[v] = (const F*)in[v], a.out[v] = (F*)out[3 + v];
+        a.bk[0] = beta, a.bk[1] = F::mul(beta, k1), a.bk[2] = F::mul(beta, k2);
+        a.gamma = gamma;
+        a.hi = hi.data(), a.lo = lo.data();
+        a.g = g;
+        for (size_t e = 0; e < g.values(); ++e) pq_e2_at(a, e);
+      }
+      {
+        PqE3Args<F> a;
+        for (int v = 0; v < 3; ++v) a.in[v] = (const F*)in[v], a.s[v] = (const F*)pub[5 + v], a.out[v] = (F*)out[6 + v];
+        a.z = (const F*)in[3];
+        a.e3d = (F*)out[9];
+        a.betad = pq_rp(beta);
+        a.gamma = gamma;
+        a.g = g;
+        for (size_t e = 0; e < g.values(); ++e) pq_e3_at(a, e);
+      }
+      return CSH_OK;
+    }
+    case 2: {
+      PqCombineArgs<F> a;
+      a.g = g;
+      a.e1 = (const F*)in[0], a.e1z = (const F*)in[1], a.z = (const F*)in[2], a.zp = (const F*)in[3], a.e2 = (const F*)in[4], a.e3 = (const F*)in[9];
+      for (int j = 0; j < 4; ++j) a.e2z[j] = (const F*)in[5 + j], a.e3z[j] = (const F*)in[10 + j];
+      a.l1 = (const F*)in[14];
+      a.t = (F*)out[0], a.tz = (F*)out[1];
+      a.k = pq_combine_consts(gen, N, pq_word<F>(scalars));
+      for (size_t e = 0; e < g.values(); ++e) pq_combine_at(a, pq_combine_lane(a, e), e);
+      return CSH_OK;
+    }
+    case 3: {
+      PqFinishArgs<F> a;
+      a.ct = (const F*)in[0], a.ctz = (const F*)in[1];
+      a.t1 = (F*)out[0], a.t2 = (F*)out[1], a.t3 = (F*)out[2];
+      pq_share(a.b9, scalars, g.ncomp);
+      pq_share(a.b10, scalars + 4 * g.ncomp, g.ncomp);
+      a.n = N / 4, a.ncomp = g.ncomp;
+      for (size_t e = 0; e < a.n * a.ncomp; ++e) pq_finish_at(a, e);
+      return CSH_OK;
+    }
+    case 4: {
+      const PqZ<F> z = pq_z_tables(gen, N);
+      memcpy(out[0], &z, sizeof z);
+      return CSH_OK;
+    }
+  }
+  return CSH_ERR_INVALID;
+}
+
 extern "C" {
+
+int csh_selftest_plonk_quot_host(int field_of, int stage, const uint64_t* gen, size_t N, uint32_t protocol, uint32_t party, const uint64_t* const* in,
+                                 size_t n_public, const uint64_t* scalars, uint64_t* const* out) {
+  if (!gen || !out || protocol > 1 || party > 2 || N < 32 || (N & (N - 1)) || stage < 0 || stage > 4) return CSH_ERR_INVALID;
+  if (field_of == CSH_BN254) return plonk_quot_host_t<Bn254Fr>(stage, gen, N, protocol, party, in, n_public, scalars, out);
+  if (field_of == CSH_BLS12_381) return plonk_quot_host_t<Bls381Fr>(stage, gen, N, protocol, party, in, n_public, scalars, out);
+  if (field_of == CSH_BLS12_377) return plonk_quot_host_t<Bls377Fr>(stage, gen, N, protocol, party, in, n_public, scalars, out);
+  return CSH_ERR_INVALID;
+}
 
 int csh_selftest_mle_fold_host(int field_of, const uint64_t* in, size_t n, uint32_t ncomp, int tile_log, const uint64_t* u, size_t m,
                                uint64_t* levels_out) {

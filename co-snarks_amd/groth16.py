@@ -445,6 +445,26 @@ def driver_mle_fold(curve: int, driver: int, op: str, polys_mont, challenges_mon
     return res.reshape(m, 4) if driver == PLAIN else res.reshape(3, m, 2, 4) if driver == REP3 else res.reshape(3, m, 4)
 
 
+def plonk_compute_t(curve: int, n: int, evals_mont, scalars_mont):
+    """PlainPlonkDriver::compute_t of the mirror (Round3::compute_t, co-plonk/src/round3.rs:246-502). evals_mont: a, b, c, z, qm, ql, qr, qo,
+    qc, s1, s2, s3 and the n_public Lagrange vectors, 4 n elements each (a list, or one array); scalars_mont: buffer_a (n_public), b0..b10, beta, gamma, alpha,
+    k1, k2 -> (t1 (n + 1, 4), t2 (n + 1, 4), t3 (n + 6, 4))."""
+    sc = np.ascontiguousarray(scalars_mont, dtype=np.uint64).reshape(-1, 4)
+    n_public = len(sc) - 16
+    if isinstance(evals_mont, np.ndarray):   # the vectors already one after the other
+        ev = np.ascontiguousarray(evals_mont, dtype=np.uint64).reshape(-1)
+    else:
+        ev = np.ascontiguousarray(np.concatenate([np.ascontiguousarray(v, dtype=np.uint64).reshape(-1) for v in evals_mont]))
+    assert ev.size == 16 * n * (12 + n_public)
+    out = np.zeros(4 * (3 * n + 8), dtype=np.uint64)
+    m = glib().cog16_plonk_compute_t(curve, C.c_size_t(n), C.c_size_t(n_public), ev.ctypes.data_as(C.c_void_p), sc.ctypes.data_as(C.c_void_p),
+                                     out.ctypes.data_as(C.c_void_p))
+    if m < 0:
+        raise CoSnarksHipError(glib().cog16_last_error().decode())
+    o = out.reshape(-1, 4)
+    return o[:n + 1], o[n + 1:2 * n + 2], o[2 * n + 2:]
+
+
 def driver_inv_vec(curve: int, driver: int, a_mont, seed: int = 1, leaking_zeros=False, in_place=False):
     """::inv_vec, ::inv_many_in_place (in_place) or ::inv_many_in_place_leaking_zeros (leaking_zeros). Plain: (n, 4); Rep3:
     (3, n, 2, 4); Shamir (three parties, threshold 1): (3, n, 4). The strict forms raise the reference's message on a zero."""

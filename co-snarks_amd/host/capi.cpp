@@ -1219,6 +1219,36 @@ int driver_mle_fold_t(int driver, int op, const uint64_t* polys, size_t npub, si
   return len;
 }
 
+// PlainPlonkDriver::compute_t (plonk_honk.hpp). evals: a, b, c, z, qm, ql, qr, qo, qc, s1, s2, s3, then the n_public Lagrange vectors, 4 n
+// elements each; scalars: buffer_a (n_public), b0..b10, beta, gamma, alpha, k1, k2. out: t1 (n + 1), t2 (n + 1), t3 (n + 6). Returns 3 n + 8.
+template <class P>
+int plonk_compute_t_t(size_t n, size_t n_public, const uint64_t* evals, const uint64_t* scalars, uint64_t* out) {
+  using Fr = typename P::Fr;
+  const size_t N = 4 * n;
+  PlonkQuotientZkey<Fr> zkey;
+  PlonkQuotientInputs<Fr, Fr> in;
+  zkey.domain_size = n;
+  std::vector<Fr>* dst[] = {&in.a, &in.b, &in.c, &in.z, &zkey.qm, &zkey.ql, &zkey.qr, &zkey.qo, &zkey.qc, &zkey.s1, &zkey.s2, &zkey.s3};
+  zkey.lagrange.resize(n_public);
+  for (size_t v = 0; v < 12 + n_public; ++v) {
+    std::vector<Fr>& d = v < 12 ? *dst[v] : zkey.lagrange[v - 12];
+    d.resize(N);
+    memcpy((void*)d.data(), evals + 4 * N * v, 32 * N);
+  }
+  const Fr* sc = reinterpret_cast<const Fr*>(scalars);
+  in.buffer_a.assign(sc, sc + n_public);
+  sc += n_public;
+  for (int j = 0; j < 11; ++j) in.blinders[j] = sc[j];
+  in.beta = sc[11], in.gamma = sc[12], in.alpha = sc[13], zkey.k1 = sc[14], zkey.k2 = sc[15];
+  const PlonkDomains<P> domains(n);
+  const auto t = PlainPlonkDriver<P>::compute_t(domains, zkey, in);
+  for (const auto& v : t) {
+    memcpy(out, v.data(), 32 * v.size());
+    out += 4 * v.size();
+  }
+  return (int)(3 * n + 8);
+}
+
 // ::inv_vec (leaking_zeros = 0), ::inv_many_in_place_leaking_zeros (1) and ::inv_many_in_place (2: inv_vec's protocol, the noir
 // drivers' name and message). Plain: (n, 4); Rep3: [party][n][component][limb]; Shamir (3 parties, threshold 1):
 // [party][n][limb]. The values are shared inside with `seed`; a dealer hands the Shamir parties their double sharings.
@@ -1671,6 +1701,17 @@ int cog16_driver_mle_fold(int curve, int driver, int op, const uint64_t* polys, 
     }
     if (curve == 0) return driver_mle_fold_t<Bn254>(driver, op, polys, npub, nshared, n, challenges, nch, flags, seed, out);
     if (curve == 1) return driver_mle_fold_t<Bls12_381>(driver, op, polys, npub, nshared, n, challenges, nch, flags, seed, out);
+    g_err = "unknown curve";
+    return -1;
+  } catch (const std::exception& e) {
+    g_err = e.what();
+    return -1;
+  }
+}
+int cog16_plonk_compute_t(int curve, size_t n, size_t n_public, const uint64_t* evals, const uint64_t* scalars, uint64_t* out) {
+  try {
+    if (curve == 0) return plonk_compute_t_t<Bn254>(n, n_public, evals, scalars, out);
+    if (curve == 1) return plonk_compute_t_t<Bls12_381>(n, n_public, evals, scalars, out);
     g_err = "unknown curve";
     return -1;
   } catch (const std::exception& e) {

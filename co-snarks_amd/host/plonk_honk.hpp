@@ -16,6 +16,9 @@
 // (co-plonk/src/mpc/rep3.rs:187-260), which is four network multiplication rounds around the same running product -- its opened
 // vector would go through csh_vec_prefix_prod exactly as the plain driver's does below.
 #pragma once
+#include <array>
+#include <memory>
+
 #include "groth16.hpp"
 
 namespace cosnarks {
@@ -363,6 +366,109 @@ inline Proj<typename C::Fq> fast_msm(const std::vector<AffineT<typename C::Fq>>&
   return detail::msm_unchecked<typename C::Fq>(C::CURVE, CSH_G1, bases, scalars.data(), scalars.size());
 }
 
+// What Round3::compute_t (co-plonk/src/round3.rs:246-253) reads: of the zkey the 4 n evaluations of the selector, permutation and Lagrange
+// polynomials and k1, k2; of Round2Polys the 4 n evaluations of a, b, c, z and buffer_a; of the challenges b[0..11), beta, gamma, alpha.
+template <class Fr>
+struct PlonkQuotientZkey {
+  size_t domain_size = 0;
+  std::vector<Fr> qm, ql, qr, qo, qc, s1, s2, s3;  // 4 n evaluations each
+  std::vector<std::vector<Fr>> lagrange;           // n_public >= 1 vectors of 4 n evaluations
+  Fr k1, k2;
+};
+template <class Fr, class Share>
+struct PlonkQuotientInputs {
+  std::vector<Share> a, b, c, z;  // poly_eval_*.eval, polys.z.eval: 4 n each
+  std::vector<Share> buffer_a;    // n_public
+  Share blinders[11];
+  Fr beta, gamma, alpha;
+};
+
+namespace detail {
+// Round3::compute_t for the plain driver, device-resident from the upload to t1, t2, t3: the four stages of csh_plonk_quot_* with the
+// reference's mul_vec rounds (round3.rs:283-295, and the two mul4vec! of 423-428) as csh_vec_mul_dev / csh_vec_add_dev between them and
+// the two iffts (468, 480) as csh_ifft_dev. Nothing comes back to the host in between; every call is on the thread's stream.
+template <class P>
+inline std::array<std::vector<typename P::Fr>, 3> plain_compute_t(const PlonkDomains<P>& domains, const PlonkQuotientZkey<typename P::Fr>& zkey,
+                                                                  const PlonkQuotientInputs<typename P::Fr, typename P::Fr>& in) {
+  using Fr = typename P::Fr;
+  const size_t n = zkey.domain_size, N = 4 * n, n_public = zkey.lagrange.size();
+  if (n < 8 || (n & (n - 1)) || domains.extended_domain.size != N) throw Error("compute_t: domain_size must be a power of two >= 8 with its 4 n domain");
+  if (n_public == 0 || in.buffer_a.size() != n_public) throw Error("compute_t: needs L_1 and one buffer_a share per Lagrange polynomial");
+  const std::vector<Fr>* evals[] = {&in.a, &in.b, &in.c, &in.z, &zkey.qm, &zkey.ql, &zkey.qr, &zkey.qo, &zkey.qc, &zkey.s1, &zkey.s2, &zkey.s3};
+  for (const auto* v : evals)
+    if (v->size() != N) throw Error("compute_t: every evaluation vector has 4 n elements");
+  for (const auto& l : zkey.lagrange)
+    if (l.size() != N) throw Error("compute_t: every evaluation vector has 4 n elements");
+  const csh_domain_t dom = domains.extended_domain.dom;
+  std::vector<std::unique_ptr<DeviceMem>> pool;  // freed together at the end: nothing is released while the stream still works
+  auto fresh = [&](size_t count = 0) {
+    pool.emplace_back(new DeviceMem(sizeof(Fr) * (count ? count : N)));
+    return (uint64_t*)pool.back()->p;
+  };
+  auto up = [&](const std::vector<Fr>& v) {
+    uint64_t* d = fresh();
+    check(csh_memcpy_h2d(d, v.data(), sizeof(Fr) * N), "csh_memcpy_h2d");
+    return d;
+  };
+  auto mul = [&](const uint64_t* x, const uint64_t* y) {  // PlainPlonkDriver::mul_vec
+    uint64_t* o = fresh();
+    check(csh_vec_mul_dev(P::ID, x, y, o, N, nullptr), "csh_vec_mul_dev");
+    return o;
+  };
+  auto add_mul = [&](const uint64_t* acc, const uint64_t* x, const uint64_t* y) {  // add_mul_vec
+    uint64_t* o = fresh();
+    check(csh_vec_add_dev(P::ID, acc, mul(x, y), o, N, 1, nullptr), "csh_vec_add_dev");
+    return o;
+  };
+  const uint64_t *a = up(in.a), *b = up(in.b), *c = up(in.c), *z = up(in.z);
+  const uint64_t* pub[8] = {up(zkey.qm), up(zkey.ql), up(zkey.qr), up(zkey.qo), up(zkey.qc), up(zkey.s1), up(zkey.s2), up(zkey.s3)};
+  std::vector<const uint64_t*> lagrange;
+  for (const auto& l : zkey.lagrange) lagrange.push_back(up(l));
+  // (a)
+  uint64_t* bl[5];
+  for (auto& o : bl) o = fresh();
+  check(csh_plonk_quot_blinders_dev(dom, 0, 0, (const uint64_t*)in.blinders, bl, nullptr), "csh_plonk_quot_blinders_dev");
+  const uint64_t *ap = bl[0], *bp = bl[1], *cp = bl[2], *zp = bl[3], *zwp = bl[4];
+  // round3.rs:283-295
+  const uint64_t *a_b = mul(a, b), *a_bp = mul(a, bp), *ap_b = mul(b, ap), *ap_bp = mul(ap, bp);
+  // (b)
+  const uint64_t* sh[11] = {a, b, c, z, a_b, a_bp, ap_b, ap_bp, ap, bp, cp};
+  uint64_t* op[10];
+  for (auto& o : op) o = fresh();
+  const Fr challenges[4] = {in.beta, in.gamma, zkey.k1, zkey.k2};
+  check(csh_plonk_quot_operands_dev(dom, 0, 0, sh, pub, lagrange.data(), n_public, (const uint64_t*)in.buffer_a.data(), (const uint64_t*)challenges, op,
+                                    nullptr),
+        "csh_plonk_quot_operands_dev");
+  // mul4vec! (round3.rs:20-86) -> r, a0, a1, a2, a3
+  auto mul4vec = [&](const uint64_t* xa, const uint64_t* xb, const uint64_t* xc, const uint64_t* xd, const uint64_t* xdp, const uint64_t* r[5]) {
+    const uint64_t *m_a_b = mul(xa, xb), *m_a_bp = mul(xa, bp), *m_ap_b = mul(ap, xb), *m_ap_bp = mul(ap, bp);
+    const uint64_t *c_d = mul(xc, xd), *c_dp = mul(xc, xdp), *cp_d = mul(cp, xd), *cp_dp = mul(cp, xdp);
+    r[0] = mul(m_a_b, c_d);
+    r[1] = add_mul(add_mul(add_mul(mul(m_ap_b, c_d), m_a_bp, c_d), m_a_b, cp_d), m_a_b, c_dp);
+    r[2] = add_mul(add_mul(add_mul(add_mul(add_mul(mul(m_ap_bp, c_d), m_ap_b, cp_d), m_ap_b, c_dp), m_a_bp, cp_d), m_a_bp, c_dp), m_a_b, cp_dp);
+    r[3] = add_mul(add_mul(add_mul(mul(m_a_bp, cp_dp), m_ap_b, cp_dp), m_ap_bp, c_dp), m_ap_bp, cp_d);
+    r[4] = mul(m_ap_bp, cp_dp);
+  };
+  const uint64_t *e2[5], *e3[5];
+  mul4vec(op[3], op[4], op[5], z, zp, e2);        // e2a, e2b, e2c, e2d = z, dp = zp
+  mul4vec(op[6], op[7], op[8], op[9], zwp, e3);   // e3a, e3b, e3c, e3d, dp = zwp
+  // (c)
+  const uint64_t* cs[14] = {op[1], op[2], z, zp, e2[0], e2[1], e2[2], e2[3], e2[4], e3[0], e3[1], e3[2], e3[3], e3[4]};
+  uint64_t* tt[2] = {fresh(), fresh()};
+  check(csh_plonk_quot_combine_dev(dom, 0, 0, cs, lagrange[0], (const uint64_t*)&in.alpha, tt, nullptr), "csh_plonk_quot_combine_dev");
+  check(csh_ifft_dev(dom, tt[0], 1, nullptr), "csh_ifft_dev");
+  check(csh_ifft_dev(dom, tt[1], 1, nullptr), "csh_ifft_dev");
+  // (d)
+  uint64_t *t1 = fresh(n + 1), *t2 = fresh(n + 1), *t3 = fresh(n + 6);
+  check(csh_plonk_quot_finish_dev(P::ID, n, 0, 0, tt[0], tt[1], (const uint64_t*)&in.blinders[9], t1, t2, t3, nullptr), "csh_plonk_quot_finish_dev");
+  std::array<std::vector<Fr>, 3> out = {std::vector<Fr>(n + 1), std::vector<Fr>(n + 1), std::vector<Fr>(n + 6)};
+  check(csh_memcpy_d2h(out[0].data(), t1, sizeof(Fr) * (n + 1)), "csh_memcpy_d2h");
+  check(csh_memcpy_d2h(out[1].data(), t2, sizeof(Fr) * (n + 1)), "csh_memcpy_d2h");
+  check(csh_memcpy_d2h(out[2].data(), t3, sizeof(Fr) * (n + 6)), "csh_memcpy_d2h");
+  return out;
+}
+}  // namespace detail
+
 // ---- plain drivers (co-plonk/src/mpc/plain.rs, co-noir-common/src/mpc/plain.rs) -----------------------------------
 template <class P>
 struct PlainPlonkDriver {
@@ -401,6 +507,11 @@ struct PlainPlonkDriver {
     return detail::compute_fold_polynomials<P, Fr>(log_n, multilinear_challenge, a_0, has_zk);
   }
   static Fr evaluate_mle(const std::vector<Fr>& coeffs, const std::vector<Fr>& points) { return detail::evaluate_mle<P, Fr>(coeffs, points); }
+  // Round3::compute_t (co-plonk/src/round3.rs:246-502) -> [t1, t2, t3]; the Rep3 and Shamir drivers have none here: their mul_vec is the
+  // network's, the stages themselves (csh_plonk_quot_*) take every share type
+  static std::array<std::vector<Fr>, 3> compute_t(const PlonkDomains<P>& domains, const PlonkQuotientZkey<Fr>& zkey, const PlonkQuotientInputs<Fr, Fr>& in) {
+    return detail::plain_compute_t<P>(domains, zkey, in);
+  }
   // co-plonk plain.rs:127-140 / co-noir plain.rs:240-252: every element's own inverse() there
   static std::vector<Fr> inv_vec(std::vector<Fr> a) {
     if (detail::batch_inverse<P>(a)) throw Error("Cannot invert zero");

@@ -385,6 +385,51 @@ int csh_mle_fold_rounds_dev(csh_curve_t field_of, const uint64_t* in_dev, size_t
 int csh_mle_fold_rounds(csh_curve_t field_of, const uint64_t* in, size_t n, uint32_t ncomp, const uint64_t* u,
                         size_t m, uint64_t* levels, uint64_t* last);
 
+/* ---- circom PLONK quotient: the element-wise stages of round 3 ---------------------------------------------
+ * Round3::compute_t (co-circom/co-plonk/src/round3.rs:246-502) between its mul_vec network rounds: three loops over the N = 4 n points of the
+ * extended domain, then the division by Z_H on coefficient form and the split into t1 / t2 / t3. Affine in the shares with public
+ * coefficients, so no network round. protocol 0 = plain / Shamir (ncomp 1), 1 = Rep3 (ncomp 2, {a, b} interleaved), as
+ * csh_evaluate_constraints_dev; party_id 0..2 decides where a public value is added (add_with_public, mpc-core/src/protocols/rep3/
+ * arithmetic.rs:41-49, shamir/arithmetic.rs:45): protocol 0 and Rep3 party 0 on component a, Rep3 party 1 on b, Rep3 party 2 nowhere.
+ * The first three calls take the EXTENDED domain (created with the snarkjs root roots[pow+2], as PlonkDomains does; at least 32 points);
+ * the library derives root_of_unity_2 = w^(N/4) and the tables z1, z2, z3 (round3.rs:212-242) from its generator, and the powers w^i on
+ * the device. Vectors travel as host arrays of device pointers in the fixed orders given below; a share vector has N ncomp elements, a
+ * public vector N. Challenges and blinding shares are host pointers read during the call, arkworks-Montgomery. Stream-ordered: no host
+ * synchronisation, scratch from the stream's workspace. Outputs are canonical. CSH_ERR_INVALID before any device work: a NULL pointer, a
+ * protocol outside 0..1 or a party outside 0..2, a domain of fewer than 32 points, n < 8 or not a power of two (finish), and any output
+ * range that overlaps an input range or another output of the same call -- the rotations by 4 make a call in place a race. */
+/* (a) the blinding polynomials on the extended domain, round3.rs:269-274 and 339-353. blinders: the shares b0..b8 (9 ncomp elements).
+ * out_dev[0..5) = ap, bp, cp, zp, zwp:  ap[i] = b1 + w^i b0, bp[i] = b3 + w^i b2, cp[i] = b5 + w^i b4, zp[i] = b8 + w^i b7 + w^(2i) b6,
+ * zwp[i] = zp[(i + 4) mod N]. */
+int csh_plonk_quot_blinders_dev(csh_domain_t ext_dom, uint32_t protocol, uint32_t party_id, const uint64_t* blinders /* host, 9 shares */,
+                                uint64_t* const* out_dev /* host array of 5 device ptrs */, void* stream);
+/* (b) gate and permutation operands, round3.rs:320-419.
+ * shares_dev[0..11) = a, b, c, z, a_b, a_bp, ap_b, ap_bp, ap, bp, cp;  public_dev[0..8) = qm, ql, qr, qo, qc, s1, s2, s3 (the zkey's 4 n
+ * evaluations);  lagrange_dev[0..n_public) = the 4 n evaluations of L_1..L_np and buffer_a the n_public shares polys.buffer_a[j] (both may
+ * be NULL when n_public = 0);  challenges = beta, gamma, k1, k2 (4 x 4 words).
+ * out_dev[0..10) = pi, e1, e1z, e2a, e2b, e2c, e3a, e3b, e3c, e3d:  pi = -sum_j L_(j+1) buffer_a[j];  e1 = (qm a_b + ql a + qr b + qo c + pi)
+ * (+) qc;  e1z = qm (a_bp + ap_b + z1[i mod 4] ap_bp) + ql ap + qr bp + qo cp;  e2a, e2b, e2c = a (+) (beta w^i + gamma), b (+) (beta k1 w^i +
+ * gamma), c (+) (beta k2 w^i + gamma);  e3a, e3b, e3c = a (+) (beta s1 + gamma), b (+) (beta s2 + gamma), c (+) (beta s3 + gamma);
+ * e3d[i] = z[(i + 4) mod N]. e2d is z itself and is not copied. The public-input sum takes its Lagrange pointers as kernel arguments,
+ * 16 per launch. */
+int csh_plonk_quot_operands_dev(csh_domain_t ext_dom, uint32_t protocol, uint32_t party_id, const uint64_t* const* shares_dev /* 11 */,
+                                const uint64_t* const* public_dev /* 8 */, const uint64_t* const* lagrange_dev /* n_public */, size_t n_public,
+                                const uint64_t* buffer_a /* host, n_public shares */, const uint64_t* challenges /* host, 4 elements */,
+                                uint64_t* const* out_dev /* 10 */, void* stream);
+/* (c) combine, round3.rs:88-105 (mul4vec_post) and 435-467.
+ * shares_dev[0..14) = e1, e1z, z, zp, e2, e2z_0, e2z_1, e2z_2, e2z_3, e3, e3z_0, e3z_1, e3z_2, e3z_3;  lagrange1_dev = the 4 n evaluations of
+ * L_1;  alpha on the host.  out_dev[0..2) = t, tz:  with X = X_0 + z1[i mod 4] X_1 + z2[i mod 4] X_2 + z3[i mod 4] X_3 for X in {e2z, e3z},
+ * t = e1 + alpha e2 - alpha e3 + alpha^2 L_1 (z (+) -1),  tz = e1z + alpha e2z - alpha e3z + alpha^2 L_1 zp. */
+int csh_plonk_quot_combine_dev(csh_domain_t ext_dom, uint32_t protocol, uint32_t party_id, const uint64_t* const* shares_dev /* 14 */,
+                               const uint64_t* lagrange1_dev, const uint64_t alpha[4], uint64_t* const* out_dev /* 2 */, void* stream);
+/* (d) finish, round3.rs:468-498, on the coefficient forms ct = ifft(t), ctz = ifft(tz) (4 n shares each); n = zkey.domain_size, a power of two
+ * >= 8; b9_b10 = the shares b9, b10 on the host. Division by Z_H per column j < n: q[j] = -ct[j], q[k n + j] = q[(k-1) n + j] - ct[k n + j]
+ * (the reference's in-place loop; no divisibility check, as there); tf = q + ctz;  t1_dev (n + 1 shares) = tf[0..n) ++ [b9],
+ * t2_dev (n + 1) = tf[n..2n) with t2[0] -= b9, ++ [b10],  t3_dev (n + 6) = tf[2n..3n+6) with t3[0] -= b10. */
+int csh_plonk_quot_finish_dev(csh_curve_t field_of, size_t n, uint32_t protocol, uint32_t party_id, const uint64_t* ct_dev,
+                              const uint64_t* ctz_dev, const uint64_t* b9_b10 /* host, 2 shares */, uint64_t* t1_dev, uint64_t* t2_dev,
+                              uint64_t* t3_dev, void* stream);
+
 /* Rep3 correlated masks generated on the device ("next" row f2): out[i] = from_be_bytes_mod_order(a_i) -
  * from_be_bytes_mod_order(b_i), a_i / b_i = the 32-byte chunks number elem_offset{1,2} + i of the ChaCha12 keystreams
  * of seed1 (own key) and seed2 (previous party's key): byte-compatible with Rep3Rand::masking_field_elements_vec

@@ -12,3 +12,5 @@ pub mod drivers;
 pub use drivers::{HipPlainPlonkDriver, HipRep3PlonkDriver, HipShamirPlonkDriver};
 pub mod scans;
 pub use scans::{hip_batch_inverse, hip_eval_poly, hip_prefix_product, hip_div_by_zerofier};
+pub mod round3;
+pub use round3::{hip_quotient_blinders, hip_quotient_combine, hip_quotient_finish, hip_quotient_operands};
