@@ -891,6 +891,8 @@ template <>
 struct LazyOf<Bls381Fr> { using type = Bls381Fr29s; };
 template <>
 struct LazyOf<Bls377Fr> { using type = Bls377Fr29s; };
+template <class F>
+using LzOf = typename LazyOf<F>::type;
 
 // ---- Fp2 = Fp[i]/(i^2 + NR) over the signed lazy field: schoolbook products accumulated double-width with ONE
 // reduction per output component (2 NL^2 + NL^2 mads per component, cheaper than Karatsuba's three full

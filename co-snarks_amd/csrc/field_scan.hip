@@ -7,6 +7,7 @@
 // at a time with a running carry (any tile count, no recursion) -> a per-tile downsweep (the evaluation has none: its spine's carry is the
 // result). Products run in the signed lazy field; field_scan.hpp says which scale every value has.
 #include "field_scan.hpp"
+#include "fr_entry.hpp"
 
 #include <string.h>
 
@@ -14,12 +15,8 @@
 
 namespace csh {
 
-template <class F>
-using LzOf = typename LazyOf<F>::type;
-
 constexpr int SCAN_TILE_MAX = 256;     // lanes of a tile kernel: 4 waves, so that the downsweep's register arrays need no occupancy
 constexpr int SCAN_SPINE_MAX = 1024;   // lanes of the spine
-constexpr size_t SCAN_MAX_N = size_t(1) << 28;
 
 struct ScanPlan {
   int E, lg_e, lanes, lg_lanes, spine, lg_spine;
@@ -393,18 +390,12 @@ static int eval_poly_t(const uint64_t* coeffs, size_t n, uint32_t ncomp, const u
     CSH_HIP(hipMemsetAsync(out, 0, sizeof(F) * ncomp, st));
     return CSH_OK;
   }
-  F x;
-  memcpy(&x, point, sizeof(F));
+  const F x = fr_load<F>(point);
   if (x.is_zero()) {  // the value at 0 is the constant term
     CSH_HIP(hipMemcpyAsync(out, coeffs, sizeof(F) * ncomp, hipMemcpyDeviceToDevice, st));
     return CSH_OK;
   }
-  PowTable<F> pw;  // about 30 squarings on the host: cheaper than a launch
-  LZ sq = LZ::from_fp(x);
-  for (int j = 0; j < SCAN_POWERS; ++j) {
-    pw.p[j] = sq.canonical().pack();
-    sq = LZ::sqr(sq);
-  }
+  const PowTable<F> pw = pow_table<LZ, F>(LZ::from_fp(x));
   const ScanPlan p = scan_plan(n);
   ScanScratch<F> s;
   CSH_TRY(scan_scratch<F>(p, 1, ncomp, st, &s));
@@ -423,16 +414,13 @@ static int poly_div_linear_t(const uint64_t* in, size_t n, uint32_t ncomp, const
     return CSH_OK;
   }
   if (n == 1 && !rem) return CSH_OK;  // no quotient coefficient, and nobody asks for b_0
-  F r, sc;
-  memcpy(&r, root, sizeof(F));
-  const F w = F::inv(r);  // the one inversion, on the host
+  const F w = F::inv(fr_load<F>(root));  // the one inversion, on the host
   const PowTable<F> pw = pow_table<LZ, F>(LZ::from_fp(w));
   DivArgs<F> a;
-  a.c = LZ::from_fp(F::neg(w)).canonical().pack();
+  a.c = fr_to_rprime(F::neg(w));
   a.scaled = scale != nullptr;
   a.accumulate = accumulate;
-  if (scale) memcpy(&sc, scale, sizeof(F));
-  a.scale = scale ? LZ::from_fp(sc).canonical().pack() : F::zero();
+  a.scale = scale ? fr_to_rprime(fr_load<F>(scale)) : F::zero();
   memset(a.sub0, 0, sizeof a.sub0);
   if (sub0) memcpy(a.sub0, sub0, sizeof(F) * ncomp);
   const ScanPlan p = scan_plan(n);
@@ -455,51 +443,41 @@ static int poly_div_linear_t(const uint64_t* in, size_t n, uint32_t ncomp, const
 
 using namespace csh;
 
-#define FR_DISPATCH(field_of, CALL)                                  \
-  switch (field_of) {                                                \
-    case CSH_BN254: { using F = Bn254Fr; return CALL; }              \
-    case CSH_BLS12_381: { using F = Bls381Fr; return CALL; }         \
-    case CSH_BLS12_377: { using F = Bls377Fr; return CALL; }         \
-    default: set_error("unknown curve %d", (int)(field_of)); return CSH_ERR_INVALID; \
-  }
-// the argument checks every entry point makes before it asks for a device
-#define SCAN_REQUIRE_FIELD(f) CSH_REQUIRE((f) == CSH_BN254 || (f) == CSH_BLS12_381 || (f) == CSH_BLS12_377, "field_of: BN254, BLS12-381 or BLS12-377")
-#define SCAN_REQUIRE_N(n) CSH_REQUIRE((n) <= SCAN_MAX_N, "n exceeds 2^28, the largest domain")
-
+// every entry point makes its argument checks (fr_entry.hpp) before it asks for a device
 extern "C" {
 
 int csh_vec_prefix_prod_dev(csh_curve_t f, const uint64_t* in, uint64_t* out, size_t n, void* stream) {
-  SCAN_REQUIRE_FIELD(f);
-  SCAN_REQUIRE_N(n);
+  FR_REQUIRE_FIELD(f);
+  FR_REQUIRE_N(n);
   CSH_REQUIRE(n == 0 || (in && out), "vec_prefix_prod: NULL argument");
   CSH_TRY(ensure_device());
   hipStream_t st = resolve_stream(stream);
-  FR_DISPATCH(f, prefix_prod_t<F>(in, out, n, st));
+  return FR_CALL(f, prefix_prod_t<F>(in, out, n, st));
 }
 int csh_vec_batch_inverse_dev(csh_curve_t f, const uint64_t* in, uint64_t* out, size_t n, uint64_t* zero_count, void* stream) {
-  SCAN_REQUIRE_FIELD(f);
-  SCAN_REQUIRE_N(n);
+  FR_REQUIRE_FIELD(f);
+  FR_REQUIRE_N(n);
   CSH_REQUIRE(n == 0 || (in && out), "vec_batch_inverse: NULL argument");
   CSH_TRY(ensure_device());
   hipStream_t st = resolve_stream(stream);
-  FR_DISPATCH(f, batch_inverse_t<F>(in, out, n, zero_count, st));
+  return FR_CALL(f, batch_inverse_t<F>(in, out, n, zero_count, st));
 }
 int csh_eval_poly_dev(csh_curve_t f, const uint64_t* coeffs, size_t n, uint32_t ncomp, const uint64_t point[4], uint64_t* out, void* stream) {
-  SCAN_REQUIRE_FIELD(f);
-  SCAN_REQUIRE_N(n);
-  CSH_REQUIRE(ncomp >= 1 && ncomp <= 2, "ncomp must be 1 or 2");
+  FR_REQUIRE_FIELD(f);
+  FR_REQUIRE_N(n);
+  FR_REQUIRE_NCOMP(ncomp);
   CSH_REQUIRE(point && out && (n == 0 || coeffs), "eval_poly: NULL argument");
   CSH_TRY(ensure_device());
   hipStream_t st = resolve_stream(stream);
-  FR_DISPATCH(f, eval_poly_t<F>(coeffs, n, ncomp, point, out, st));
+  return FR_CALL(f, eval_poly_t<F>(coeffs, n, ncomp, point, out, st));
 }
 
 // the checks both forms of the division make before they ask for a device
 static int poly_div_linear_check(csh_curve_t f, const uint64_t* in, size_t n, uint32_t ncomp, const uint64_t* root, int accumulate,
                                  const uint64_t* out) {
-  SCAN_REQUIRE_FIELD(f);
-  SCAN_REQUIRE_N(n);
-  CSH_REQUIRE(ncomp >= 1 && ncomp <= 2, "ncomp must be 1 or 2");
+  FR_REQUIRE_FIELD(f);
+  FR_REQUIRE_N(n);
+  FR_REQUIRE_NCOMP(ncomp);
   CSH_REQUIRE(root && (n == 0 || in) && (n <= 1 || out), "poly_div_linear: NULL argument");
   CSH_REQUIRE(root[0] | root[1] | root[2] | root[3], "poly_div_linear: root is 0 -- the quotient by X is a shift of the coefficients, do that instead");
   CSH_REQUIRE(!(accumulate && out == in), "poly_div_linear: accumulate needs out != in");
@@ -510,13 +488,13 @@ int csh_poly_div_linear_dev(csh_curve_t f, const uint64_t* in, size_t n, uint32_
   CSH_TRY(poly_div_linear_check(f, in, n, ncomp, root, accumulate, out));
   CSH_TRY(ensure_device());
   hipStream_t st = resolve_stream(stream);
-  FR_DISPATCH(f, poly_div_linear_t<F>(in, n, ncomp, root, sub0, scale, accumulate, out, rem, st));
+  return FR_CALL(f, poly_div_linear_t<F>(in, n, ncomp, root, sub0, scale, accumulate, out, rem, st));
 }
 
 // ---- host-pointer forms: H2D, compute, D2H on the thread's stream ------------------------------------------------------------------------
 int csh_vec_prefix_prod(csh_curve_t f, const uint64_t* in, uint64_t* out, size_t n) {
-  SCAN_REQUIRE_FIELD(f);
-  SCAN_REQUIRE_N(n);
+  FR_REQUIRE_FIELD(f);
+  FR_REQUIRE_N(n);
   CSH_REQUIRE(n == 0 || (in && out), "vec_prefix_prod: NULL argument");
   HostStage h;
   const size_t eb = 32 * n;
@@ -528,8 +506,8 @@ int csh_vec_prefix_prod(csh_curve_t f, const uint64_t* in, uint64_t* out, size_t
   return h.down(out, d, eb);
 }
 int csh_vec_batch_inverse(csh_curve_t f, const uint64_t* in, uint64_t* out, size_t n, size_t* zero_count) {
-  SCAN_REQUIRE_FIELD(f);
-  SCAN_REQUIRE_N(n);
+  FR_REQUIRE_FIELD(f);
+  FR_REQUIRE_N(n);
   CSH_REQUIRE(n == 0 || (in && out), "vec_batch_inverse: NULL argument");
   HostStage h;
   const size_t eb = 32 * n;
@@ -548,9 +526,9 @@ int csh_vec_batch_inverse(csh_curve_t f, const uint64_t* in, uint64_t* out, size
   return CSH_OK;
 }
 int csh_eval_poly(csh_curve_t f, const uint64_t* coeffs, size_t n, uint32_t ncomp, const uint64_t point[4], uint64_t* out) {
-  SCAN_REQUIRE_FIELD(f);
-  SCAN_REQUIRE_N(n);
-  CSH_REQUIRE(ncomp >= 1 && ncomp <= 2, "ncomp must be 1 or 2");
+  FR_REQUIRE_FIELD(f);
+  FR_REQUIRE_N(n);
+  FR_REQUIRE_NCOMP(ncomp);
   CSH_REQUIRE(point && out && (n == 0 || coeffs), "eval_poly: NULL argument");
   HostStage h;
   const size_t cb = 32 * n * ncomp, ob = 32 * ncomp;

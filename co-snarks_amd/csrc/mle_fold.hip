@@ -22,8 +22,6 @@
 
 namespace csh {
 
-constexpr size_t FOLD_MAX_N = size_t(1) << 28;
-
 // the pointers of one launch, a kernel argument (1 KiB): k > FOLD_VECS_PER_LAUNCH vectors are several launches, nothing is copied to the device
 template <class F>
 struct FoldVecs {
@@ -60,13 +58,9 @@ static int fold_tile_log() {
 
 template <class F>
 static int mle_fold_t(const uint64_t* const* in, uint64_t* const* out, size_t k, size_t n, uint32_t ncomp, const uint64_t u[4], hipStream_t st) {
-  F uf;
-  memcpy(&uf, u, sizeof(F));
-  const F ud = fold_challenge(uf);
+  const F ud = fr_to_rprime(fr_load<F>(u));
   const size_t n_out = n / 2 * ncomp;
-  int mb = tune().vec_max_blocks.load(std::memory_order_relaxed);
-  if (mb <= 0) mb = 65536;
-  const unsigned gx = (unsigned)grid_for(n_out, FOLD_WG, mb);
+  const unsigned gx = (unsigned)fr_stream_grid(n_out, FOLD_WG);
   for (size_t v0 = 0; v0 < k; v0 += FOLD_VECS_PER_LAUNCH) {
     const size_t kk = k - v0 < (size_t)FOLD_VECS_PER_LAUNCH ? k - v0 : (size_t)FOLD_VECS_PER_LAUNCH;
     FoldVecs<F> vs;
@@ -95,9 +89,7 @@ static void launch_fold(const F* in0, F* out0, F* out1, size_t n, uint32_t ncomp
   vs.out[0] = out0;
   vs.out[1] = out1;
   const size_t n_out = n / 2 * ncomp;
-  int mb = tune().vec_max_blocks.load(std::memory_order_relaxed);
-  if (mb <= 0) mb = 65536;
-  hipLaunchKernelGGL(k_mle_fold<F>, dim3((unsigned)grid_for(n_out, FOLD_WG, mb), out1 ? 2u : 1u), dim3(FOLD_WG), 0, st, vs, ud, n_out, ncomp);
+  hipLaunchKernelGGL(k_mle_fold<F>, dim3((unsigned)fr_stream_grid(n_out, FOLD_WG), out1 ? 2u : 1u), dim3(FOLD_WG), 0, st, vs, ud, n_out, ncomp);
 }
 
 template <class F>
@@ -125,28 +117,22 @@ static int mle_fold_rounds_t(const uint64_t* in, size_t n, uint32_t ncomp, const
   }
   const F* src = (const F*)in;
   for (size_t l = 0; l < lead; ++l) {  // level l -> level l + 1
-    F uf;
-    memcpy(&uf, u + 4 * l, sizeof(F));
     const bool final_round = l + 1 == m;
     F* lvl = levels ? (F*)levels + fold_level_offset(n, (int)l + 1) * ncomp : nullptr;
     F* out0 = lvl ? lvl : (final_round ? (F*)last : lead_buf[l & 1]);
     F* out1 = (lvl && final_round) ? (F*)last : nullptr;  // both asked for: the same sweep writes level m twice
-    launch_fold<F>(src, out0, out1, n >> l, ncomp, fold_challenge(uf), st);
+    launch_fold<F>(src, out0, out1, n >> l, ncomp, fr_to_rprime(fr_load<F>(u + 4 * l)), st);
     src = out0;
   }
   if (mf) {
-    const size_t lds = sizeof(int32_t) * LazyOf<F>::type::NL * (fold_plane_a(T, ncomp) + fold_plane_b(T, ncomp));
+    const size_t lds = sizeof(int32_t) * LzOf<F>::NL * (fold_plane_a(T, ncomp) + fold_plane_b(T, ncomp));
     if (lds > 48 * 1024) CSH_TRY(raise_lds_limit((const void*)k_mle_fold_rounds<F>, 160 * 1024));
     F* lev_f = levels ? (F*)levels + fold_level_offset(n, (int)lead + 1) * ncomp : nullptr;  // level lead + 1 = the fused chain's level 1
     for (size_t p = 0; p < launches; ++p) {
       FoldRoundsArgs<F> a;
       memset(&a, 0, sizeof a);
       a.rounds = (int)(mf - p * T < (size_t)T ? mf - p * T : (size_t)T);
-      for (int r = 0; r < a.rounds; ++r) {
-        F uf;
-        memcpy(&uf, u + 4 * (lead + p * T + r), sizeof(F));
-        a.ud[r] = fold_challenge(uf);
-      }
+      for (int r = 0; r < a.rounds; ++r) a.ud[r] = fr_to_rprime(fr_load<F>(u + 4 * (lead + p * T + r)));
       a.in = src;
       a.n_in = nf >> (p * T);
       a.ncomp = ncomp;
@@ -164,41 +150,28 @@ static int mle_fold_rounds_t(const uint64_t* in, size_t n, uint32_t ncomp, const
   return CSH_OK;
 }
 
-static bool ranges_overlap(const void* a, size_t abytes, const void* b, size_t bbytes) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return x < y + bbytes && y < x + abytes;
-}
-
 }  // namespace csh
 
 using namespace csh;
 
-#define FR_DISPATCH(field_of, CALL)                                  \
-  switch (field_of) {                                                \
-    case CSH_BN254: { using F = Bn254Fr; return CALL; }              \
-    case CSH_BLS12_381: { using F = Bls381Fr; return CALL; }         \
-    case CSH_BLS12_377: { using F = Bls377Fr; return CALL; }         \
-    default: set_error("unknown curve %d", (int)(field_of)); return CSH_ERR_INVALID; \
-  }
-
 // the argument rules, checked before either form asks for a device
 static int fold_check_common(csh_curve_t f, size_t n, uint32_t ncomp) {
-  CSH_REQUIRE(f == CSH_BN254 || f == CSH_BLS12_381 || f == CSH_BLS12_377, "field_of: BN254, BLS12-381 or BLS12-377");
-  CSH_REQUIRE(ncomp >= 1 && ncomp <= 2, "ncomp must be 1 or 2");
-  CSH_REQUIRE(n <= FOLD_MAX_N, "n exceeds 2^28, the largest domain");
+  FR_REQUIRE_FIELD(f);
+  FR_REQUIRE_NCOMP(ncomp);
+  FR_REQUIRE_N(n);
   return CSH_OK;
 }
 static int mle_fold_check(csh_curve_t f, const uint64_t* const* in, uint64_t* const* out, size_t k, size_t n, uint32_t ncomp, const uint64_t* u) {
   CSH_TRY(fold_check_common(f, n, ncomp));
   CSH_REQUIRE(n >= 2 && n % 2 == 0, "mle_fold: n must be even and at least 2");
   CSH_REQUIRE(k >= 1, "mle_fold: k must be at least 1");
-  CSH_REQUIRE(in && out && u, "mle_fold: NULL argument");
-  for (size_t v = 0; v < k; ++v) CSH_REQUIRE(in[v] && out[v], "mle_fold: NULL argument");
-  const size_t ib = 32 * n * ncomp, ob = ib / 2;
-  for (size_t v = 0; v < k; ++v)
-    for (size_t w = 0; w < k; ++w)
-      CSH_REQUIRE(!ranges_overlap(out[v], ob, in[w], ib), "mle_fold: an output overlaps an input (fold into a second buffer and swap)");
-  return CSH_OK;
+  CSH_REQUIRE(u, "mle_fold: NULL argument");
+  CSH_TRY(fr_require_ptrs((const void* const*)in, k, "mle_fold"));
+  CSH_TRY(fr_require_ptrs((const void* const*)out, k, "mle_fold"));
+  FrRanges ins, outs;  // an output may not overlap any vector's input: fold into a second buffer and swap
+  ins.add((const void* const*)in, k, 32 * n * ncomp);
+  outs.add((const void* const*)out, k, 16 * n * ncomp);
+  return fr_check_ranges(ins, outs, "mle_fold", false);
 }
 static int mle_fold_rounds_check(csh_curve_t f, const uint64_t* in, size_t n, uint32_t ncomp, const uint64_t* u, size_t m, const uint64_t* levels,
                                  const uint64_t* last) {
@@ -206,10 +179,11 @@ static int mle_fold_rounds_check(csh_curve_t f, const uint64_t* in, size_t n, ui
   CSH_REQUIRE(m >= 1 && m <= 28 && n >= 2 && (n & ((size_t(1) << m) - 1)) == 0, "mle_fold_rounds: m must be at least 1 and 2^m must divide n");
   CSH_REQUIRE(in && u, "mle_fold_rounds: NULL argument");
   CSH_REQUIRE(levels || last, "mle_fold_rounds: one of levels and last must be given");
-  const size_t ib = 32 * n * ncomp, lb = 32 * (n - (n >> m)) * ncomp, eb = 32 * (n >> m) * ncomp;
-  CSH_REQUIRE(!(levels && ranges_overlap(levels, lb, in, ib)) && !(last && ranges_overlap(last, eb, in, ib)),
-              "mle_fold_rounds: an output overlaps the input");
-  return CSH_OK;
+  FrRanges ins, outs;
+  ins.add(in, 32 * n * ncomp);
+  if (levels) outs.add(levels, 32 * (n - (n >> m)) * ncomp);
+  if (last) outs.add(last, 32 * (n >> m) * ncomp);
+  return fr_check_ranges(ins, outs, "mle_fold_rounds", false);
 }
 
 extern "C" {
@@ -219,14 +193,14 @@ int csh_mle_fold_dev(csh_curve_t f, const uint64_t* const* in, uint64_t* const* 
   CSH_TRY(mle_fold_check(f, in, out, k, n, ncomp, u));
   CSH_TRY(ensure_device());
   hipStream_t st = resolve_stream(stream);
-  FR_DISPATCH(f, mle_fold_t<F>(in, out, k, n, ncomp, u, st));
+  return FR_CALL(f, mle_fold_t<F>(in, out, k, n, ncomp, u, st));
 }
 int csh_mle_fold_rounds_dev(csh_curve_t f, const uint64_t* in, size_t n, uint32_t ncomp, const uint64_t* u, size_t m, uint64_t* levels,
                             uint64_t* last, void* stream) {
   CSH_TRY(mle_fold_rounds_check(f, in, n, ncomp, u, m, levels, last));
   CSH_TRY(ensure_device());
   hipStream_t st = resolve_stream(stream);
-  FR_DISPATCH(f, mle_fold_rounds_t<F>(in, n, ncomp, u, m, levels, last, st));
+  return FR_CALL(f, mle_fold_rounds_t<F>(in, n, ncomp, u, m, levels, last, st));
 }
 
 // ---- host-pointer forms: H2D, compute, D2H on the thread's stream --------------------------------------------------------------------

@@ -1,7 +1,7 @@
 // Multilinear folds out[j] = in[2j] + u (in[2j+1] - in[2j]) (mle_fold.hip): what the two kernels and the host
 // self-test (selftest.hip, limb-bound checks on) share -- the challenge's scale, the index algebra of a tile, and the bound derivation.
 //
-// Scale. Elements are arkworks-Montgomery (R scale, field_scan.hpp). fold_challenge() brings u to the R' domain once per call on the host;
+// Scale. Elements are arkworks-Montgomery (R scale, field_scan.hpp). fr_to_rprime() (fr_entry.hpp) brings u to the R' domain once per call on the host;
 // mul(b - a, ud) = (b - a) R u R' / R' is then R scale again, like a and b: no product multiplies two loaded operands, nothing is
 // scaled by 32 on the device.
 //
@@ -21,6 +21,7 @@
 #include "common.hpp"
 #include "field.hpp"
 #include "field29.hpp"
+#include "fr_entry.hpp"
 #include "vec_elem.hpp"
 
 namespace csh {
@@ -28,13 +29,6 @@ namespace csh {
 constexpr int FOLD_WG = 256;          // lanes of a k_mle_fold_rounds workgroup
 constexpr int FOLD_MAX_ROUNDS = FOLD_TILE_LOG_MAX;
 constexpr int FOLD_VECS_PER_LAUNCH = 64;  // vectors of one k_mle_fold launch (their pointers travel as kernel arguments)
-
-// u (arkworks Montgomery) -> u R' mod p, canonical and packed
-template <class F>
-CSH_HD F fold_challenge(const F& u) {
-  using LZ = typename LazyOf<F>::type;
-  return LZ::from_fp(u).canonical().pack();
-}
 
 // Flat indexing of a vector of n elements x ncomp interleaved components (ncomp 1 or 2). Output value o = j ncomp + c of a round reads
 // the input values 2 o - c (element 2 j) and 2 o - c + ncomp (element 2 j + 1).

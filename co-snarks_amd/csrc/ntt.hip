@@ -25,6 +25,7 @@
 #include "common.hpp"
 #include "field.hpp"
 #include "field29.hpp"
+#include "fr_entry.hpp"
 
 namespace csh {
 
@@ -621,26 +622,7 @@ __global__ __launch_bounds__(256) void k_powers_lazy_scaled(F* out, F base, F sc
   }
 }
 
-// ---- host-side helpers -----------------------------------------------------------------------------
-template <class F>
-static F f_from_words(const void* p) {
-  F f;
-  memcpy(&f, p, sizeof(F));
-  return f;
-}
-
-// the field type of a curve's scalar field, handed to a generic callable as a tag: with_fr(curve, [&](auto fr) -> int { using F = typename decltype(fr)::type; ... })
-template <class F>
-struct FrTag {
-  using type = F;
-};
-template <class Fn>
-static int with_fr(csh_curve_t curve, Fn&& f) {
-  if (curve == CSH_BN254) return f(FrTag<Bn254Fr>{});
-  if (curve == CSH_BLS12_377) return f(FrTag<Bls377Fr>{});
-  return f(FrTag<Bls381Fr>{});
-}
-
+// ---- host-side helpers (curve -> F, bytes -> F: fr_entry.hpp) ------------------------------------------
 struct Pass {
   int s0, k, cb;
 };
@@ -783,8 +765,8 @@ static hipError_t build_natural_tables(Domain* d, hipStream_t st) {
   if (e == hipSuccess) e = hipMalloc(&d->tw_inv, half * sizeof(F));
   if (e != hipSuccess) return e;
   const dim3 grid(grid_for((half + POW_CHUNK - 1) / POW_CHUNK, 256));
-  hipLaunchKernelGGL((k_powers<F, false>), grid, dim3(256), 0, st, (F*)d->tw_fwd, f_from_words<F>(d->gen), half, 0);
-  hipLaunchKernelGGL((k_powers<F, false>), grid, dim3(256), 0, st, (F*)d->tw_inv, f_from_words<F>(d->gen_inv), half, 0);
+  hipLaunchKernelGGL((k_powers<F, false>), grid, dim3(256), 0, st, (F*)d->tw_fwd, fr_load<F>(d->gen), half, 0);
+  hipLaunchKernelGGL((k_powers<F, false>), grid, dim3(256), 0, st, (F*)d->tw_inv, fr_load<F>(d->gen_inv), half, 0);
   return hipGetLastError();
 }
 
@@ -830,7 +812,7 @@ static PassArgs<F> pass_args(const NttPlan& plan, const Domain* d, F* data, cons
   a.k = p.k;
   a.cb = p.cb;
   a.ncomp_log = plan.ncomp_log;
-  a.scale = f_from_words<F>(plan.lazy ? d->n_inv_lazy : d->n_inv);
+  a.scale = fr_load<F>(plan.lazy ? d->n_inv_lazy : d->n_inv);
   a.scale_tbl = scale_out ? scale_tbl : nullptr;
   a.scale_out = scale_out;
   a.swz_mask = plan.swz_mask;
@@ -863,14 +845,14 @@ static int run_passes(const NttPlan& plan, const Domain* d, F* data, bool dif, h
 }
 
 template <class F>
-static int create_domain_t(csh_curve_t curve, uint32_t log_n, const uint64_t* gen_words, uint64_t ark_generator, Domain** out) {
+static int create_domain_t(csh_curve_t curve, uint32_t log_n, const uint64_t* gen_words, Domain** out) {
   if (log_n > (uint32_t)F::Params::TWO_ADICITY) {
     set_error("Polynomial Degree too large");
     return CSH_ERR_DOMAIN;
   }
   F gen;
   if (gen_words) {
-    gen = f_from_words<F>(gen_words);
+    gen = fr_load<F>(gen_words);
   } else {
     // GENERATOR^TRACE has order 2^TWO_ADICITY; TRACE = (p-1) >> TWO_ADICITY
     uint32_t tr[F::N];
@@ -884,7 +866,7 @@ static int create_domain_t(csh_curve_t curve, uint32_t log_n, const uint64_t* ge
       const uint64_t hi2 = wi + 1 < F::N ? pm1[wi + 1] : 0;
       tr[i] = (uint32_t)((lo | (hi2 << 32)) >> (s % 32));
     }
-    F g = F::from_u64(ark_generator);
+    F g = F::from_u64(std::is_same<F, Bn254Fr>::value ? 5 : std::is_same<F, Bls381Fr>::value ? 7 : 22);  // ark_{bn254, bls12_381, bls12_377}::Fr::GENERATOR
     gen = F::pow_limbs(g, tr, F::N);
     for (uint32_t i = log_n; i < (uint32_t)s; ++i) gen = F::sqr(gen);
   }
@@ -966,17 +948,11 @@ static int run_ntt_pair(const Domain* d, F* data, uint32_t ncomp, hipStream_t st
   return run_passes<F>(plan, d, data, false, st, nullptr, 1);  // the strided passes of the forward transform
 }
 int ntt_run_pair_table(const Domain* d, uint64_t* data, uint32_t ncomp, const uint64_t* scale_table, hipStream_t st) {
-  return with_fr(d->curve, [&](auto fr) -> int {
-    using F = typename decltype(fr)::type;
-    return run_ntt_pair<F>(d, (F*)data, ncomp, st, (const F*)scale_table);
-  });
+  return FR_CALL(d->curve, run_ntt_pair<F>(d, (F*)data, ncomp, st, (const F*)scale_table));
 }
 
 int ntt_run(const Domain* d, uint64_t* data, uint32_t ncomp, bool dif, hipStream_t st) {
-  return with_fr(d->curve, [&](auto fr) -> int {
-    using F = typename decltype(fr)::type;
-    return run_passes<F>(NttPlan((int)d->log_n, ncomp), d, (F*)data, dif, st);
-  });
+  return FR_CALL(d->curve, run_passes<F>(NttPlan((int)d->log_n, ncomp), d, (F*)data, dif, st));
 }
 // whether ntt_run_pair_table / ntt_coset_table_scaled apply (the table is in the lazy passes' storage form); false when the lazy
 // passes are switched off (the caller then runs the unfused sequence)
@@ -985,9 +961,8 @@ bool ntt_scale_table_supported(const Domain* d) { return tune().ntt_lazy.load(st
 int ntt_coset_table_scaled(const Domain* d, const uint64_t* shift, uint64_t* out_dev, hipStream_t st) {
   return with_fr(d->curve, [&](auto fr) -> int {
     using F = typename decltype(fr)::type;
-    using LZ = typename LazyOf<F>::type;
-    hipLaunchKernelGGL((k_powers_lazy_scaled<F, LZ>), dim3(grid_for((d->n + POW_CHUNK - 1) / POW_CHUNK, 256)), dim3(256), 0, st, (F*)out_dev, f_from_words<F>(shift),
-                       f_from_words<F>(d->n_inv), d->n, (int)d->log_n);
+    hipLaunchKernelGGL((k_powers_lazy_scaled<F, LzOf<F>>), dim3(grid_for((d->n + POW_CHUNK - 1) / POW_CHUNK, 256)), dim3(256), 0, st, (F*)out_dev, fr_load<F>(shift),
+                       fr_load<F>(d->n_inv), d->n, (int)d->log_n);
     CSH_HIP(hipGetLastError());
     return CSH_OK;
   });
@@ -1028,7 +1003,7 @@ int ntt_coset_table_scaled_cached(const Domain* dc, const uint64_t* shift, uint6
 int ntt_coset_table(const Domain* d, const uint64_t* shift, uint64_t* out_dev, hipStream_t st) {
   return with_fr(d->curve, [&](auto fr) -> int {
     using F = typename decltype(fr)::type;
-    hipLaunchKernelGGL((k_powers<F, true>), dim3(grid_for((d->n + POW_CHUNK - 1) / POW_CHUNK, 256)), dim3(256), 0, st, (F*)out_dev, f_from_words<F>(shift), d->n,
+    hipLaunchKernelGGL((k_powers<F, true>), dim3(grid_for((d->n + POW_CHUNK - 1) / POW_CHUNK, 256)), dim3(256), 0, st, (F*)out_dev, fr_load<F>(shift), d->n,
                        (int)d->log_n);
     CSH_HIP(hipGetLastError());
     return CSH_OK;
@@ -1055,7 +1030,7 @@ using namespace csh;
 
 static int check_dom(csh_domain_t dom, uint32_t ncomp) {
   CSH_REQUIRE(dom, "domain is NULL");
-  CSH_REQUIRE(ncomp == 1 || ncomp == 2, "ncomp must be 1 or 2");
+  FR_REQUIRE_NCOMP(ncomp);
   int cur = -1;
   const Domain* d = reinterpret_cast<const Domain*>(dom);
   if (hipGetDevice(&cur) == hipSuccess && cur != d->device) {
@@ -1071,20 +1046,8 @@ int csh_domain_create(csh_curve_t field_of, uint32_t log_n, const uint64_t group
   CSH_REQUIRE(out, "out is NULL");
   CSH_REQUIRE(log_n <= 31, "log_n too large");
   CSH_TRY(ensure_device());
-  uint64_t ark_generator;  // ark_{bn254, bls12_381, bls12_377}::Fr::GENERATOR
-  if (field_of == CSH_BN254)
-    ark_generator = 5;
-  else if (field_of == CSH_BLS12_381)
-    ark_generator = 7;
-  else if (field_of == CSH_BLS12_377)
-    ark_generator = 22;
-  else {
-    set_error("unknown curve %d", (int)field_of);
-    return CSH_ERR_INVALID;
-  }
   Domain* d = nullptr;
-  const int rc = with_fr(field_of, [&](auto fr) -> int { return create_domain_t<typename decltype(fr)::type>(field_of, log_n, group_gen, ark_generator, &d); });
-  if (rc != CSH_OK) return rc;
+  CSH_TRY(FR_CALL(field_of, create_domain_t<F>(field_of, log_n, group_gen, &d)));
   *out = reinterpret_cast<csh_domain_t>(d);
   return CSH_OK;
 }
@@ -1127,8 +1090,8 @@ int csh_ifft_dev(csh_domain_t dom, uint64_t* data, uint32_t ncomp, void* stream)
   return ntt_bit_reverse(d->curve, data, d->log_n, ncomp, st);
 }
 int csh_bit_reverse_dev(csh_curve_t field_of, uint64_t* data, uint32_t log_n, uint32_t ncomp, void* stream) {
-  CSH_REQUIRE(ncomp == 1 || ncomp == 2, "ncomp must be 1 or 2");
-  CSH_REQUIRE(field_of == CSH_BN254 || field_of == CSH_BLS12_381 || field_of == CSH_BLS12_377, "unknown curve");
+  FR_REQUIRE_NCOMP(ncomp);
+  CSH_REQUIRE(fr_known(field_of), "unknown curve");
   CSH_REQUIRE(log_n <= 31, "log_n too large");
   CSH_TRY(ensure_device());
   return ntt_bit_reverse(field_of, data, log_n, ncomp, resolve_stream(stream));

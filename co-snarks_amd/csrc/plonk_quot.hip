@@ -14,8 +14,6 @@
 
 namespace csh {
 
-constexpr size_t PQ_MAX_N = size_t(1) << 28;
-
 template <class F>
 __global__ __launch_bounds__(PQ_WG) void k_pq_pow_tables(PqPowArgs<F> a) {
   const size_t total = a.n_hi + (size_t(1) << PQ_POW_LO_LOG);
@@ -56,25 +54,19 @@ __global__ __launch_bounds__(PQ_WG) void k_pq_finish(PqFinishArgs<F> a) {
   for (size_t e = blockIdx.x * (size_t)PQ_WG + threadIdx.x; e < nv; e += (size_t)gridDim.x * PQ_WG) pq_finish_at(a, e);
 }
 
-static unsigned pq_grid(size_t values) {
-  int mb = tune().vec_max_blocks.load(std::memory_order_relaxed);
-  if (mb <= 0) mb = 65536;
-  return (unsigned)grid_for(values, PQ_WG, mb);
-}
-
 // the two-level power table of the domain's generator, in the stream's workspace (valid for work queued on `st` until the next call that
 // takes workspace on it)
 template <class F>
 static int pq_power_tables(const F& gen, size_t N, hipStream_t st, const F** hi, const F** lo) {
   PqPowArgs<F> a;
-  a.gd = pq_rp(gen);
+  a.gd = fr_to_rprime(gen);
   a.n_hi = pq_pow_hi_count(N);
   const size_t n_lo = size_t(1) << PQ_POW_LO_LOG;
   Arena& ar = arena_for(st);
   CSH_TRY(ar.reserve(Arena::padded(a.n_hi * sizeof(F)) + Arena::padded(n_lo * sizeof(F))));
   a.hi = ar.take<F>(a.n_hi);
   a.lo = ar.take<F>(n_lo);
-  hipLaunchKernelGGL(k_pq_pow_tables<F>, dim3(pq_grid(a.n_hi + n_lo)), dim3(PQ_WG), 0, st, a);
+  hipLaunchKernelGGL(k_pq_pow_tables<F>, dim3(fr_stream_grid(a.n_hi + n_lo, PQ_WG)), dim3(PQ_WG), 0, st, a);
   *hi = a.hi;
   *lo = a.lo;
   return CSH_OK;
@@ -84,13 +76,13 @@ static PqGeom pq_geom(size_t N, uint32_t protocol, uint32_t party) { return PqGe
 
 template <class F>
 static int blinders_t(const Domain* d, uint32_t protocol, uint32_t party, const uint64_t* blinders, uint64_t* const* out, hipStream_t st) {
-  const F gen = pq_word<F>(domain_gen_of(d));
+  const F gen = fr_load<F>(domain_gen_of(d));
   PqBlindArgs<F> a;
   a.g = pq_geom(domain_size_of(d), protocol, party);
   pq_blinders_consts(a, gen, blinders, a.g.ncomp);
   CSH_TRY(pq_power_tables<F>(gen, a.g.N, st, &a.hi, &a.lo));
   for (int v = 0; v < 5; ++v) a.out[v] = (F*)out[v];
-  hipLaunchKernelGGL(k_pq_blinders<F>, dim3(pq_grid(a.g.values()), 5), dim3(PQ_WG), 0, st, a);
+  hipLaunchKernelGGL(k_pq_blinders<F>, dim3(fr_stream_grid(a.g.values(), PQ_WG), 5), dim3(PQ_WG), 0, st, a);
   CSH_HIP(hipGetLastError());
   return CSH_OK;
 }
@@ -99,10 +91,10 @@ template <class F>
 static int operands_t(const Domain* d, uint32_t protocol, uint32_t party, const uint64_t* const* sh, const uint64_t* const* pub,
                       const uint64_t* const* lagrange, size_t n_public, const uint64_t* buffer_a, const uint64_t* ch, uint64_t* const* out,
                       hipStream_t st) {
-  const F gen = pq_word<F>(domain_gen_of(d));
+  const F gen = fr_load<F>(domain_gen_of(d));
   const PqGeom g = pq_geom(domain_size_of(d), protocol, party);
-  const dim3 grid(pq_grid(g.values())), wg(PQ_WG);
-  const F beta = pq_word<F>(ch), gamma = pq_word<F>(ch + 4), k1 = pq_word<F>(ch + 8), k2 = pq_word<F>(ch + 12);
+  const dim3 grid(fr_stream_grid(g.values(), PQ_WG)), wg(PQ_WG);
+  const F beta = fr_load<F>(ch), gamma = fr_load<F>(ch + 4), k1 = fr_load<F>(ch + 8), k2 = fr_load<F>(ch + 12);
   // pi: ceil(n_public / PQ_PI_CHUNK) launches, at least one (n_public = 0 writes zeros)
   for (size_t j0 = 0; j0 == 0 || j0 < n_public; j0 += PQ_PI_CHUNK) {
     PqPiArgs<F> p;
@@ -120,7 +112,7 @@ static int operands_t(const Domain* d, uint32_t protocol, uint32_t party, const 
     a.qm = (const F*)pub[0], a.ql = (const F*)pub[1], a.qr = (const F*)pub[2], a.qo = (const F*)pub[3], a.qc = (const F*)pub[4];
     a.e1 = (F*)out[1], a.e1z = (F*)out[2];
     const PqZ<F> z = pq_z_tables(gen, g.N);
-    for (int m = 0; m < 4; ++m) a.z1d[m] = pq_rp(z.z1[m]);
+    for (int m = 0; m < 4; ++m) a.z1d[m] = fr_to_rprime(z.z1[m]);
     a.g = g;
     hipLaunchKernelGGL(k_pq_e1<F>, grid, wg, 0, st, a);
   }
@@ -138,7 +130,7 @@ static int operands_t(const Domain* d, uint32_t protocol, uint32_t party, const 
     for (int v = 0; v < 3; ++v) a.in[v] = (const F*)sh[v], a.s[v] = (const F*)pub[5 + v], a.out[v] = (F*)out[6 + v];
     a.z = (const F*)sh[3];
     a.e3d = (F*)out[9];
-    a.betad = pq_rp(beta);
+    a.betad = fr_to_rprime(beta);
     a.gamma = gamma;
     a.g = g;
     hipLaunchKernelGGL(k_pq_e3<F>, grid, wg, 0, st, a);
@@ -156,8 +148,8 @@ static int combine_t(const Domain* d, uint32_t protocol, uint32_t party, const u
   for (int j = 0; j < 4; ++j) a.e2z[j] = (const F*)sh[5 + j], a.e3z[j] = (const F*)sh[10 + j];
   a.l1 = (const F*)l1;
   a.t = (F*)out[0], a.tz = (F*)out[1];
-  a.k = pq_combine_consts(pq_word<F>(domain_gen_of(d)), a.g.N, pq_word<F>(alpha));
-  hipLaunchKernelGGL(k_pq_combine<F>, dim3(pq_grid(a.g.values())), dim3(PQ_WG), 0, st, a);
+  a.k = pq_combine_consts(fr_load<F>(domain_gen_of(d)), a.g.N, fr_load<F>(alpha));
+  hipLaunchKernelGGL(k_pq_combine<F>, dim3(fr_stream_grid(a.g.values(), PQ_WG)), dim3(PQ_WG), 0, st, a);
   CSH_HIP(hipGetLastError());
   return CSH_OK;
 }
@@ -171,34 +163,8 @@ static int finish_t(size_t n, uint32_t ncomp, const uint64_t* ct, const uint64_t
   pq_share(a.b9, b9_b10, ncomp);
   pq_share(a.b10, b9_b10 + 4 * ncomp, ncomp);
   a.n = n, a.ncomp = ncomp;
-  hipLaunchKernelGGL(k_pq_finish<F>, dim3(pq_grid(n * ncomp)), dim3(PQ_WG), 0, st, a);
+  hipLaunchKernelGGL(k_pq_finish<F>, dim3(fr_stream_grid(n * ncomp, PQ_WG)), dim3(PQ_WG), 0, st, a);
   CSH_HIP(hipGetLastError());
-  return CSH_OK;
-}
-
-struct PqRange {
-  const void* p;
-  size_t bytes;
-};
-static bool pq_overlap(const PqRange& a, const PqRange& b) {
-  const uintptr_t x = (uintptr_t)a.p, y = (uintptr_t)b.p;
-  return x < y + b.bytes && y < x + a.bytes;
-}
-// no output may overlap an input or another output: the rotations by 4 (zwp, e3d) and the chunked columns of the finish make a call in
-// place a race between workgroups
-static int pq_check_ranges(const std::vector<PqRange>& in, const std::vector<PqRange>& out, const char* what) {
-  for (size_t o = 0; o < out.size(); ++o) {
-    for (const PqRange& r : in)
-      if (pq_overlap(out[o], r)) {
-        set_error("%s: an output overlaps an input", what);
-        return CSH_ERR_INVALID;
-      }
-    for (size_t q = 0; q < o; ++q)
-      if (pq_overlap(out[o], out[q])) {
-        set_error("%s: two outputs overlap", what);
-        return CSH_ERR_INVALID;
-      }
-  }
   return CSH_OK;
 }
 
@@ -206,13 +172,8 @@ static int pq_check_ranges(const std::vector<PqRange>& in, const std::vector<PqR
 
 using namespace csh;
 
-#define FR_DISPATCH(field_of, CALL)                                  \
-  switch (field_of) {                                                \
-    case CSH_BN254: { using F = Bn254Fr; return CALL; }              \
-    case CSH_BLS12_381: { using F = Bls381Fr; return CALL; }         \
-    case CSH_BLS12_377: { using F = Bls377Fr; return CALL; }         \
-    default: set_error("unknown curve %d", (int)(field_of)); return CSH_ERR_INVALID; \
-  }
+// No output of a call may overlap an input or another output (fr_check_ranges): the rotations by 4 (zwp, e3d) and the chunked columns of
+// the finish make a call in place a race between workgroups.
 
 static int pq_check_party(uint32_t protocol, uint32_t party, const char* what) {
   if (protocol > 1 || party > 2) {
@@ -221,20 +182,10 @@ static int pq_check_party(uint32_t protocol, uint32_t party, const char* what) {
   }
   return CSH_OK;
 }
-static int pq_check_ptrs(const void* const* p, size_t k, const char* what) {
-  if (p)
-    for (size_t v = 0; v < k; ++v)
-      if (!p[v]) p = nullptr;
-  if (!p && k) {
-    set_error("%s: NULL argument", what);
-    return CSH_ERR_INVALID;
-  }
-  return CSH_OK;
-}
 // a domain handle exists only in a process that has a device, so it is looked into after ensure_device() and before any launch
 static int pq_check_domain(const Domain* d, const char* what) {
   const size_t N = domain_size_of(d);
-  if (N < 32 || N > PQ_MAX_N) {
+  if (N < 32 || N > FR_MAX_N) {
     set_error("%s: the extended domain must have 32 .. 2^28 points (n >= 8)", what);
     return CSH_ERR_INVALID;
   }
@@ -245,9 +196,6 @@ static int pq_check_domain(const Domain* d, const char* what) {
   }
   return CSH_OK;
 }
-static void pq_add(std::vector<PqRange>& r, const void* const* p, size_t k, size_t bytes) {
-  for (size_t v = 0; v < k; ++v) r.push_back(PqRange{p[v], bytes});
-}
 
 extern "C" {
 
@@ -256,15 +204,15 @@ int csh_plonk_quot_blinders_dev(csh_domain_t ext_dom, uint32_t protocol, uint32_
   const char* what = "plonk_quot_blinders";
   CSH_TRY(pq_check_party(protocol, party_id, what));
   CSH_REQUIRE(ext_dom && blinders && out_dev, "plonk_quot_blinders: NULL argument");
-  CSH_TRY(pq_check_ptrs((const void* const*)out_dev, 5, what));
+  CSH_TRY(fr_require_ptrs((const void* const*)out_dev, 5, what));
   CSH_TRY(ensure_device());
   const Domain* d = reinterpret_cast<const Domain*>(ext_dom);
   CSH_TRY(pq_check_domain(d, what));
-  std::vector<PqRange> in, out;
-  pq_add(out, (const void* const*)out_dev, 5, 32 * domain_size_of(d) * (protocol + 1));
-  CSH_TRY(pq_check_ranges(in, out, what));
+  FrRanges in, out;
+  out.add((const void* const*)out_dev, 5, 32 * domain_size_of(d) * (protocol + 1));
+  CSH_TRY(fr_check_ranges(in, out, what));
   hipStream_t st = resolve_stream(stream);
-  FR_DISPATCH(domain_curve_of(d), blinders_t<F>(d, protocol, party_id, blinders, out_dev, st));
+  return FR_CALL(domain_curve_of(d), blinders_t<F>(d, protocol, party_id, blinders, out_dev, st));
 }
 
 int csh_plonk_quot_operands_dev(csh_domain_t ext_dom, uint32_t protocol, uint32_t party_id, const uint64_t* const* shares_dev,
@@ -275,23 +223,23 @@ int csh_plonk_quot_operands_dev(csh_domain_t ext_dom, uint32_t protocol, uint32_
   CSH_REQUIRE(ext_dom && shares_dev && public_dev && challenges && out_dev && (n_public == 0 || (lagrange_dev && buffer_a)),
               "plonk_quot_operands: NULL argument");
   CSH_REQUIRE(n_public <= (size_t(1) << 24), "plonk_quot_operands: n_public exceeds 2^24");
-  CSH_TRY(pq_check_ptrs((const void* const*)shares_dev, 11, what));
-  CSH_TRY(pq_check_ptrs((const void* const*)public_dev, 8, what));
-  CSH_TRY(pq_check_ptrs((const void* const*)lagrange_dev, n_public, what));
-  CSH_TRY(pq_check_ptrs((const void* const*)out_dev, 10, what));
+  CSH_TRY(fr_require_ptrs((const void* const*)shares_dev, 11, what));
+  CSH_TRY(fr_require_ptrs((const void* const*)public_dev, 8, what));
+  CSH_TRY(fr_require_ptrs((const void* const*)lagrange_dev, n_public, what));
+  CSH_TRY(fr_require_ptrs((const void* const*)out_dev, 10, what));
   CSH_TRY(ensure_device());
   const Domain* d = reinterpret_cast<const Domain*>(ext_dom);
   CSH_TRY(pq_check_domain(d, what));
   const size_t pb = 32 * domain_size_of(d), sb = pb * (protocol + 1);
-  std::vector<PqRange> in, out;
-  pq_add(in, (const void* const*)shares_dev, 11, sb);
-  pq_add(in, (const void* const*)public_dev, 8, pb);
-  pq_add(in, (const void* const*)lagrange_dev, n_public, pb);
-  pq_add(out, (const void* const*)out_dev, 10, sb);
-  CSH_TRY(pq_check_ranges(in, out, what));
+  FrRanges in, out;
+  in.add((const void* const*)shares_dev, 11, sb);
+  in.add((const void* const*)public_dev, 8, pb);
+  in.add((const void* const*)lagrange_dev, n_public, pb);
+  out.add((const void* const*)out_dev, 10, sb);
+  CSH_TRY(fr_check_ranges(in, out, what));
   hipStream_t st = resolve_stream(stream);
-  FR_DISPATCH(domain_curve_of(d),
-              operands_t<F>(d, protocol, party_id, shares_dev, public_dev, lagrange_dev, n_public, buffer_a, challenges, out_dev, st));
+  return FR_CALL(domain_curve_of(d),
+                 operands_t<F>(d, protocol, party_id, shares_dev, public_dev, lagrange_dev, n_public, buffer_a, challenges, out_dev, st));
 }
 
 int csh_plonk_quot_combine_dev(csh_domain_t ext_dom, uint32_t protocol, uint32_t party_id, const uint64_t* const* shares_dev,
@@ -299,36 +247,36 @@ int csh_plonk_quot_combine_dev(csh_domain_t ext_dom, uint32_t protocol, uint32_t
   const char* what = "plonk_quot_combine";
   CSH_TRY(pq_check_party(protocol, party_id, what));
   CSH_REQUIRE(ext_dom && shares_dev && lagrange1_dev && alpha && out_dev, "plonk_quot_combine: NULL argument");
-  CSH_TRY(pq_check_ptrs((const void* const*)shares_dev, 14, what));
-  CSH_TRY(pq_check_ptrs((const void* const*)out_dev, 2, what));
+  CSH_TRY(fr_require_ptrs((const void* const*)shares_dev, 14, what));
+  CSH_TRY(fr_require_ptrs((const void* const*)out_dev, 2, what));
   CSH_TRY(ensure_device());
   const Domain* d = reinterpret_cast<const Domain*>(ext_dom);
   CSH_TRY(pq_check_domain(d, what));
   const size_t pb = 32 * domain_size_of(d), sb = pb * (protocol + 1);
-  std::vector<PqRange> in, out;
-  pq_add(in, (const void* const*)shares_dev, 14, sb);
-  in.push_back(PqRange{lagrange1_dev, pb});
-  pq_add(out, (const void* const*)out_dev, 2, sb);
-  CSH_TRY(pq_check_ranges(in, out, what));
+  FrRanges in, out;
+  in.add((const void* const*)shares_dev, 14, sb);
+  in.add(lagrange1_dev, pb);
+  out.add((const void* const*)out_dev, 2, sb);
+  CSH_TRY(fr_check_ranges(in, out, what));
   hipStream_t st = resolve_stream(stream);
-  FR_DISPATCH(domain_curve_of(d), combine_t<F>(d, protocol, party_id, shares_dev, lagrange1_dev, alpha, out_dev, st));
+  return FR_CALL(domain_curve_of(d), combine_t<F>(d, protocol, party_id, shares_dev, lagrange1_dev, alpha, out_dev, st));
 }
 
 int csh_plonk_quot_finish_dev(csh_curve_t field_of, size_t n, uint32_t protocol, uint32_t party_id, const uint64_t* ct_dev, const uint64_t* ctz_dev,
                               const uint64_t* b9_b10, uint64_t* t1_dev, uint64_t* t2_dev, uint64_t* t3_dev, void* stream) {
   const char* what = "plonk_quot_finish";
-  CSH_REQUIRE(field_of == CSH_BN254 || field_of == CSH_BLS12_381 || field_of == CSH_BLS12_377,
-              "plonk_quot_finish: field_of must be BN254, BLS12-381 or BLS12-377");
+  CSH_REQUIRE(fr_known(field_of), "plonk_quot_finish: field_of must be BN254, BLS12-381 or BLS12-377");
   CSH_TRY(pq_check_party(protocol, party_id, what));
   CSH_REQUIRE(ct_dev && ctz_dev && b9_b10 && t1_dev && t2_dev && t3_dev, "plonk_quot_finish: NULL argument");
-  CSH_REQUIRE(n >= 8 && n <= PQ_MAX_N / 4 && (n & (n - 1)) == 0, "plonk_quot_finish: n must be a power of two, 8 .. 2^26");
+  CSH_REQUIRE(n >= 8 && n <= FR_MAX_N / 4 && (n & (n - 1)) == 0, "plonk_quot_finish: n must be a power of two, 8 .. 2^26");
   const size_t sb = 32 * (size_t)(protocol + 1);
-  const std::vector<PqRange> in = {{ct_dev, 4 * n * sb}, {ctz_dev, 4 * n * sb}};
-  const std::vector<PqRange> out = {{t1_dev, (n + 1) * sb}, {t2_dev, (n + 1) * sb}, {t3_dev, (n + 6) * sb}};
-  CSH_TRY(pq_check_ranges(in, out, what));
+  FrRanges in, out;
+  in.add(ct_dev, 4 * n * sb), in.add(ctz_dev, 4 * n * sb);
+  out.add(t1_dev, (n + 1) * sb), out.add(t2_dev, (n + 1) * sb), out.add(t3_dev, (n + 6) * sb);
+  CSH_TRY(fr_check_ranges(in, out, what));
   CSH_TRY(ensure_device());
   hipStream_t st = resolve_stream(stream);
-  FR_DISPATCH(field_of, finish_t<F>(n, protocol + 1, ct_dev, ctz_dev, b9_b10, t1_dev, t2_dev, t3_dev, st));
+  return FR_CALL(field_of, finish_t<F>(n, protocol + 1, ct_dev, ctz_dev, b9_b10, t1_dev, t2_dev, t3_dev, st));
 }
 
 }  // extern "C"

@@ -7,7 +7,7 @@
 // shamir/arithmetic.rs:45) on component `pub_comp` only: 0 for plain / Shamir and Rep3 party 0, 1 for Rep3 party 1, none for party 2.
 //
 // Scale. Elements are arkworks-Montgomery (R = 2^256 scale) and are re-sliced into 9 x 29-bit limbs as they are (unpack). A constant of the
-// call is brought to the R' = 2^261 domain once on the host (pq_rp: c R' mod p, canonical and packed), so mul(x, c') = x c R R' / R' is at
+// call is brought to the R' = 2^261 domain once on the host (fr_to_rprime, fr_entry.hpp: c R' mod p, canonical and packed), so mul(x, c') = x c R R' / R' is at
 // the operands' scale again. A product of two LOADED operands scales one of them by 2^5 = R' / R (times32()), as vec_elem.hpp does. The powers
 // w^i are kept in the R' domain: mul(hi', lo') of two table entries is w^i R', and mul(share, that) is at R scale.
 //
@@ -29,19 +29,13 @@
 #include "common.hpp"
 #include "field.hpp"
 #include "field29.hpp"
+#include "fr_entry.hpp"
 
 namespace csh {
 
 constexpr int PQ_WG = 256;          // lanes of a workgroup, as vec_ops.hip
 constexpr int PQ_POW_LO_LOG = 8;    // w^i = hi[i >> 8] * lo[i & 255]: the two-level power table (256 + N / 256 entries, built on the device per call)
 constexpr int PQ_PI_CHUNK = 16;     // Lagrange vectors per launch of the public-input sum: 16 pointers + 32 constants = 1152 B of kernel arguments
-
-// c (arkworks Montgomery) -> c R' mod p, canonical and packed
-template <class F>
-CSH_HD F pq_rp(const F& c) {
-  using LZ = typename LazyOf<F>::type;
-  return LZ::from_fp(c).canonical().pack();
-}
 
 // word-wise selects: a lane-dependent index into a kernel argument would put the argument into scratch memory
 template <class F>
@@ -177,12 +171,12 @@ template <class F>
 inline PqCombineK<F> pq_combine_consts(const F& gen, size_t N, const F& alpha) {
   const PqZ<F> z = pq_z_tables(gen, N);
   PqCombineK<F> k;
-  k.alphad = pq_rp(alpha);
-  k.alpha2d = pq_rp(F::mul(alpha, alpha));
+  k.alphad = fr_to_rprime(alpha);
+  k.alpha2d = fr_to_rprime(F::mul(alpha, alpha));
   for (int m = 0; m < 4; ++m) {
-    k.az1d[m] = pq_rp(F::mul(alpha, z.z1[m]));
-    k.az2d[m] = pq_rp(F::mul(alpha, z.z2[m]));
-    k.az3d[m] = pq_rp(F::mul(alpha, z.z3[m]));
+    k.az1d[m] = fr_to_rprime(F::mul(alpha, z.z1[m]));
+    k.az2d[m] = fr_to_rprime(F::mul(alpha, z.z2[m]));
+    k.az3d[m] = fr_to_rprime(F::mul(alpha, z.z3[m]));
   }
   return k;
 }
@@ -241,17 +235,11 @@ CSH_HD PqFinishCol<F> pq_finish_col(const F& ct0, const F& ct1, const F& ct2, co
 // ---- what one launch is told, how the host fills it in, and what a lane does with flat index e -----------------------------------------
 // The kernels call pq_*_at() inside their grid-stride loops; the self-test calls the same functions index after index on host arrays.
 CSH_HD int pq_pub_comp(uint32_t protocol, uint32_t party) { return protocol == 0 ? 0 : (party == 0 ? 0 : (party == 1 ? 1 : -1)); }
-template <class F>
-inline F pq_word(const void* p) {
-  F f;
-  memcpy(&f, p, sizeof(F));
-  return f;
-}
 // a host share (ncomp elements) by component; the absent component of ncomp 1 is zero
 template <class F>
 inline void pq_share(F dst[2], const uint64_t* p, uint32_t ncomp) {
-  dst[0] = pq_word<F>(p);
-  dst[1] = ncomp == 2 ? pq_word<F>(p + 4) : F::zero();
+  dst[0] = fr_load<F>(p);
+  dst[1] = ncomp == 2 ? fr_load<F>(p + 4) : F::zero();
 }
 
 struct PqGeom {
@@ -289,7 +277,7 @@ struct PqBlindArgs {
 template <class F>
 inline void pq_blinders_consts(PqBlindArgs<F>& a, const F& gen, const uint64_t* blinders, uint32_t ncomp) {
   for (int j = 0; j < 9; ++j) pq_share(a.k.b[j], blinders + 4 * ncomp * j, ncomp);
-  a.k.w4d = pq_rp(F::pow_u64(gen, 4));
+  a.k.w4d = fr_to_rprime(F::pow_u64(gen, 4));
 }
 template <class F>
 CSH_HD void pq_blinders_at(const PqBlindArgs<F>& a, int v, size_t e) {
@@ -314,8 +302,8 @@ inline void pq_pi_consts(PqPiArgs<F>& a, const uint64_t* const* lagrange, const 
     if (j < a.k) {
       F s[2];
       pq_share(s, buffer_a + 4 * ncomp * (j0 + j), ncomp);
-      a.nbd[j][0] = pq_rp(F::neg(s[0]));
-      a.nbd[j][1] = pq_rp(F::neg(s[1]));
+      a.nbd[j][0] = fr_to_rprime(F::neg(s[0]));
+      a.nbd[j][1] = fr_to_rprime(F::neg(s[1]));
     }
   }
 }

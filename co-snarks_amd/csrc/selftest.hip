@@ -13,6 +13,7 @@
 #include "chacha.hpp"
 #include "field29.hpp"
 #include "field_scan.hpp"
+#include "fr_entry.hpp"
 #include "mle_fold.hpp"
 #include "msm_digits.hpp"
 #include "plonk_quot.hpp"
@@ -195,15 +196,12 @@ int lazy_chain_check_t(const void* affine_pts, size_t n, size_t len, size_t nthr
 // Host run of the lazy NTT butterfly arithmetic (ntt.hip k_ntt_pass_lazy): a, b, w arkworks-Montgomery elements of the
 // scalar field; k times  acc = (acc +/- b*w).normalized()  with the twiddle in the R' domain, then canonical_wide().pack().
 // Expected: a +/- k*b*w (still arkworks-Montgomery). Exercises the value drift a pass accumulates and its reduction.
-template <class LZ, class F>
+template <class F>
 static int lazy_fr_chain_t(const uint64_t a[4], const uint64_t b[4], const uint64_t w[4], int k, int negative, uint64_t out[4]) {
-  F fa, fb, fw;
-  memcpy(&fa, a, 32);
-  memcpy(&fb, b, 32);
-  memcpy(&fw, w, 32);
-  LZ acc = LZ::unpack(fa);
-  const LZ lb = LZ::unpack(fb);
-  const LZ lw = LZ::unpack(LZ::repack_for_storage(fw));
+  using LZ = LzOf<F>;
+  LZ acc = LZ::unpack(fr_load<F>(a));
+  const LZ lb = LZ::unpack(fr_load<F>(b));
+  const LZ lw = LZ::unpack(LZ::repack_for_storage(fr_load<F>(w)));
   for (int i = 0; i < k; ++i) {  // as the decimation-in-time stages do: the carry step only every second stage
     const LZ x = LZ::mul(lb, lw);
     acc = negative ? LZ::sub(acc, x) : LZ::add(acc, x);
@@ -235,13 +233,8 @@ static int lazy_fr_chain_t(const uint64_t a[4], const uint64_t b[4], const uint6
 template <class F>
 static int lazy_vec_t(int op, const uint64_t* a, const uint64_t* b, const uint64_t* c, const uint64_t* d, const uint64_t* m, const uint64_t* s, uint64_t* out) {
   if (op < 0 || op > 4 || !a || !b || !c || !out || (op != 0 && op != 2 && !d) || (op == 1 && !m)) return CSH_ERR_INVALID;
-  F fa, fb, fc, fd = F::zero(), fm = F::zero(), fs = F::zero();
-  memcpy(&fa, a, 32);
-  memcpy(&fb, b, 32);
-  memcpy(&fc, c, 32);
-  if (d) memcpy(&fd, d, 32);
-  if (m) memcpy(&fm, m, 32);
-  if (op == 3 && s) memcpy(&fs, s, 32);
+  const F fa = fr_load<F>(a), fb = fr_load<F>(b), fc = fr_load<F>(c), fd = d ? fr_load<F>(d) : F::zero(), fm = m ? fr_load<F>(m) : F::zero(),
+          fs = op == 3 && s ? fr_load<F>(s) : F::zero();
   F r;
   switch (op) {
     case 0: r = elem_mul(fa, fb); break;
@@ -299,8 +292,9 @@ static int zero_flags_t(const int32_t* limbs, size_t n, uint8_t* flags) {
 // Host run of the field scans' arithmetic (field_scan.hip) with the limb-bound checks on: the same routines and the same order of
 // scales, lane after lane instead of side by side. op 0: running product; 1: batch inverse (zeros stay zero); 2: lazy_inv alone
 // (n = 1). run = elements per lane. All arkworks-Montgomery in and out.
-template <class LZ, class F>
+template <class F>
 static int scan_host_t(int op, const uint64_t* in, size_t n, int run, uint64_t* out) {
+  using LZ = LzOf<F>;
   std::vector<F> x(n);
   if (n) memcpy(x.data(), in, n * sizeof(F));
   InvScratch<LZ> scratch;
@@ -371,21 +365,18 @@ static void hillis_steele(std::vector<LZ>& v, int levels, const std::function<LZ
     }
   }
 }
-template <class LZ, class F>
+template <class F>
 static int divlin_host_t(const uint64_t* in, size_t n, uint32_t ncomp, int run, const uint64_t* root, const uint64_t* sub0, uint64_t* out) {
-  F r;
-  memcpy(&r, root, sizeof(F));
-  const F w = F::inv(r);
+  using LZ = LzOf<F>;
+  const F w = F::inv(fr_load<F>(root));
   const PowTable<F> pw = pow_table<LZ, F>(LZ::from_fp(w));
-  const LZ wz = LZ::unpack(pw.p[0]), c = LZ::unpack(LZ::from_fp(F::neg(w)).canonical().pack());
+  const LZ wz = LZ::unpack(pw.p[0]), c = LZ::unpack(fr_to_rprime(F::neg(w)));
   int base = 0;
   while ((1 << base) < run) ++base;
   const size_t lanes = (n + run - 1) / run, block = 1024;
   for (uint32_t comp = 0; comp < ncomp; ++comp) {
     auto coeff = [&](size_t i) {
-      F x = F::zero(), s0 = F::zero();
-      if (i < n) memcpy(&x, in + 4 * (i * ncomp + comp), sizeof(F));
-      if (i == 0 && sub0) memcpy(&s0, sub0 + 4 * comp, sizeof(F));
+      const F x = i < n ? fr_load<F>(in + 4 * (i * ncomp + comp)) : F::zero(), s0 = i == 0 && sub0 ? fr_load<F>(sub0 + 4 * comp) : F::zero();
       return i == 0 ? LZ::sub(LZ::unpack(x), LZ::unpack(s0)) : LZ::unpack(x);
     };
     LZ carry = LZ::zero();
@@ -430,7 +421,7 @@ static int divlin_host_t(const uint64_t* in, size_t n, uint32_t ncomp, int run, 
 // a result). levels_out: levels 1..m back to back as csh_mle_fold_rounds lays them out. All arkworks-Montgomery in and out.
 template <class F>
 static int mle_fold_host_t(const uint64_t* in, size_t n, uint32_t ncomp, int T, const uint64_t* u, size_t m, uint64_t* levels_out) {
-  using LZ = typename LazyOf<F>::type;
+  using LZ = LzOf<F>;
   std::vector<F> src(n * ncomp), lev((n - (n >> m)) * ncomp);
   memcpy(src.data(), in, sizeof(F) * src.size());
   std::vector<int32_t> planes(LZ::NL * (fold_plane_a(T, ncomp) + fold_plane_b(T, ncomp)));
@@ -439,11 +430,7 @@ static int mle_fold_host_t(const uint64_t* in, size_t n, uint32_t ncomp, int T, 
     FoldRoundsArgs<F> a;
     memset(&a, 0, sizeof a);
     a.rounds = (int)(m - p * T < (size_t)T ? m - p * T : (size_t)T);
-    for (int r = 0; r < a.rounds; ++r) {
-      F uf;
-      memcpy(&uf, u + 4 * (p * T + r), sizeof(F));
-      a.ud[r] = fold_challenge(uf);
-    }
+    for (int r = 0; r < a.rounds; ++r) a.ud[r] = fr_to_rprime(fr_load<F>(u + 4 * (p * T + r)));
     a.in = p ? lev.data() + fold_level_offset(n, (int)(p * T)) * ncomp : src.data();
     a.n_in = n >> (p * T);
     a.ncomp = ncomp;
@@ -457,9 +444,7 @@ static int mle_fold_host_t(const uint64_t* in, size_t n, uint32_t ncomp, int T, 
   }
   std::vector<F> cur(src), nxt;
   for (size_t l = 1; l <= m; ++l) {  // k_mle_fold, sweep after sweep
-    F uf;
-    memcpy(&uf, u + 4 * (l - 1), sizeof(F));
-    const F ud = fold_challenge(uf);
+    const F ud = fr_to_rprime(fr_load<F>(u + 4 * (l - 1)));
     nxt.resize(cur.size() / 2);
     for (size_t o = 0; o < nxt.size(); ++o) {
       const size_t s = fold_src(o, ncomp);
@@ -478,13 +463,9 @@ static int mle_fold_host_t(const uint64_t* in, size_t n, uint32_t ncomp, int T, 
 // chain goes on from the lazy ones).
 template <class F>
 static int fold_step_chain_t(const uint64_t* a, const uint64_t* b, const uint64_t* u, size_t rounds, uint64_t* out) {
-  using LZ = typename LazyOf<F>::type;
-  F fa, fb, fu;
-  memcpy(&fa, a, sizeof(F));
-  memcpy(&fb, b, sizeof(F));
-  memcpy(&fu, u, sizeof(F));
-  const LZ ud = LZ::unpack(fold_challenge(fu));
-  LZ x = LZ::unpack(fa), y = LZ::unpack(fb);
+  using LZ = LzOf<F>;
+  const LZ ud = LZ::unpack(fr_to_rprime(fr_load<F>(u)));
+  LZ x = LZ::unpack(fr_load<F>(a)), y = LZ::unpack(fr_load<F>(b));
   for (size_t r = 0; r < rounds; ++r) {
     const LZ nx = fold_step(x, y, ud), ny = fold_step(y, x, ud);
     x = nx;
@@ -508,12 +489,12 @@ static int fold_step_chain_t(const uint64_t* a, const uint64_t* b, const uint64_
 template <class F>
 static int plonk_quot_host_t(int stage, const uint64_t* gen_w, size_t N, uint32_t protocol, uint32_t party, const uint64_t* const* in, size_t n_public,
                              const uint64_t* scalars, uint64_t* const* out) {
-  const F gen = pq_word<F>(gen_w);
+  const F gen = fr_load<F>(gen_w);
   const PqGeom g{N, protocol + 1, pq_pub_comp(protocol, party)};
   std::vector<F> hi(pq_pow_hi_count(N)), lo(size_t(1) << PQ_POW_LO_LOG);
   if (stage == 0 || stage == 1) {
     PqPowArgs<F> p;
-    p.gd = pq_rp(gen);
+    p.gd = fr_to_rprime(gen);
     p.hi = hi.data(), p.lo = lo.data(), p.n_hi = hi.size();
     for (size_t i = 0; i < hi.size() + lo.size(); ++i) pq_pow_tables_at(p, i);
   }
@@ -531,7 +512,7 @@ static int plonk_quot_host_t(int stage, const uint64_t* gen_w, size_t N, uint32_
     case 1: {
       const uint64_t* const* pub = in + 11;
       const uint64_t* ch = scalars + 4 * g.ncomp * n_public;
-      const F beta = pq_word<F>(ch), gamma = pq_word<F>(ch + 4), k1 = pq_word<F>(ch + 8), k2 = pq_word<F>(ch + 12);
+      const F beta = fr_load<F>(ch), gamma = fr_load<F>(ch + 4), k1 = fr_load<F>(ch + 8), k2 = fr_load<F>(ch + 12);
       for (size_t j0 = 0; j0 == 0 || j0 < n_public; j0 += PQ_PI_CHUNK) {
         PqPiArgs<F> p;
         pq_pi_consts(p, in + 19, scalars, j0, n_public, g.ncomp);
@@ -548,7 +529,7 @@ static int plonk_quot_host_t(int stage, const uint64_t* gen_w, size_t N, uint32_
         a.qm = (const F*)pub[0], a.ql = (const F*)pub[1], a.qr = (const F*)pub[2], a.qo = (const F*)pub[3], a.qc = (const F*)pub[4];
         a.e1 = (F*)out[1], a.e1z = (F*)out[2];
         const PqZ<F> z = pq_z_tables(gen, N);
-        for (int m = 0; m < 4; ++m) a.z1d[m] = pq_rp(z.z1[m]);
+        for (int m = 0; m < 4; ++m) a.z1d[m] = fr_to_rprime(z.z1[m]);
         a.g = g;
         for (size_t e = 0; e < g.values(); ++e) pq_e1_at(a, pq_e1_lane(a, e), e);
       }
@@ -566,7 +547,7 @@ static int plonk_quot_host_t(int stage, const uint64_t* gen_w, size_t N, uint32_
         for (int v = 0; v < 3; ++v) a.in[v] = (const F*)in[v], a.s[v] = (const F*)pub[5 + v], a.out[v] = (F*)out[6 + v];
         a.z = (const F*)in[3];
         a.e3d = (F*)out[9];
-        a.betad = pq_rp(beta);
+        a.betad = fr_to_rprime(beta);
         a.gamma = gamma;
         a.g = g;
         for (size_t e = 0; e < g.values(); ++e) pq_e3_at(a, e);
@@ -580,7 +561,7 @@ static int plonk_quot_host_t(int stage, const uint64_t* gen_w, size_t N, uint32_
       for (int j = 0; j < 4; ++j) a.e2z[j] = (const F*)in[5 + j], a.e3z[j] = (const F*)in[10 + j];
       a.l1 = (const F*)in[14];
       a.t = (F*)out[0], a.tz = (F*)out[1];
-      a.k = pq_combine_consts(gen, N, pq_word<F>(scalars));
+      a.k = pq_combine_consts(gen, N, fr_load<F>(scalars));
       for (size_t e = 0; e < g.values(); ++e) pq_combine_at(a, pq_combine_lane(a, e), e);
       return CSH_OK;
     }
@@ -608,10 +589,7 @@ extern "C" {
 int csh_selftest_plonk_quot_host(int field_of, int stage, const uint64_t* gen, size_t N, uint32_t protocol, uint32_t party, const uint64_t* const* in,
                                  size_t n_public, const uint64_t* scalars, uint64_t* const* out) {
   if (!gen || !out || protocol > 1 || party > 2 || N < 32 || (N & (N - 1)) || stage < 0 || stage > 4) return CSH_ERR_INVALID;
-  if (field_of == CSH_BN254) return plonk_quot_host_t<Bn254Fr>(stage, gen, N, protocol, party, in, n_public, scalars, out);
-  if (field_of == CSH_BLS12_381) return plonk_quot_host_t<Bls381Fr>(stage, gen, N, protocol, party, in, n_public, scalars, out);
-  if (field_of == CSH_BLS12_377) return plonk_quot_host_t<Bls377Fr>(stage, gen, N, protocol, party, in, n_public, scalars, out);
-  return CSH_ERR_INVALID;
+  return FR_CALL(field_of, plonk_quot_host_t<F>(stage, gen, N, protocol, party, in, n_public, scalars, out));
 }
 
 int csh_selftest_mle_fold_host(int field_of, const uint64_t* in, size_t n, uint32_t ncomp, int tile_log, const uint64_t* u, size_t m,
@@ -619,35 +597,23 @@ int csh_selftest_mle_fold_host(int field_of, const uint64_t* in, size_t n, uint3
   if (!in || !u || !levels_out || ncomp < 1 || ncomp > 2 || !fold_tile_log_ok(tile_log) || m < 1 || m > 28 || n < 2 ||
       (n & ((size_t(1) << m) - 1)))
     return CSH_ERR_INVALID;
-  if (field_of == CSH_BN254) return mle_fold_host_t<Bn254Fr>(in, n, ncomp, tile_log, u, m, levels_out);
-  if (field_of == CSH_BLS12_381) return mle_fold_host_t<Bls381Fr>(in, n, ncomp, tile_log, u, m, levels_out);
-  if (field_of == CSH_BLS12_377) return mle_fold_host_t<Bls377Fr>(in, n, ncomp, tile_log, u, m, levels_out);
-  return CSH_ERR_INVALID;
+  return FR_CALL(field_of, mle_fold_host_t<F>(in, n, ncomp, tile_log, u, m, levels_out));
 }
 
 int csh_selftest_fold_step_chain_host(int field_of, const uint64_t* a, const uint64_t* b, const uint64_t* u, size_t rounds, uint64_t* out) {
   if (!a || !b || !u || !out) return CSH_ERR_INVALID;
-  if (field_of == CSH_BN254) return fold_step_chain_t<Bn254Fr>(a, b, u, rounds, out);
-  if (field_of == CSH_BLS12_381) return fold_step_chain_t<Bls381Fr>(a, b, u, rounds, out);
-  if (field_of == CSH_BLS12_377) return fold_step_chain_t<Bls377Fr>(a, b, u, rounds, out);
-  return CSH_ERR_INVALID;
+  return FR_CALL(field_of, fold_step_chain_t<F>(a, b, u, rounds, out));
 }
 
 int csh_selftest_divlin_host(int field_of, const uint64_t* in, size_t n, uint32_t ncomp, int run, const uint64_t* root, const uint64_t* sub0,
                              uint64_t* out) {
   if (run < 1 || (run & (run - 1)) || ncomp < 1 || ncomp > 2 || !root || !(root[0] | root[1] | root[2] | root[3])) return CSH_ERR_INVALID;
-  if (field_of == CSH_BN254) return divlin_host_t<Fr29s, Bn254Fr>(in, n, ncomp, run, root, sub0, out);
-  if (field_of == CSH_BLS12_381) return divlin_host_t<Bls381Fr29s, Bls381Fr>(in, n, ncomp, run, root, sub0, out);
-  if (field_of == CSH_BLS12_377) return divlin_host_t<Bls377Fr29s, Bls377Fr>(in, n, ncomp, run, root, sub0, out);
-  return CSH_ERR_INVALID;
+  return FR_CALL(field_of, divlin_host_t<F>(in, n, ncomp, run, root, sub0, out));
 }
 
 int csh_selftest_scan_host(int field_of, int op, const uint64_t* in, size_t n, int run, uint64_t* out) {
   if (op < 0 || op > 2 || run < 1) return CSH_ERR_INVALID;
-  if (field_of == CSH_BN254) return scan_host_t<Fr29s, Bn254Fr>(op, in, n, run, out);
-  if (field_of == CSH_BLS12_381) return scan_host_t<Bls381Fr29s, Bls381Fr>(op, in, n, run, out);
-  if (field_of == CSH_BLS12_377) return scan_host_t<Bls377Fr29s, Bls377Fr>(op, in, n, run, out);
-  return CSH_ERR_INVALID;
+  return FR_CALL(field_of, scan_host_t<F>(op, in, n, run, out));
 }
 
 // type: 0 Fq29s, 1 Fq28s, 2 Fr29s, 3 Fq28s377, 4 Fq29s2, 5 Fq28s2, 6 Fq28s377x2
@@ -734,19 +700,13 @@ int csh_selftest_lazy_tree(int curve, int group, const void* affine_pts, const u
 }
 
 int csh_selftest_lazy_fr_chain(int field_of, const uint64_t a[4], const uint64_t b[4], const uint64_t w[4], int k, int negative, uint64_t out[4]) {
-  if (field_of == CSH_BN254) return lazy_fr_chain_t<Fr29s, Bn254Fr>(a, b, w, k, negative, out);
-  if (field_of == CSH_BLS12_381) return lazy_fr_chain_t<Bls381Fr29s, Bls381Fr>(a, b, w, k, negative, out);
-  if (field_of == CSH_BLS12_377) return lazy_fr_chain_t<Bls377Fr29s, Bls377Fr>(a, b, w, k, negative, out);
-  return CSH_ERR_INVALID;
+  return FR_CALL(field_of, lazy_fr_chain_t<F>(a, b, w, k, negative, out));
 }
 
 // s (the `sub` operand of op 3) comes last: ops 0 and 1 keep their numbers, their meaning and their arguments
 int csh_selftest_lazy_vec(int field_of, int op, const uint64_t* a, const uint64_t* b, const uint64_t* c, const uint64_t* d, const uint64_t* m,
                           uint64_t* out, const uint64_t* s) {
-  if (field_of == CSH_BN254) return lazy_vec_t<Bn254Fr>(op, a, b, c, d, m, s, out);
-  if (field_of == CSH_BLS12_381) return lazy_vec_t<Bls381Fr>(op, a, b, c, d, m, s, out);
-  if (field_of == CSH_BLS12_377) return lazy_vec_t<Bls377Fr>(op, a, b, c, d, m, s, out);
-  return CSH_ERR_INVALID;
+  return FR_CALL(field_of, lazy_vec_t<F>(op, a, b, c, d, m, s, out));
 }
 
 // out = to_fp(mul(from_fp(a) (+/-) from_fp(b), from_fp(c))) for the signed lazy field: op 0: (a+b)*c, 1: (a-b)*c
@@ -775,28 +735,26 @@ int csh_selftest_rep3_masks_host(int curve, const uint8_t seed1[32], uint64_t e1
   uint32_t k1[8], k2[8];
   memcpy(k1, seed1, 32);
   memcpy(k2, seed2, 32);
-  for (size_t i = 0; i < n; ++i) {
-    if (curve == CSH_BN254) {
-      Bn254Fr v = rep3_mask_element<Bn254Fr>(k1, k2, e1 + i, e2 + i);
-      memcpy(out + 4 * i, &v, 32);
-    } else {
-      Bls381Fr v = rep3_mask_element<Bls381Fr>(k1, k2, e1 + i, e2 + i);
+  return with_fr((csh_curve_t)curve, [&](auto fr) -> int {
+    for (size_t i = 0; i < n; ++i) {
+      const auto v = rep3_mask_element<typename decltype(fr)::type>(k1, k2, e1 + i, e2 + i);
       memcpy(out + 4 * i, &v, 32);
     }
-  }
-  return CSH_OK;
+    return CSH_OK;
+  });
 }
 
 // canonical scalar limbs -> signed digits (digits_out[w], w < *W_out)
 int csh_selftest_digits(int curve, const uint64_t scalar[4], int c, int32_t* digits_out, int* W_out) {
-  const int bits = curve == CSH_BN254 ? Bn254FrParams::BITS : curve == CSH_BLS12_377 ? Bls377FrParams::BITS : Bls381FrParams::BITS;
-  const int W = windows_for(bits, c);
-  uint32_t s[8];
-  memcpy(s, scalar, 32);
-  for (int w = 0; w < W; ++w) digits_out[w] = 0;
-  for_each_digit<8>(s, c, W, [&](int w, uint32_t b, uint32_t neg) { digits_out[w] = neg ? -(int32_t)b : (int32_t)b; });
-  *W_out = W;
-  return CSH_OK;
+  return with_fr((csh_curve_t)curve, [&](auto fr) -> int {
+    const int W = windows_for(decltype(fr)::type::Params::BITS, c);
+    uint32_t s[8];
+    memcpy(s, scalar, 32);
+    for (int w = 0; w < W; ++w) digits_out[w] = 0;
+    for_each_digit<8>(s, c, W, [&](int w, uint32_t b, uint32_t neg) { digits_out[w] = neg ? -(int32_t)b : (int32_t)b; });
+    *W_out = W;
+    return CSH_OK;
+  });
 }
 
 }  // extern "C"

@@ -7,6 +7,7 @@
 
 #include "common.hpp"
 #include "field.hpp"
+#include "fr_entry.hpp"
 
 namespace csh {
 
@@ -105,7 +106,7 @@ extern "C" {
 int csh_matrix_upload(csh_curve_t field_of, const uint64_t* row_ptr, const uint32_t* col_idx, const uint64_t* coeffs, size_t n_rows, size_t nnz,
                       csh_matrix_t* out) {
   CSH_REQUIRE(out && row_ptr && (nnz == 0 || (col_idx && coeffs)), "matrix_upload: NULL argument");
-  CSH_REQUIRE(field_of == CSH_BN254 || field_of == CSH_BLS12_381 || field_of == CSH_BLS12_377, "unknown curve");
+  CSH_REQUIRE(fr_known(field_of), "unknown curve");
   CSH_REQUIRE(row_ptr[n_rows] == nnz, "matrix_upload: row_ptr[n_rows] != nnz");
   CSH_REQUIRE(row_ptr[0] == 0, "matrix_upload: row_ptr[0] != 0");
   for (size_t i = 0; i < n_rows; ++i) CSH_REQUIRE(row_ptr[i] <= row_ptr[i + 1], "matrix_upload: row_ptr is not monotone");
@@ -182,9 +183,7 @@ int csh_evaluate_constraints_dev(csh_matrix_t mm, int protocol, int party_id, co
   // a matrix from an untrusted circuit must not index past the vectors the caller handed over (the kernel gathers by column)
   CSH_REQUIRE(m->nnz == 0 || (size_t)m->max_col < n_public + n_witness, "evaluate_constraints: a matrix column index exceeds n_public + n_witness");
   hipStream_t st = resolve_stream(stream);
-  if (m->curve == CSH_BN254) return eval_t<Bn254Fr>(m, protocol, party_id, public_dev, n_public, witness_dev, out_dev, n_out, st);
-  if (m->curve == CSH_BLS12_377) return eval_t<Bls377Fr>(m, protocol, party_id, public_dev, n_public, witness_dev, out_dev, n_out, st);
-  return eval_t<Bls381Fr>(m, protocol, party_id, public_dev, n_public, witness_dev, out_dev, n_out, st);
+  return FR_CALL(m->curve, eval_t<F>(m, protocol, party_id, public_dev, n_public, witness_dev, out_dev, n_out, st));
 }
 
 }  // extern "C"
@@ -226,9 +225,7 @@ int witness_map_core(csh_domain_t dom, const uint64_t shift[4], int protocol, in
   if (n_public) CSH_HIP(hipMemcpyAsync(dpub, public_inputs, 32 * n_public, hipMemcpyHostToDevice, st));
   CSH_TRY(csh_evaluate_constraints_dev(ma, protocol, party_id, dpub, n_public, witness_dev, n_witness, da, n, st));   // reduction.rs:102-110
   CSH_TRY(csh_evaluate_constraints_dev(mb, protocol, party_id, dpub, n_public, witness_dev, n_witness, db, n, st));   // :118-127
-  if (f == CSH_BN254) CSH_TRY(promote_t<Bn254Fr>(protocol, da, num_constraints, dpub, n_public, party_id, st));  // :111-113
-  else if (f == CSH_BLS12_377) CSH_TRY(promote_t<Bls377Fr>(protocol, da, num_constraints, dpub, n_public, party_id, st));
-  else CSH_TRY(promote_t<Bls381Fr>(protocol, da, num_constraints, dpub, n_public, party_id, st));
+  CSH_TRY(FR_CALL(f, promote_t<F>(protocol, da, num_constraints, dpub, n_public, party_id, st)));  // :111-113
   if (protocol == 1 && !(dmc && dmab) && ms.seed1 && ms.seed2) {
     uint64_t* gc = reinterpret_cast<uint64_t*>(ar.take<char>(eb));
     uint64_t* gab = reinterpret_cast<uint64_t*>(ar.take<char>(eb));
@@ -364,9 +361,7 @@ static int witness_map_libsnark_host(csh_domain_t dom, const uint64_t generator[
   CSH_TRY(h.up(dpub, public_inputs, 32 * n_public));
   CSH_TRY(h.up(dwit, witness, 32 * comp * n_witness));
   CSH_TRY(csh_evaluate_constraints_dev(ma, protocol, party_id, dpub, n_public, dwit, n_witness, da, n, h.st));    // reduction.rs:260-266
-  if (f == CSH_BN254) CSH_TRY(promote_t<Bn254Fr>(protocol, da, num_constraints, dpub, n_public, party_id, h.st));  // :267-269
-  else if (f == CSH_BLS12_377) CSH_TRY(promote_t<Bls377Fr>(protocol, da, num_constraints, dpub, n_public, party_id, h.st));
-  else CSH_TRY(promote_t<Bls381Fr>(protocol, da, num_constraints, dpub, n_public, party_id, h.st));
+  CSH_TRY(FR_CALL(f, promote_t<F>(protocol, da, num_constraints, dpub, n_public, party_id, h.st)));                // :267-269
   CSH_TRY(csh_evaluate_constraints_dev(mb, protocol, party_id, dpub, n_public, dwit, n_witness, db, n, h.st));    // :276-282
   CSH_TRY(csh_evaluate_constraints_dev(mc, protocol, party_id, dpub, n_public, dwit, n_witness, dcf, n, h.st));   // :292-298
   if (protocol == 1) {  // half share = component a

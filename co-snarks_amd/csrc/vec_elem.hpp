@@ -45,7 +45,7 @@ CSH_HD F elem_rep3_to_shamir(const F& a, const F& b, const F& x, const F& y) {
 }
 
 // a + u (b - a), the multilinear fold of one pair (k_mle_fold, k_mle_fold_rounds; partially_evaluate, co_sumcheck_prover.rs:34-98).
-// ud: the challenge in the R' domain (u R' mod p, canonical and packed: fold_challenge() of mle_fold.hpp, once per call on the host), so
+// ud: the challenge in the R' domain (u R' mod p, canonical and packed: fr_to_rprime() of fr_entry.hpp, once per call on the host), so
 // mul(b - a, ud) comes out at the operands' scale and no loaded operand is scaled. fold_step is the same on lazy values, for the rounds that
 // stay on chip: a, b within (-1.1 p, 2.1 p) with limbs 0..NL-2 in [0, 2^B) (loaded, or an earlier fold_step); bounds in mle_fold.hpp.
 template <class LZ>

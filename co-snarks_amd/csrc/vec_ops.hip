@@ -8,6 +8,7 @@
 #include "common.hpp"
 #include "field.hpp"
 #include "field29.hpp"
+#include "fr_entry.hpp"
 #include "vec_elem.hpp"
 #include "chacha.hpp"
 #include <stdlib.h>
@@ -16,11 +17,6 @@
 namespace csh {
 
 constexpr int VB = 256;
-static int vec_grid(size_t n) {
-  int mb = tune().vec_max_blocks.load(std::memory_order_relaxed);  // default 65536: up to one element per lane at 2^24, measured 8-10 % faster than 4096 blocks + grid stride
-  if (mb <= 0) mb = 65536;
-  return grid_for(n, VB, mb);
-}
 
 template <class F>
 __global__ __launch_bounds__(VB) void k_vec_mul(const F* __restrict__ a, const F* __restrict__ b, F* out, size_t n) {
@@ -106,14 +102,14 @@ __global__ __launch_bounds__(VB) void k_lincomb(LincombArgs<F> args, F* out, siz
 template <class F>
 static int vec_mul_t(const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n, hipStream_t st) {
   if (n == 0) return CSH_OK;
-  hipLaunchKernelGGL(k_vec_mul<F>, dim3(vec_grid(n)), dim3(VB), 0, st, (const F*)a, (const F*)b, (F*)out, n);
+  hipLaunchKernelGGL(k_vec_mul<F>, dim3(fr_stream_grid(n, VB)), dim3(VB), 0, st, (const F*)a, (const F*)b, (F*)out, n);
   CSH_HIP(hipGetLastError());
   return CSH_OK;
 }
 template <class F>
 static int vec_mul_sub_t(const uint64_t* a, const uint64_t* b, const uint64_t* c, uint64_t* out, size_t n, hipStream_t st) {
   if (n == 0) return CSH_OK;
-  hipLaunchKernelGGL(k_vec_mul_sub<F>, dim3(vec_grid(n)), dim3(VB), 0, st, (const F*)a, (const F*)b, (const F*)c, (F*)out, n);
+  hipLaunchKernelGGL(k_vec_mul_sub<F>, dim3(fr_stream_grid(n, VB)), dim3(VB), 0, st, (const F*)a, (const F*)b, (const F*)c, (F*)out, n);
   CSH_HIP(hipGetLastError());
   return CSH_OK;
 }
@@ -121,33 +117,30 @@ template <class F>
 static int vec_addsub_t(bool sub, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n_elems, hipStream_t st) {
   if (n_elems == 0) return CSH_OK;
   if (sub)
-    hipLaunchKernelGGL((k_vec_addsub<F, true>), dim3(vec_grid(n_elems)), dim3(VB), 0, st, (const F*)a, (const F*)b, (F*)out, n_elems);
+    hipLaunchKernelGGL((k_vec_addsub<F, true>), dim3(fr_stream_grid(n_elems, VB)), dim3(VB), 0, st, (const F*)a, (const F*)b, (F*)out, n_elems);
   else
-    hipLaunchKernelGGL((k_vec_addsub<F, false>), dim3(vec_grid(n_elems)), dim3(VB), 0, st, (const F*)a, (const F*)b, (F*)out, n_elems);
+    hipLaunchKernelGGL((k_vec_addsub<F, false>), dim3(fr_stream_grid(n_elems, VB)), dim3(VB), 0, st, (const F*)a, (const F*)b, (F*)out, n_elems);
   CSH_HIP(hipGetLastError());
   return CSH_OK;
 }
 template <class F>
 static int vec_mul_table_t(uint64_t* v, const uint64_t* table, size_t n, uint32_t ncomp, hipStream_t st) {
   if (n == 0) return CSH_OK;
-  hipLaunchKernelGGL(k_vec_mul_table<F>, dim3(vec_grid(n * ncomp)), dim3(VB), 0, st, (F*)v, (const F*)table, n * ncomp, ncomp);
+  hipLaunchKernelGGL(k_vec_mul_table<F>, dim3(fr_stream_grid(n * ncomp, VB)), dim3(VB), 0, st, (F*)v, (const F*)table, n * ncomp, ncomp);
   CSH_HIP(hipGetLastError());
   return CSH_OK;
 }
 template <class F>
 static int rep3_local_mul_t(const uint64_t* l, const uint64_t* r, const uint64_t* m, uint64_t* out, size_t n, hipStream_t st, const uint64_t* sub = nullptr) {
   if (n == 0) return CSH_OK;
-  hipLaunchKernelGGL(k_rep3_local_mul<F>, dim3(vec_grid(n)), dim3(VB), 0, st, (const F*)l, (const F*)r, (const F*)m, (const F*)sub, (F*)out, n);
+  hipLaunchKernelGGL(k_rep3_local_mul<F>, dim3(fr_stream_grid(n, VB)), dim3(VB), 0, st, (const F*)l, (const F*)r, (const F*)m, (const F*)sub, (F*)out, n);
   CSH_HIP(hipGetLastError());
   return CSH_OK;
 }
 template <class F>
 static int rep3_to_shamir_t(const uint64_t* in, const uint64_t* x, const uint64_t* y, uint64_t* out, size_t n, hipStream_t st) {
   if (n == 0) return CSH_OK;
-  F fx, fy;
-  memcpy(&fx, x, sizeof(F));
-  memcpy(&fy, y, sizeof(F));
-  hipLaunchKernelGGL(k_rep3_to_shamir<F>, dim3(vec_grid(n)), dim3(VB), 0, st, (const F*)in, fx, fy, (F*)out, n);
+  hipLaunchKernelGGL(k_rep3_to_shamir<F>, dim3(fr_stream_grid(n, VB)), dim3(VB), 0, st, (const F*)in, fr_load<F>(x), fr_load<F>(y), (F*)out, n);
   CSH_HIP(hipGetLastError());
   return CSH_OK;
 }
@@ -157,7 +150,7 @@ static int rep3_masks_t(const uint8_t* seed1, uint64_t e1, const uint8_t* seed2,
   ChaChaKeys keys;
   memcpy(keys.k1, seed1, 32);
   memcpy(keys.k2, seed2, 32);
-  hipLaunchKernelGGL(k_rep3_masks<F>, dim3(vec_grid(n)), dim3(VB), 0, st, keys, e1, e2, (F*)out, n);
+  hipLaunchKernelGGL(k_rep3_masks<F>, dim3(fr_stream_grid(n, VB)), dim3(VB), 0, st, keys, e1, e2, (F*)out, n);
   CSH_HIP(hipGetLastError());
   return CSH_OK;
 }
@@ -170,11 +163,11 @@ static int lincomb_t(const uint64_t* const* shares, const uint64_t* coeffs, size
   int unit = 1;
   for (size_t j = 0; j < k; ++j) {
     args.shares[j] = (const F*)shares[j];
-    memcpy(&args.coeffs[j], coeffs + 4 * j, sizeof(F));
+    args.coeffs[j] = fr_load<F>(coeffs + 4 * j);
     if (!(args.coeffs[j] == one)) unit = 0;
   }
   args.unit = unit;
-  hipLaunchKernelGGL(k_lincomb<F>, dim3(vec_grid(n)), dim3(VB), 0, st, args, (F*)out, n);
+  hipLaunchKernelGGL(k_lincomb<F>, dim3(fr_stream_grid(n, VB)), dim3(VB), 0, st, args, (F*)out, n);
   CSH_HIP(hipGetLastError());
   return CSH_OK;
 }
@@ -183,20 +176,12 @@ static int lincomb_t(const uint64_t* const* shares, const uint64_t* coeffs, size
 
 using namespace csh;
 
-#define FR_DISPATCH(field_of, CALL)                                  \
-  switch (field_of) {                                                \
-    case CSH_BN254: { using F = Bn254Fr; return CALL; }              \
-    case CSH_BLS12_381: { using F = Bls381Fr; return CALL; }         \
-    case CSH_BLS12_377: { using F = Bls377Fr; return CALL; }         \
-    default: set_error("unknown curve %d", (int)(field_of)); return CSH_ERR_INVALID; \
-  }
-
 namespace csh {
 int vec_mul_sub_dev(csh_curve_t f, const uint64_t* a, const uint64_t* b, const uint64_t* c, uint64_t* out, size_t n, hipStream_t st) {
-  FR_DISPATCH(f, vec_mul_sub_t<F>(a, b, c, out, n, st));
+  return FR_CALL(f, vec_mul_sub_t<F>(a, b, c, out, n, st));
 }
 int rep3_local_mul_sub_dev(csh_curve_t f, const uint64_t* a, const uint64_t* b, const uint64_t* mask, const uint64_t* c, uint64_t* out, size_t n, hipStream_t st) {
-  FR_DISPATCH(f, rep3_local_mul_t<F>(a, b, mask, out, n, st, c));
+  return FR_CALL(f, rep3_local_mul_t<F>(a, b, mask, out, n, st, c));
 }
 }  // namespace csh
 
@@ -205,49 +190,49 @@ extern "C" {
 int csh_vec_mul_dev(csh_curve_t f, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n, void* stream) {
   CSH_TRY(ensure_device());
   hipStream_t st = resolve_stream(stream);
-  FR_DISPATCH(f, vec_mul_t<F>(a, b, out, n, st));
+  return FR_CALL(f, vec_mul_t<F>(a, b, out, n, st));
 }
 int csh_vec_add_dev(csh_curve_t f, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n, uint32_t ncomp, void* stream) {
   CSH_TRY(ensure_device());
   hipStream_t st = resolve_stream(stream);
-  FR_DISPATCH(f, vec_addsub_t<F>(false, a, b, out, n * ncomp, st));
+  return FR_CALL(f, vec_addsub_t<F>(false, a, b, out, n * ncomp, st));
 }
 int csh_vec_sub_dev(csh_curve_t f, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n, uint32_t ncomp, void* stream) {
   CSH_TRY(ensure_device());
   hipStream_t st = resolve_stream(stream);
-  FR_DISPATCH(f, vec_addsub_t<F>(true, a, b, out, n * ncomp, st));
+  return FR_CALL(f, vec_addsub_t<F>(true, a, b, out, n * ncomp, st));
 }
 int csh_vec_mul_table_dev(csh_curve_t f, uint64_t* v, const uint64_t* table, size_t n, uint32_t ncomp, void* stream) {
-  CSH_REQUIRE(ncomp >= 1 && ncomp <= 2, "ncomp must be 1 or 2");
+  FR_REQUIRE_NCOMP(ncomp);
   CSH_TRY(ensure_device());
   hipStream_t st = resolve_stream(stream);
-  FR_DISPATCH(f, vec_mul_table_t<F>(v, table, n, ncomp, st));
+  return FR_CALL(f, vec_mul_table_t<F>(v, table, n, ncomp, st));
 }
 int csh_rep3_local_mul_vec_dev(csh_curve_t f, const uint64_t* l, const uint64_t* r, const uint64_t* m, uint64_t* out, size_t n, void* stream) {
   CSH_TRY(require_rep3_masks(m != nullptr || n == 0, "rep3_local_mul_vec"));
   CSH_TRY(ensure_device());
   hipStream_t st = resolve_stream(stream);
-  FR_DISPATCH(f, rep3_local_mul_t<F>(l, r, m, out, n, st));
+  return FR_CALL(f, rep3_local_mul_t<F>(l, r, m, out, n, st));
 }
 int csh_rep3_to_shamir_vec_dev(csh_curve_t f, const uint64_t* in, const uint64_t x[4], const uint64_t y[4], uint64_t* out, size_t n, void* stream) {
   CSH_REQUIRE(x && y, "translation points are NULL");
   CSH_TRY(ensure_device());
   hipStream_t st = resolve_stream(stream);
-  FR_DISPATCH(f, rep3_to_shamir_t<F>(in, x, y, out, n, st));
+  return FR_CALL(f, rep3_to_shamir_t<F>(in, x, y, out, n, st));
 }
 int csh_rep3_masks_dev(csh_curve_t f, const uint8_t seed1[32], uint64_t elem_offset1, const uint8_t seed2[32], uint64_t elem_offset2,
                        uint64_t* out, size_t n, void* stream) {
   CSH_REQUIRE(seed1 && seed2 && (out || n == 0), "rep3_masks: NULL argument");
   CSH_TRY(ensure_device());
   hipStream_t st = resolve_stream(stream);
-  FR_DISPATCH(f, rep3_masks_t<F>(seed1, elem_offset1, seed2, elem_offset2, out, n, st));
+  return FR_CALL(f, rep3_masks_t<F>(seed1, elem_offset1, seed2, elem_offset2, out, n, st));
 }
 int csh_lincomb_dev(csh_curve_t f, const uint64_t* const* shares, const uint64_t* coeffs, size_t k, uint64_t* out, size_t n, void* stream) {
   CSH_REQUIRE(k >= 1 && k <= (size_t)MAX_LINCOMB, "lincomb: 1 <= k <= 16");
   CSH_REQUIRE(shares && coeffs, "lincomb: NULL argument");
   CSH_TRY(ensure_device());
   hipStream_t st = resolve_stream(stream);
-  FR_DISPATCH(f, lincomb_t<F>(shares, coeffs, k, out, n, st));
+  return FR_CALL(f, lincomb_t<F>(shares, coeffs, k, out, n, st));
 }
 
 // ---- host-pointer convenience wrappers: H2D, compute, D2H on the thread's stream (HostStage) -------
