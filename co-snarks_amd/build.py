@@ -59,29 +59,33 @@ def _compile(src_dir, name, force, hdrs):
     return obj
 
 
+def _compile_host(name, force, hdrs):
+    src = os.path.join(HOST, name)
+    obj = os.path.join(OBJDIR, "host_" + os.path.splitext(name)[0] + ".o")
+    if force or _newer(obj, [src] + hdrs):
+        _run([HIPCC, "-O2", "-std=c++17", "-fPIC", "-x", "hip", "--offload-arch=" + ARCH, "-Wno-unused-value", "-c", src, "-o", obj])
+    return obj
+
+
 def build_all(force: bool = False, verbose: bool = True):
     os.makedirs(LIBDIR, exist_ok=True)
     os.makedirs(OBJDIR, exist_ok=True)
-    hdrs = _headers(CSRC, HOST)
+    hdrs = _headers(CSRC)
     srcs = [s for s in HIP_SOURCES if os.path.exists(os.path.join(CSRC, s))]
+    # host-side mirror of the reference interface (C++ above the C ABI): its units go through the same pool as the device library's
+    host_srcs = sorted(f for f in (os.listdir(HOST) if os.path.isdir(HOST) else []) if f.endswith(".cpp"))
+    host_hdrs = _headers(CSRC, HOST)
     with concurrent.futures.ThreadPoolExecutor(max_workers=min(os.cpu_count() or 8, len(srcs))) as ex:
+        hobjs = [ex.submit(_compile_host, f, force, host_hdrs) for f in host_srcs]
         objs = list(ex.map(lambda s: _compile(CSRC, s, force, hdrs), srcs))
+        hobjs = [f.result() for f in hobjs]
     lib = os.path.join(LIBDIR, "libcosnarks_hip.so")
     if force or _newer(lib, objs):
         _run([HIPCC, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", lib] + objs)
     if verbose:
         print("built", lib)
     outs = [lib]
-    # host-side mirror of the reference interface (C++ above the C ABI)
-    host_srcs = [f for f in (os.listdir(HOST) if os.path.isdir(HOST) else []) if f.endswith(".cpp")]
     if host_srcs:
-        hobjs = []
-        for f in host_srcs:
-            src = os.path.join(HOST, f)
-            obj = os.path.join(OBJDIR, "host_" + os.path.splitext(f)[0] + ".o")
-            if force or _newer(obj, [src] + hdrs):
-                _run([HIPCC, "-O2", "-std=c++17", "-fPIC", "-x", "hip", "--offload-arch=" + ARCH, "-Wno-unused-value", "-c", src, "-o", obj])
-            hobjs.append(obj)
         hlib = os.path.join(LIBDIR, "libcosnarks_groth16.so")
         if force or _newer(hlib, hobjs + [lib]):
             _run([HIPCC, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", hlib] + hobjs +

@@ -45,6 +45,7 @@ struct Bn254 {
   static constexpr uint64_t FR_GENERATOR = 5;  // ark_bn254::Fr::GENERATOR
   static const char* name() { return "bn128"; }
   static const uint32_t* g1_generator_words() { return csh::Bn254G1Gen; }
+  static const uint32_t* g2_generator_words() { return csh::Bn254G2Gen; }
 };
 struct Bls12_381 {
   static constexpr csh_curve_t ID = CSH_BLS12_381;
@@ -54,6 +55,7 @@ struct Bls12_381 {
   static constexpr uint64_t FR_GENERATOR = 7;  // ark_bls12_381::Fr::GENERATOR
   static const char* name() { return "bls12381"; }
   static const uint32_t* g1_generator_words() { return csh::Bls381G1Gen; }
+  static const uint32_t* g2_generator_words() { return csh::Bls381G2Gen; }
 };
 
 // the curve of the reference's LibSnarkReduction fixtures (co-groth16/src/lib.rs:231-300): witness maps and, since round 6, the
@@ -66,6 +68,7 @@ struct Bls12_377 {
   static constexpr uint64_t FR_GENERATOR = 22;  // ark_bls12_377::Fr::GENERATOR
   static const char* name() { return "bls12377"; }
   static const uint32_t* g1_generator_words() { return csh::Bls377G1Gen; }
+  static const uint32_t* g2_generator_words() { return csh::Bls377G2Gen; }
 };
 
 // Tracing spans mirroring the reference's `tracing::debug_span!` names (groth16.rs:229-331, reduction.rs:97-191):
