@@ -27,6 +27,7 @@ from .bindings import (  # noqa: F401
     device_count,
     eval_poly,
     poly_div_linear,
+    poly_lincomb,
     fr_bytes,
     groth16_h,
     have_device,
@@ -38,10 +39,12 @@ from .bindings import (  # noqa: F401
     msm_fold_partials,
     msm_partial_bytes,
     msm_split,
+    plonk_blind_coefficients,
     plonk_quot_blinders,
     plonk_quot_combine,
     plonk_quot_finish,
     plonk_quot_operands,
+    plonk_z_operands,
     point_bytes,
     rep3_local_mul_vec,
     rep3_to_shamir_vec,
@@ -54,5 +57,6 @@ from .bindings import (  # noqa: F401
     vec_mul,
     vec_mul_table,
     vec_prefix_prod,
+    vec_rotate_right,
     vec_sub,
 )

@@ -528,7 +528,7 @@ def mle_fold_rounds(curve: int, vec, us, ncomp: int = 1, n: int | None = None, l
 
 
 def _devptr_array(bufs):
-    return (C.c_void_p * len(bufs))(*[_devptr(b).value for b in bufs]) if len(bufs) else None
+    return (C.c_void_p * len(bufs))(*[_devptr(b).value if b is not None else None for b in bufs]) if len(bufs) else None
 
 
 def plonk_quot_blinders(dom: "Domain", protocol: int, party: int, blinders, outs, stream=None):
@@ -571,6 +571,47 @@ def plonk_quot_finish(curve: int, n: int, protocol: int, party: int, ct, ctz, b9
     _check(lib().csh_plonk_quot_finish_dev(curve, C.c_size_t(n), C.c_uint32(protocol), C.c_uint32(party), _devptr(ct), _devptr(ctz), _p(bb),
                                            _devptr(t1), _devptr(t2), _devptr(t3), _stream(stream)))
     return t1, t2, t3
+
+
+def plonk_z_operands(dom: "Domain", protocol: int, party: int, shares, sigma, challenges, outs, stream=None):
+    """csh_plonk_z_operands_dev on the EXTENDED domain `dom` (4 n points). shares: the DeviceBuffers buffer_a, buffer_b, buffer_c (n shares);
+    sigma: the DeviceBuffers S1, S2, S3 (4 n evaluations); challenges: beta, gamma, k1, k2 on the host; outs: the 6 DeviceBuffers n1, n2, n3,
+    d1, d2, d3, which are returned."""
+    ch = _u64(challenges)
+    assert len(shares) == 3 and len(sigma) == 3 and len(outs) == 6 and ch.size == 16
+    _check(lib().csh_plonk_z_operands_dev(dom.h, C.c_uint32(protocol), C.c_uint32(party), _devptr_array(shares), _devptr_array(sigma), _p(ch),
+                                          _devptr_array(outs), _stream(stream)))
+    return outs
+
+
+def vec_rotate_right(curve: int, vec, out, n: int, ncomp: int = 1, k: int = 1, stream=None):
+    """csh_vec_rotate_right_dev: out[(i + k) mod n] = vec[i] on DeviceBuffers of n shares; out is returned."""
+    _check(lib().csh_vec_rotate_right_dev(curve, _devptr(vec), _devptr(out), C.c_size_t(n), C.c_uint32(ncomp), C.c_size_t(k), _stream(stream)))
+    return out
+
+
+def plonk_blind_coefficients(curve: int, poly, n: int, coeff_rev, ncomp: int = 1, stream=None):
+    """csh_plonk_blind_coefficients_dev: poly (a DeviceBuffer with room for n + k shares) in place; coeff_rev: the k host shares."""
+    cr = _u64(coeff_rev)
+    k = cr.size // (4 * ncomp)
+    assert cr.size == k * 4 * ncomp
+    _check(lib().csh_plonk_blind_coefficients_dev(curve, _devptr(poly), C.c_size_t(n), C.c_uint32(ncomp), _p(cr), C.c_size_t(k), _stream(stream)))
+    return poly
+
+
+def poly_lincomb(curve: int, protocol: int, party: int, shares, share_lens, share_coeffs, public, public_lens, public_coeffs, out, out_len: int,
+                 const0=None, stream=None):
+    """csh_poly_lincomb_dev: out[i] = sum cs_j S_j[i] (+) (sum cp_j P_j[i] + [i = 0] const0) over DeviceBuffers of differing lengths
+    (share_lens in shares, public_lens in elements); the coefficients and const0 are host elements. out (out_len shares) is returned."""
+    cs, cp = _u64(share_coeffs), _u64(public_coeffs)
+    ks, kp = len(shares), len(public)
+    assert cs.size == 4 * ks and cp.size == 4 * kp and len(share_lens) == ks and len(public_lens) == kp
+    c0 = _u64(const0) if const0 is not None else None
+    sl, pl = (C.c_size_t * ks)(*share_lens), (C.c_size_t * kp)(*public_lens)
+    _check(lib().csh_poly_lincomb_dev(curve, C.c_uint32(protocol), C.c_uint32(party), _devptr_array(shares), sl if ks else None, _p(cs) if ks else None,
+                                      C.c_size_t(ks), _devptr_array(public), pl if kp else None, _p(cp) if kp else None, C.c_size_t(kp), _p(c0),
+                                      _devptr(out), C.c_size_t(out_len), _stream(stream)))
+    return out
 
 
 def rep3_local_mul_vec(curve: int, lhs_ab, rhs_ab, mask=None):

@@ -15,11 +15,6 @@
 namespace csh {
 
 template <class F>
-__global__ __launch_bounds__(PQ_WG) void k_pq_pow_tables(PqPowArgs<F> a) {
-  const size_t total = a.n_hi + (size_t(1) << PQ_POW_LO_LOG);
-  for (size_t i = blockIdx.x * (size_t)PQ_WG + threadIdx.x; i < total; i += (size_t)gridDim.x * PQ_WG) pq_pow_tables_at(a, i);
-}
-template <class F>
 __global__ __launch_bounds__(PQ_WG) void k_pq_blinders(PqBlindArgs<F> a) {
   for (size_t e = blockIdx.x * (size_t)PQ_WG + threadIdx.x; e < a.g.values(); e += (size_t)gridDim.x * PQ_WG)
     pq_blinders_at(a, (int)blockIdx.y, e);  // blockIdx.y = the output: ap, bp, cp, zp, zwp
@@ -52,24 +47,6 @@ template <class F>
 __global__ __launch_bounds__(PQ_WG) void k_pq_finish(PqFinishArgs<F> a) {
   const size_t nv = a.n * a.ncomp;
   for (size_t e = blockIdx.x * (size_t)PQ_WG + threadIdx.x; e < nv; e += (size_t)gridDim.x * PQ_WG) pq_finish_at(a, e);
-}
-
-// the two-level power table of the domain's generator, in the stream's workspace (valid for work queued on `st` until the next call that
-// takes workspace on it)
-template <class F>
-static int pq_power_tables(const F& gen, size_t N, hipStream_t st, const F** hi, const F** lo) {
-  PqPowArgs<F> a;
-  a.gd = fr_to_rprime(gen);
-  a.n_hi = pq_pow_hi_count(N);
-  const size_t n_lo = size_t(1) << PQ_POW_LO_LOG;
-  Arena& ar = arena_for(st);
-  CSH_TRY(ar.reserve(Arena::padded(a.n_hi * sizeof(F)) + Arena::padded(n_lo * sizeof(F))));
-  a.hi = ar.take<F>(a.n_hi);
-  a.lo = ar.take<F>(n_lo);
-  hipLaunchKernelGGL(k_pq_pow_tables<F>, dim3(fr_stream_grid(a.n_hi + n_lo, PQ_WG)), dim3(PQ_WG), 0, st, a);
-  *hi = a.hi;
-  *lo = a.lo;
-  return CSH_OK;
 }
 
 static PqGeom pq_geom(size_t N, uint32_t protocol, uint32_t party) { return PqGeom{N, protocol + 1, pq_pub_comp(protocol, party)}; }

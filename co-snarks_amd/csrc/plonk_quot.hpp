@@ -431,4 +431,30 @@ CSH_HD void pq_finish_at(const PqFinishArgs<F>& a, size_t e) {
   }
 }
 
+// ---- the power tables on the device: the kernel and its launcher, for every unit that needs w^i (plonk_quot.hip, plonk_rounds.hip) ------
+#if defined(__HIPCC__)
+template <class F>
+__global__ __launch_bounds__(PQ_WG) void k_pq_pow_tables(PqPowArgs<F> a) {
+  const size_t total = a.n_hi + (size_t(1) << PQ_POW_LO_LOG);
+  for (size_t i = blockIdx.x * (size_t)PQ_WG + threadIdx.x; i < total; i += (size_t)gridDim.x * PQ_WG) pq_pow_tables_at(a, i);
+}
+// the two-level power table of the domain's generator, in the stream's workspace (valid for work queued on `st` until the next call that
+// takes workspace on it)
+template <class F>
+inline int pq_power_tables(const F& gen, size_t N, hipStream_t st, const F** hi, const F** lo) {
+  PqPowArgs<F> a;
+  a.gd = fr_to_rprime(gen);
+  a.n_hi = pq_pow_hi_count(N);
+  const size_t n_lo = size_t(1) << PQ_POW_LO_LOG;
+  Arena& ar = arena_for(st);
+  CSH_TRY(ar.reserve(Arena::padded(a.n_hi * sizeof(F)) + Arena::padded(n_lo * sizeof(F))));
+  a.hi = ar.take<F>(a.n_hi);
+  a.lo = ar.take<F>(n_lo);
+  hipLaunchKernelGGL(k_pq_pow_tables<F>, dim3(fr_stream_grid(a.n_hi + n_lo, PQ_WG)), dim3(PQ_WG), 0, st, a);
+  *hi = a.hi;
+  *lo = a.lo;
+  return CSH_OK;
+}
+#endif
+
 }  // namespace csh

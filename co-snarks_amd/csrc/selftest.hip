@@ -17,6 +17,7 @@
 #include "mle_fold.hpp"
 #include "msm_digits.hpp"
 #include "plonk_quot.hpp"
+#include "plonk_rounds.hpp"
 #include "vec_elem.hpp"
 
 using namespace csh;
@@ -584,12 +585,74 @@ static int plonk_quot_host_t(int stage, const uint64_t* gen_w, size_t N, uint32_
   return CSH_ERR_INVALID;
 }
 
+// Host run of the round-2 / round-5 stretches (plonk_rounds.hip) with the limb-bound checks on: the argument structs are filled in by the
+// functions the launchers use and every flat index goes through the pr_*_at() function its kernel calls -- on host arrays.
+//   entry 0 z operands: aux = the generator of the EXTENDED domain, n = its quarter; in = a, b, c (n shares), S1, S2, S3 (4 n elements);
+//                       scalars = beta, gamma, k1, k2; out = n1, n2, n3, d1, d2, d3
+//   entry 1 rotate:     in[0] (n shares) -> out[0], ks = k
+//   entry 2 blind:      out[0] = the polynomial, n + k shares, in place; scalars = coeff_rev (k shares); ks = k
+//   entry 3 lincomb:    n = out_len; in = the ks share vectors, then the kp public ones; lens = their lengths; scalars = the ks + kp
+//                       coefficients; aux = const0 or NULL; out[0]
+template <class F>
+static int plonk_rounds_host_t(int entry, const uint64_t* aux, size_t n, uint32_t protocol, uint32_t party, const uint64_t* const* in,
+                               const size_t* lens, const uint64_t* scalars, size_t ks, size_t kp, uint64_t* const* out) {
+  const uint32_t ncomp = protocol + 1;
+  switch (entry) {
+    case 0: {
+      PrZArgs<F> a;
+      a.g = PqGeom{n, ncomp, pq_pub_comp(protocol, party)};
+      std::vector<F> hi(pq_pow_hi_count(n)), lo(size_t(1) << PQ_POW_LO_LOG);
+      PqPowArgs<F> p;
+      p.gd = fr_to_rprime(F::pow_u64(fr_load<F>(aux), 4));
+      p.hi = hi.data(), p.lo = lo.data(), p.n_hi = hi.size();
+      for (size_t i = 0; i < hi.size() + lo.size(); ++i) pq_pow_tables_at(p, i);
+      a.hi = hi.data(), a.lo = lo.data();
+      for (int v = 0; v < 3; ++v) a.in[v] = (const F*)in[v], a.sigma[v] = (const F*)in[3 + v];
+      for (int v = 0; v < 6; ++v) a.out[v] = (F*)out[v];
+      pr_z_consts(a, scalars);
+      for (size_t e = 0; e < a.g.values(); ++e) pr_z_num_at(a, e);
+      for (size_t e = 0; e < a.g.values(); ++e) pr_z_den_at(a, e);
+      return CSH_OK;
+    }
+    case 1: {
+      if (ks >= n) return CSH_ERR_INVALID;
+      PrRotArgs<F> a{(const F*)in[0], (F*)out[0], n, ks, ncomp};
+      for (size_t e = 0; e < n * ncomp; ++e) pr_rotate_at(a, e);
+      return CSH_OK;
+    }
+    case 2: {
+      if (ks < 1 || ks > 3 || n < 3) return CSH_ERR_INVALID;
+      PrBlindArgs<F> a;
+      a.poly = (F*)out[0];
+      a.n = n, a.ncomp = ncomp, a.k = (uint32_t)ks;
+      pr_blind_consts(a, scalars, ncomp, a.k);
+      for (size_t e = 0; e < ks * ncomp; ++e) pr_blind_at(a, e);
+      return CSH_OK;
+    }
+    case 3: {
+      if (ks > PR_LC_MAX_TERMS || kp > PR_LC_MAX_TERMS || ks + kp < 1) return CSH_ERR_INVALID;
+      for (size_t j = 0; j < ks + kp; ++j)
+        if (lens[j] > n) return CSH_ERR_INVALID;
+      for (const PrLcArgs<F>& a : pr_lc_launches<F>(protocol, party, in, lens, scalars, ks, in + ks, lens + ks, scalars + 4 * ks, kp, aux, out[0], n))
+        for (size_t e = 0; e < a.g.values(); ++e) pr_lc_at(a, e);
+      return CSH_OK;
+    }
+  }
+  return CSH_ERR_INVALID;
+}
+
 extern "C" {
 
 int csh_selftest_plonk_quot_host(int field_of, int stage, const uint64_t* gen, size_t N, uint32_t protocol, uint32_t party, const uint64_t* const* in,
                                  size_t n_public, const uint64_t* scalars, uint64_t* const* out) {
   if (!gen || !out || protocol > 1 || party > 2 || N < 32 || (N & (N - 1)) || stage < 0 || stage > 4) return CSH_ERR_INVALID;
   return FR_CALL(field_of, plonk_quot_host_t<F>(stage, gen, N, protocol, party, in, n_public, scalars, out));
+}
+
+int csh_selftest_plonk_rounds_host(int field_of, int entry, const uint64_t* aux, size_t n, uint32_t protocol, uint32_t party,
+                                   const uint64_t* const* in, const size_t* lens, const uint64_t* scalars, size_t ks, size_t kp, uint64_t* const* out) {
+  if (!out || protocol > 1 || party > 2 || entry < 0 || entry > 3 || (entry == 0 && (!aux || n < 8 || (n & (n - 1))))) return CSH_ERR_INVALID;
+  return FR_CALL(field_of, plonk_rounds_host_t<F>(entry, aux, n, protocol, party, in, lens, scalars, ks, kp, out));
 }
 
 int csh_selftest_mle_fold_host(int field_of, const uint64_t* in, size_t n, uint32_t ncomp, int tile_log, const uint64_t* u, size_t m,

@@ -10,6 +10,8 @@
 //       co-noir-common/src/polynomials/polynomial.rs:183, shared_polynomial.rs:92-140, co_shplemini_prover.rs:661-737, co-plonk/src/round5.rs:78-91
 //   partially_evaluate_init / partially_evaluate_inplace, compute_fold_polynomials, Polynomial / SharedPolynomial::evaluate_mle
 //       co_sumcheck_prover.rs:34-98, co_shplemini_prover.rs:236-312, polynomial.rs:270-312, shared_polynomial.rs:154-199 (csh_mle_fold / csh_mle_fold_rounds)
+//   Round2::compute_z, Round5::compute_r + compute_wxi, compute_wxiw for the plain driver
+//       co-plonk/src/round2.rs:104-190, round5.rs:118-278 (csh_plonk_z_operands / csh_vec_rotate_right / csh_plonk_blind_coefficients / csh_poly_lincomb)
 // These data-parallel methods are mirrored, the whole-vector scans among them (running product, batch inverse, polynomial
 // evaluation, division by (X - z): csh_vec_prefix_prod / csh_vec_batch_inverse / csh_eval_poly / csh_poly_div_linear). The PLONK rounds / sumcheck / relations above them are
 // control logic and stay in the Rust host (SURVEY.md 8 "out of scope"). NOT mirrored: the Rep3 / Shamir array_prod_mul
@@ -382,6 +384,30 @@ struct PlonkQuotientInputs {
   Share blinders[11];
   Fr beta, gamma, alpha;
 };
+// What Round2::compute_z (co-plonk/src/round2.rs:104-190) reads: the three wire buffers, of the zkey the 4 n evaluations of S1, S2, S3 and
+// k1, k2, the challenges beta and gamma, and the blinders b7, b8, b9 in the order blind_coefficients takes them.
+template <class Fr>
+struct PlonkRound2Inputs {
+  std::vector<Fr> buffer_a, buffer_b, buffer_c;  // n each
+  std::vector<Fr> s1, s2, s3;                    // 4 n evaluations each
+  Fr beta, gamma, k1, k2;
+  Fr blinders[3];
+};
+template <class Fr>
+struct PlonkPolyEval {  // types.rs PolyEval: n + k blinded coefficients, the 4 n evaluations of the unblinded polynomial
+  std::vector<Fr> poly, eval;
+};
+// What Round5::compute_r + compute_wxi (round5.rs:118-259) read: the blinded polynomials of rounds 1-3, of the zkey the n coefficients of
+// the selector and permutation polynomials and k1, k2, the public inputs, the round-4 evaluations and every challenge so far.
+template <class Fr>
+struct PlonkRound5Inputs {
+  size_t domain_size = 0;
+  std::vector<Fr> z, t1, t2, t3, a, b, c;          // n + 3, n + 1, n + 1, n + 6, n + 2, n + 2, n + 2 coefficients
+  std::vector<Fr> qm, ql, qr, qo, qc, s1, s2, s3;  // n coefficients each
+  std::vector<Fr> public_inputs;
+  Fr eval_a, eval_b, eval_c, eval_s1, eval_s2, eval_zw;
+  Fr beta, gamma, alpha, xi, v[5], k1, k2;
+};
 
 namespace detail {
 // Round3::compute_t for the plain driver, device-resident from the upload to t1, t2, t3: the four stages of csh_plonk_quot_* with the
@@ -467,6 +493,161 @@ inline std::array<std::vector<typename P::Fr>, 3> plain_compute_t(const PlonkDom
   check(csh_memcpy_d2h(out[2].data(), t3, sizeof(Fr) * (n + 6)), "csh_memcpy_d2h");
   return out;
 }
+
+// device buffers of one driver call, freed together at its end: nothing is released while the stream still works
+struct DevicePool {
+  std::vector<std::unique_ptr<DeviceMem>> mem;
+  uint64_t* fresh(size_t bytes) {
+    mem.emplace_back(new DeviceMem(bytes));
+    return (uint64_t*)mem.back()->p;
+  }
+  template <class Fr>
+  uint64_t* up(const std::vector<Fr>& v) {
+    uint64_t* d = fresh(sizeof(Fr) * v.size());
+    if (!v.empty()) check(csh_memcpy_h2d(d, v.data(), sizeof(Fr) * v.size()), "csh_memcpy_h2d");
+    return d;
+  }
+};
+
+// Round2::compute_z for the plain driver (round2.rs:104-190 with the array_prod_mul of co-plonk/src/mpc/plain.rs:195-247), device-resident
+// from the upload of the wire buffers to the blinded polynomial and its 4 n evaluations: csh_plonk_z_operands_dev, the two triple products
+// as csh_vec_mul_dev, their running products (csh_vec_prefix_prod_dev), the denominators' inverses (csh_vec_batch_inverse_dev), the last
+// product, rotate_right(1) straight into the polynomial's buffer, ifft over n, a zero-padded copy with fft over 4 n, and the blinding.
+// Nothing comes back to the host in between; every call is on the thread's stream.
+template <class P>
+inline PlonkPolyEval<typename P::Fr> plain_compute_z(const PlonkDomains<P>& domains, const PlonkRound2Inputs<typename P::Fr>& in) {
+  using Fr = typename P::Fr;
+  const size_t n = domains.domain.size, N = 4 * n;
+  if (n < 8 || domains.extended_domain.size != N) throw Error("compute_z: domain_size must be a power of two >= 8 with its 4 n domain");
+  for (const auto* v : {&in.buffer_a, &in.buffer_b, &in.buffer_c})
+    if (v->size() != n) throw Error("compute_z: every wire buffer has n elements");
+  for (const auto* v : {&in.s1, &in.s2, &in.s3})
+    if (v->size() != N) throw Error("compute_z: every permutation polynomial has 4 n evaluations");
+  DevicePool pool;
+  auto fresh = [&](size_t count) { return pool.fresh(sizeof(Fr) * count); };
+  auto mul = [&](const uint64_t* x, const uint64_t* y) {  // PlainPlonkDriver::mul_vec
+    uint64_t* o = fresh(n);
+    check(csh_vec_mul_dev(P::ID, x, y, o, n, nullptr), "csh_vec_mul_dev");
+    return o;
+  };
+  const uint64_t* sh[3] = {pool.up(in.buffer_a), pool.up(in.buffer_b), pool.up(in.buffer_c)};
+  const uint64_t* sigma[3] = {pool.up(in.s1), pool.up(in.s2), pool.up(in.s3)};
+  uint64_t* op[6];
+  for (auto& o : op) o = fresh(n);
+  const Fr challenges[4] = {in.beta, in.gamma, in.k1, in.k2};
+  check(csh_plonk_z_operands_dev(domains.extended_domain.dom, 0, 0, sh, sigma, (const uint64_t*)challenges, op, nullptr), "csh_plonk_z_operands_dev");
+  // array_prod_mul: the running products of n1 n2 n3 and of d1 d2 d3, the latter inverted
+  uint64_t *num = mul(mul(op[0], op[1]), op[2]), *den = mul(mul(op[3], op[4]), op[5]);
+  uint64_t* zeros = pool.fresh(sizeof(uint64_t));
+  check(csh_vec_prefix_prod_dev(P::ID, num, num, n, nullptr), "csh_vec_prefix_prod_dev");
+  check(csh_vec_prefix_prod_dev(P::ID, den, den, n, nullptr), "csh_vec_prefix_prod_dev");
+  check(csh_vec_batch_inverse_dev(P::ID, den, den, n, zeros, nullptr), "csh_vec_batch_inverse_dev");
+  // buffer_z = (num * den).rotate_right(1) (round2.rs:166-171), written where the polynomial's first n coefficients will stand
+  uint64_t *poly = fresh(n + 3), *eval = fresh(N);
+  check(csh_vec_rotate_right_dev(P::ID, mul(num, den), poly, n, 1, 1, nullptr), "csh_vec_rotate_right_dev");
+  check(csh_ifft_dev(domains.domain.dom, poly, 1, nullptr), "csh_ifft_dev");
+  const uint64_t* coeffs[1] = {poly};
+  const Fr one = Fr::one();
+  check(csh_poly_lincomb_dev(P::ID, 0, 0, coeffs, &n, (const uint64_t*)&one, 1, nullptr, nullptr, nullptr, 0, nullptr, eval, N, nullptr), "csh_poly_lincomb_dev");
+  check(csh_fft_dev(domains.extended_domain.dom, eval, 1, nullptr), "csh_fft_dev");
+  check(csh_plonk_blind_coefficients_dev(P::ID, poly, n, 1, (const uint64_t*)in.blinders, 3, nullptr), "csh_plonk_blind_coefficients_dev");
+  PlonkPolyEval<Fr> out{std::vector<Fr>(n + 3), std::vector<Fr>(N)};
+  uint64_t zero_count = 0;
+  check(csh_memcpy_d2h(out.poly.data(), poly, sizeof(Fr) * (n + 3)), "csh_memcpy_d2h");
+  check(csh_memcpy_d2h(out.eval.data(), eval, sizeof(Fr) * N), "csh_memcpy_d2h");
+  check(csh_memcpy_d2h(&zero_count, zeros, sizeof zero_count), "csh_memcpy_d2h");
+  if (zero_count) throw Error("Cannot invert zero");
+  return out;
+}
+
+// The scalar part of Round5::compute_r (round5.rs:118-190): calculate_lagrange_evaluations, calculate_pi, e2, e3, e4, r0 -- O(n_public +
+// log n) host arithmetic -- as the coefficients of the one linear combination: cs for z, t1, t2, t3, a, b, c; cp for qm, ql, qr, qo, qc,
+// s3, s1, s2; const0 for coefficient 0. xiw = xi w is compute_wxiw's root.
+template <class Fr>
+struct PlonkRound5Scalars {
+  Fr cs[7], cp[8], const0, xiw;
+};
+template <class P>
+inline PlonkRound5Scalars<typename P::Fr> round5_scalars(const PlonkRound5Inputs<typename P::Fr>& in) {
+  using Fr = typename P::Fr;
+  const size_t n = in.domain_size;
+  if (n == 0 || (n & (n - 1))) throw Error("InvalidDomainSize");
+  uint32_t lg = 0;
+  while ((size_t(1) << lg) < n) ++lg;
+  Fr w, shift;
+  groth16_roots_of_unity<Fr>(lg, w, shift);
+  auto neg = [](const Fr& x) { return Fr::sub(Fr::zero(), x); };
+  Fr xin = in.xi;
+  for (uint32_t i = 0; i < lg; ++i) xin = Fr::mul(xin, xin);
+  const Fr zh = Fr::sub(xin, Fr::one()), nf = Fr::from_u64(n);
+  // L_i(xi) = w^i zh / (n (xi - w^i)); pi = -sum L_i(xi) public_i
+  Fr wi = Fr::one(), l1 = Fr::zero(), pi = Fr::zero();
+  const size_t n_lagrange = in.public_inputs.empty() ? 1 : in.public_inputs.size();
+  for (size_t i = 0; i < n_lagrange; ++i) {
+    const Fr li = Fr::mul(Fr::mul(wi, zh), Fr::inv(Fr::mul(nf, Fr::sub(in.xi, wi))));
+    if (i == 0) l1 = li;
+    if (i < in.public_inputs.size()) pi = Fr::sub(pi, Fr::mul(li, in.public_inputs[i]));
+    wi = Fr::mul(wi, w);
+  }
+  const Fr betaxi = Fr::mul(in.beta, in.xi);
+  auto plus_gamma = [&](const Fr& e, const Fr& x) { return Fr::add(Fr::add(e, x), in.gamma); };
+  const Fr e2 = Fr::mul(Fr::mul(Fr::mul(plus_gamma(in.eval_a, betaxi), plus_gamma(in.eval_b, Fr::mul(betaxi, in.k1))),
+                                plus_gamma(in.eval_c, Fr::mul(betaxi, in.k2))), in.alpha);
+  const Fr e3 = Fr::mul(Fr::mul(Fr::mul(plus_gamma(in.eval_a, Fr::mul(in.beta, in.eval_s1)), plus_gamma(in.eval_b, Fr::mul(in.beta, in.eval_s2))),
+                                in.eval_zw), in.alpha);
+  const Fr e4 = Fr::mul(Fr::mul(in.alpha, in.alpha), l1);
+  const Fr r0 = Fr::sub(Fr::sub(pi, Fr::mul(e3, Fr::add(in.eval_c, in.gamma))), e4);
+  PlonkRound5Scalars<Fr> s;
+  const Fr mzh = neg(zh);
+  const Fr cs[7] = {Fr::add(e2, e4), mzh, Fr::mul(mzh, xin), Fr::mul(Fr::mul(mzh, xin), xin), in.v[0], in.v[1], in.v[2]};
+  const Fr cp[8] = {Fr::mul(in.eval_a, in.eval_b), in.eval_a, in.eval_b, in.eval_c, Fr::one(), neg(Fr::mul(e3, in.beta)), in.v[3], in.v[4]};
+  std::copy(cs, cs + 7, s.cs);
+  std::copy(cp, cp + 8, s.cp);
+  const Fr evs[5] = {in.eval_a, in.eval_b, in.eval_c, in.eval_s1, in.eval_s2};
+  s.const0 = r0;
+  for (int j = 0; j < 5; ++j) s.const0 = Fr::sub(s.const0, Fr::mul(in.v[j], evs[j]));
+  s.xiw = Fr::mul(in.xi, w);
+  return s;
+}
+// Round5::compute_r + compute_wxi (round5.rs:118-259) for the plain driver: ONE csh_poly_lincomb_dev over the seven shared and eight
+// public polynomials with const0 on coefficient 0, then div_by_zerofier(.., 1, xi) in place as csh_poly_div_linear_dev. -> W_xi, n + 5
+// coefficients (the popped remainder dropped as the reference drops it).
+template <class P>
+inline std::vector<typename P::Fr> plain_compute_r_wxi(const PlonkRound5Inputs<typename P::Fr>& in) {
+  using Fr = typename P::Fr;
+  if (in.xi.is_zero()) throw Error("Highly unlikely to be zero");
+  const PlonkRound5Scalars<Fr> s = round5_scalars<P>(in);
+  const size_t out_len = in.domain_size + 6;
+  const std::vector<Fr>* shares[7] = {&in.z, &in.t1, &in.t2, &in.t3, &in.a, &in.b, &in.c};
+  const std::vector<Fr>* publics[8] = {&in.qm, &in.ql, &in.qr, &in.qo, &in.qc, &in.s3, &in.s1, &in.s2};
+  DevicePool pool;
+  const uint64_t *sp[7], *pp[8];
+  size_t sl[7], pl[8];
+  for (int j = 0; j < 7; ++j) sp[j] = pool.up(*shares[j]), sl[j] = shares[j]->size();
+  for (int j = 0; j < 8; ++j) pp[j] = pool.up(*publics[j]), pl[j] = publics[j]->size();
+  uint64_t* r = pool.fresh(sizeof(Fr) * out_len);
+  check(csh_poly_lincomb_dev(P::ID, 0, 0, sp, sl, (const uint64_t*)s.cs, 7, pp, pl, (const uint64_t*)s.cp, 8, (const uint64_t*)&s.const0, r, out_len, nullptr),
+        "csh_poly_lincomb_dev");
+  check(csh_poly_div_linear_dev(P::ID, r, out_len, 1, (const uint64_t*)&in.xi, nullptr, nullptr, 0, r, nullptr, nullptr), "csh_poly_div_linear_dev");
+  std::vector<Fr> wxi(out_len - 1);
+  check(csh_memcpy_d2h(wxi.data(), r, sizeof(Fr) * wxi.size()), "csh_memcpy_d2h");
+  return wxi;
+}
+// Round5::compute_wxiw (round5.rs:262-278): (z(X) - eval_zw) / (X - xi w), the subtraction on coefficient 0 as the division loads it
+template <class P>
+inline std::vector<typename P::Fr> plain_compute_wxiw(const PlonkRound5Inputs<typename P::Fr>& in) {
+  using Fr = typename P::Fr;
+  if (in.z.size() < 2) throw Error("compute_wxiw: z has fewer than two coefficients");
+  const Fr xiw = round5_scalars<P>(in).xiw;
+  if (xiw.is_zero()) throw Error("Highly unlikely to be zero");
+  DevicePool pool;
+  uint64_t* z = pool.up(in.z);
+  check(csh_poly_div_linear_dev(P::ID, z, in.z.size(), 1, (const uint64_t*)&xiw, (const uint64_t*)&in.eval_zw, nullptr, 0, z, nullptr, nullptr),
+        "csh_poly_div_linear_dev");
+  std::vector<Fr> wxiw(in.z.size() - 1);
+  check(csh_memcpy_d2h(wxiw.data(), z, sizeof(Fr) * wxiw.size()), "csh_memcpy_d2h");
+  return wxiw;
+}
 }  // namespace detail
 
 // ---- plain drivers (co-plonk/src/mpc/plain.rs, co-noir-common/src/mpc/plain.rs) -----------------------------------
@@ -512,6 +693,12 @@ struct PlainPlonkDriver {
   static std::array<std::vector<Fr>, 3> compute_t(const PlonkDomains<P>& domains, const PlonkQuotientZkey<Fr>& zkey, const PlonkQuotientInputs<Fr, Fr>& in) {
     return detail::plain_compute_t<P>(domains, zkey, in);
   }
+  // Round2::compute_z (round2.rs:104-190) -> the blinded z(X) and its 4 n evaluations; Round5::compute_r + compute_wxi (round5.rs:118-259)
+  // -> W_xi; Round5::compute_wxiw (round5.rs:262-278) -> W_xiw. The Rep3 and Shamir drivers have no compute_z here: their array_prod_mul
+  // is the network's; the stages themselves (csh_plonk_z_operands_dev, csh_poly_lincomb_dev, ...) take every share type
+  static PlonkPolyEval<Fr> compute_z(const PlonkDomains<P>& domains, const PlonkRound2Inputs<Fr>& in) { return detail::plain_compute_z<P>(domains, in); }
+  static std::vector<Fr> compute_r_wxi(const PlonkRound5Inputs<Fr>& in) { return detail::plain_compute_r_wxi<P>(in); }
+  static std::vector<Fr> compute_wxiw(const PlonkRound5Inputs<Fr>& in) { return detail::plain_compute_wxiw<P>(in); }
   // co-plonk plain.rs:127-140 / co-noir plain.rs:240-252: every element's own inverse() there
   static std::vector<Fr> inv_vec(std::vector<Fr> a) {
     if (detail::batch_inverse<P>(a)) throw Error("Cannot invert zero");

@@ -430,6 +430,49 @@ int csh_plonk_quot_finish_dev(csh_curve_t field_of, size_t n, uint32_t protocol,
                               const uint64_t* ctz_dev, const uint64_t* b9_b10 /* host, 2 shares */, uint64_t* t1_dev, uint64_t* t2_dev,
                               uint64_t* t3_dev, void* stream);
 
+/* ---- circom PLONK rounds 2 and 5: z operands, rotation, blinding, the linearisation and opening numerators ----
+ * What a device-resident PLONK prover does to whole vectors between the network rounds of Round2::compute_z
+ * (co-circom/co-plonk/src/round2.rs:104-155, its rotate_right at :171), in blind_coefficients (co-plonk/src/lib.rs:162-177, rounds 1 and 2)
+ * and in Round5::compute_r + compute_wxi (round5.rs:118-259). Affine in the shares with public coefficients, so no network round.
+ * protocol, party_id and the add_with_public rule (mpc-core/src/protocols/rep3/arithmetic.rs:41-49, shamir/arithmetic.rs:45) are those of
+ * the quotient stages above: a public value goes to component a for protocol 0 and Rep3 party 0, to b for Rep3 party 1, nowhere for
+ * Rep3 party 2. Challenges, coefficients and blinding shares are host pointers read during the call, arkworks-Montgomery.
+ * Stream-ordered: no host synchronisation, scratch from the stream's workspace. Outputs are canonical. CSH_ERR_INVALID before any device
+ * work: a NULL pointer, a protocol outside 0..1 or a party outside 0..2, a size outside the stated range, and any output range that
+ * overlaps an input range or another output of the same call. */
+/* The operands of the grand product, round2.rs:116-155 (the loop the reference marks "TODO: multithread me"). ext_dom is the EXTENDED
+ * domain (N = 4 n >= 32 points, snarkjs root), as the quotient stages take it; w = w_ext^4 generates the n-point domain and its powers are
+ * made on the device. shares_dev[0..3) = buffer_a, buffer_b, buffer_c (n shares); sigma_dev[0..3) = the zkey's 4 n evaluations of S1, S2, S3,
+ * read at index 4 i; challenges = beta, gamma, k1, k2. out_dev[0..6) = n1, n2, n3, d1, d2, d3 (n shares), for i < n:
+ * n1 = a (+) (beta w^i + gamma), n2 = b (+) (beta k1 w^i + gamma), n3 = c (+) (beta k2 w^i + gamma), d1 = a (+) (beta S1[4 i] + gamma),
+ * d2 = b (+) (beta S2[4 i] + gamma), d3 = c (+) (beta S3[4 i] + gamma). */
+int csh_plonk_z_operands_dev(csh_domain_t ext_dom, uint32_t protocol, uint32_t party_id, const uint64_t* const* shares_dev /* 3 */,
+                             const uint64_t* const* sigma_dev /* 3 */, const uint64_t* challenges /* host, 4 elements */,
+                             uint64_t* const* out_dev /* 6 */, void* stream);
+/* out[(i + k) mod n] = in[i] for n shares of ncomp elements, k < n: buffer_z.rotate_right(1), round2.rs:171. out must not overlap in;
+ * n == 0 does nothing. */
+int csh_vec_rotate_right_dev(csh_curve_t field_of, const uint64_t* in_dev, uint64_t* out_dev, size_t n, uint32_t ncomp, size_t k, void* stream);
+/* blind_coefficients, co-plonk/src/lib.rs:162-177 (called at round1.rs:132 and round2.rs:181), on the polynomial the next MSM reads:
+ * poly[j] -= coeff_rev[k - 1 - j] and poly[n + j] = coeff_rev[k - 1 - j] for j < k. poly_dev has room for n + k shares; 1 <= k <= 3 <= n;
+ * coeff_rev = k shares on the host. One small launch. */
+int csh_plonk_blind_coefficients_dev(csh_curve_t field_of, uint64_t* poly_dev, size_t n, uint32_t ncomp, const uint64_t* coeff_rev /* host, k shares */,
+                                     size_t k, void* stream);
+/* A ragged linear combination of shared and public polynomials under public coefficients, for i < out_len:
+ *   out[i] = sum_{j < ks, i < share_lens[j]} cs_j S_j[i]  (+)  (sum_{j < kp, i < public_lens[j]} cp_j P_j[i] + [i = 0] const0).
+ * Lengths (shares, elements) may differ and may be 0 (the pointer is then not looked at); each is at most out_len <= 2^28; positions past
+ * every input are written as zero. ks + kp >= 1, ks <= 64, kp <= 64. const0 may be NULL. A coefficient equal to one skips its
+ * multiplication. Pointers, lengths and constants travel as kernel arguments, 16 vectors per launch; every input is read once and nothing
+ * is copied. out may not overlap any input. Round5::compute_r and compute_wxi, round5.rs:118-259, are ONE call followed by
+ * csh_poly_div_linear_dev(root = xi): shares z, t1, t2, t3, a, b, c under e24, -zh, -zh xi^n, -zh xi^2n, v0, v1, v2; public qm, ql, qr, qo,
+ * qc, s3, s1, s2 under ea eb, ea, eb, ec, 1, -e3 beta, v3, v4; const0 = r0 - v0 ea - v1 eb - v2 ec - v3 es1 - v4 es2. The batched
+ * polynomials of Gemini (shared and public polynomials under powers of rho, compute_batched_polys, co-noir/co-ultrahonk/src/co_decider/co_shplemini/co_shplemini_prover.rs:49-119)
+ * are the same call. */
+int csh_poly_lincomb_dev(csh_curve_t field_of, uint32_t protocol, uint32_t party_id, const uint64_t* const* shares_dev /* host array of ks device ptrs */,
+                         const size_t* share_lens, const uint64_t* share_coeffs /* host, ks elements */, size_t ks,
+                         const uint64_t* const* public_dev /* host array of kp device ptrs */, const size_t* public_lens,
+                         const uint64_t* public_coeffs /* host, kp elements */, size_t kp, const uint64_t* const0 /* host, may be NULL */,
+                         uint64_t* out_dev, size_t out_len, void* stream);
+
 /* Rep3 correlated masks generated on the device ("next" row f2): out[i] = from_be_bytes_mod_order(a_i) -
  * from_be_bytes_mod_order(b_i), a_i / b_i = the 32-byte chunks number elem_offset{1,2} + i of the ChaCha12 keystreams
  * of seed1 (own key) and seed2 (previous party's key): byte-compatible with Rep3Rand::masking_field_elements_vec

@@ -11,4 +11,4 @@ mod cold;
 pub mod drivers;
 pub use drivers::{hip_fast_msm, HipPlainUltraHonkDriver, HipRep3UltraHonkDriver, HipShamirUltraHonkDriver};
 pub mod scans;
-pub use scans::{hip_batch_inverse, hip_eval_poly, hip_prefix_product, hip_factor_roots};
+pub use scans::{hip_batch_inverse, hip_batched_polys_dev, hip_eval_poly, hip_prefix_product, hip_factor_roots};

@@ -3,7 +3,7 @@
 //! ("field scans"). `field` is the `csh_curve_t` whose scalar field the elements live in (`sys::CSH_BN254` for
 //! BN254 G1); `S` is a field element or a share made of field elements (`Rep3PrimeFieldShare`: two).
 use ark_ff::PrimeField;
-use co_groth16_hip::error::hip_ok;
+use co_groth16_hip::error::{check, hip_ok};
 use co_groth16_hip::layout::{limbs_mut, limbs_of, ncomp};
 use cosnarks_hip_sys as sys;
 
@@ -94,4 +94,30 @@ pub fn hip_evaluate_mle<F: PrimeField, S: Copy + Default>(field: i32, coeffs: &[
         sys::csh_mle_fold_rounds(field, limbs_of(coeffs), coeffs.len(), ncomp::<S>(), limbs_of(&evaluation_points[..dim]), dim, std::ptr::null_mut(), res.cast())
     });
     out
+}
+
+/// The batched polynomials of Gemini, `compute_batched_polys` (co-ultrahonk co_decider/co_shplemini/co_shplemini_prover.rs:49-119): one of
+/// `batched_unshifted` / `batched_to_be_shifted` = sum_j rho^(first + j) f_j over the precomputed (public) polynomials, promoted to a share,
+/// plus the same over the shared ones -- the reference's `add_scaled_slice` loops and `promote_poly` as ONE call on device-resident
+/// polynomials. `public` / `shared`: device pointers with their lengths in elements / shares (a polynomial shorter than `n` counts as
+/// zero behind its end); `public_scalars` / `shared_scalars`: the powers of rho the reference's `running_scalar` takes for them; `out`: n
+/// shares, another buffer. `party` = `state.id()` as 0, 1, 2 (0 for the plain and Shamir drivers). Stream-ordered on the calling thread's stream.
+#[allow(clippy::too_many_arguments)]
+pub fn hip_batched_polys_dev<F: PrimeField, S: Copy>(
+    field: i32,
+    party: u32,
+    public: &[*const u64],
+    public_lens: &[usize],
+    public_scalars: &[F],
+    shared: &[*const u64],
+    shared_lens: &[usize],
+    shared_scalars: &[F],
+    out: *mut u64,
+    n: usize,
+) -> eyre::Result<()> {
+    assert!(public.len() == public_lens.len() && public.len() == public_scalars.len());
+    assert!(shared.len() == shared_lens.len() && shared.len() == shared_scalars.len());
+    check(unsafe {
+        sys::csh_poly_lincomb_dev(field, ncomp::<S>() - 1, party, shared.as_ptr(), shared_lens.as_ptr(), limbs_of(shared_scalars), shared.len(), public.as_ptr(), public_lens.as_ptr(), limbs_of(public_scalars), public.len(), std::ptr::null(), out, n, std::ptr::null_mut())
+    })
 }

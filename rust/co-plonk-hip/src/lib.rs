@@ -14,3 +14,7 @@ pub mod scans;
 pub use scans::{hip_batch_inverse, hip_eval_poly, hip_prefix_product, hip_div_by_zerofier};
 pub mod round3;
 pub use round3::{hip_quotient_blinders, hip_quotient_combine, hip_quotient_finish, hip_quotient_operands};
+pub mod round2;
+pub use round2::{hip_blind_coefficients, hip_rotate_right, hip_z_operands};
+pub mod round5;
+pub use round5::{hip_poly_lincomb, hip_wxi_numerator, round5_coefficients, Round5Coefficients, Round5Scalars};
