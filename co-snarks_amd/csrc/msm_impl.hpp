@@ -68,7 +68,9 @@ __device__ __forceinline__ void load_scalar(const Fr* __restrict__ scalars, size
 // Signed-digit codes of every scalar, dig[row(w) * n + i] (row(w) = w, or the grouped-table order (w % W') * g + w / W'). Straight-line
 // per window: the scalar is shifted right by c bits after every digit (constant register indices, no indexed register access), the code
 // is selected without branches and every row gets exactly one 2-byte store per scalar (rows past W hold no digits). Same recoding
-// as for_each_digit (msm_digits.hpp), which the host self-test and the oracle comparison pin. Round 3: stage "digits + histogram" 0.081-0.087 -> 0.071 ms at 2^20, 0.91 -> 0.68 ms at 2^24 (profiles/archive/r03_x_digits_stages.log)
+// as for_each_digit (msm_digits.hpp), which the host self-test and the oracle comparison pin; this device form -- with the balanced
+// windows and the grouped row order that the host form cannot express -- is pinned by tests/test_gpu_msm_sort.py, which runs the sort
+// stage alone (selftest_dev.hip csh_selftest_msm_sort_dev) and compares every bucket list with tests/msm_sort_ref.py. Round 3: stage "digits + histogram" 0.081-0.087 -> 0.071 ms at 2^20, 0.91 -> 0.68 ms at 2^24 (profiles/archive/r03_x_digits_stages.log)
 // (the former loop over for_each_digit compiled to 116 basic blocks with indexed register moves and an integer division per row).
 template <class Fr>
 __global__ __launch_bounds__(MSM_BLK) void k_msm_digits(const Fr* __restrict__ scalars, MsmParams p, uint16_t* __restrict__ dig) {

@@ -393,13 +393,27 @@ bool msm_sort_two_level(const MsmParams& p) {
   return p.n >= (1u << 20);
 }
 
+SortPath msm_sort_path(const MsmParams& p) {
+  SortPath s{msm_sort_two_level(p), false, false};
+  if (!s.two_level) return s;
+  // 4-byte intermediate records when every stored entry id fits 23 bits (n, or rows x bases with tables, <= 2^23); tune "msm_variant"
+  // bit 3 forces the 8-byte records (A/B runs, tests). (4-byte records + a separate sign byte for ids up to 2^24 were
+  // measured and lose to the 8-byte records: scatter 2.29 against 2.10 ms on BN254 G1 2^24 -- byte-granular scattered
+  // writes cost more than the 3 bytes per entry they save, profiles/archive/r02_g_rec_stages.log.)
+  const uint64_t max_id = p.remap_n ? (uint64_t)(p.n / p.remap_n) * p.remap_stride : (uint64_t)p.n;  // stored ids: table indices
+  const int variant = tune().msm_variant.load(std::memory_order_relaxed);
+  s.rec4 = (variant & 8) == 0 && max_id <= (1u << (31 - PART_LB));
+  s.per_partition = (variant & 32) != 0;
+  return s;
+}
+
 // the two-level scatter with 4-byte (REC = 1) or 8-byte intermediate records
 template <int REC>
-static void launch_two_level(const MsmParams& p, const SortBuffers& b, hipStream_t st) {
+static void launch_two_level(const MsmParams& p, const SortBuffers& b, bool per_partition, hipStream_t st) {
   const uint32_t nparts = p.NB / PART_BUCKETS;
   hipLaunchKernelGGL(k_msm_scatter_l1<REC>, dim3(p.CH, p.W), dim3(SORT_BLK), 0, st, p, b.dig, b.part_cnt, (void*)b.inter);
   // level 2: one block per slice of about one tile of a partition (default), or -- tune "msm_variant" bit 5 -- one block per partition
-  if ((tune().msm_variant.load(std::memory_order_relaxed) & 32) != 0) {
+  if (per_partition) {
     hipLaunchKernelGGL(k_msm_scatter_l2<REC>, dim3(nparts, p.W), dim3(SORT_BLK), 0, st, p, b.start, (const void*)b.inter, b.sorted);
   } else {
     const uint32_t l2_blocks = (uint32_t)(p.n / L2_TILE) + nparts + 1;
@@ -408,7 +422,8 @@ static void launch_two_level(const MsmParams& p, const SortBuffers& b, hipStream
 }
 
 int msm_sort_launch(const MsmParams& p, const SortBuffers& b, hipStream_t st, hipEvent_t* ev) {
-  const bool two_level = msm_sort_two_level(p);
+  const SortPath path = msm_sort_path(p);
+  const bool two_level = path.two_level;
   const size_t sort_lds = sizeof(uint32_t) * p.NB;
   if (sort_lds > 48 * 1024) {
     CSH_TRY(raise_lds_limit((const void*)k_msm_hist_lds, 128 * 1024));
@@ -425,13 +440,7 @@ int msm_sort_launch(const MsmParams& p, const SortBuffers& b, hipStream_t st, hi
   if (ev) CSH_HIP(hipEventRecord(ev[2], st));
   if (two_level) {
     hipLaunchKernelGGL(k_msm_part_offsets, dim3((p.NB / PART_BUCKETS + 255) / 256, p.W), dim3(256), 0, st, p, b.start, b.part_cnt);
-    // 4-byte intermediate records when every stored entry id fits 23 bits (n, or rows x bases with tables, <= 2^23); tune "msm_variant"
-    // bit 3 forces the 8-byte records (A/B runs, tests). (4-byte records + a separate sign byte for ids up to 2^24 were
-    // measured and lose to the 8-byte records: scatter 2.29 against 2.10 ms on BN254 G1 2^24 -- byte-granular scattered
-    // writes cost more than the 3 bytes per entry they save, profiles/archive/r02_g_rec_stages.log.)
-    const uint64_t max_id = p.remap_n ? (uint64_t)(p.n / p.remap_n) * p.remap_stride : (uint64_t)p.n;  // stored ids: table indices
-    const bool wide_only = (tune().msm_variant.load(std::memory_order_relaxed) & 8) != 0;
-    (!wide_only && max_id <= (1u << (31 - PART_LB))) ? launch_two_level<1>(p, b, st) : launch_two_level<0>(p, b, st);
+    path.rec4 ? launch_two_level<1>(p, b, path.per_partition, st) : launch_two_level<0>(p, b, path.per_partition, st);  // msm_sort_path
   } else {
     hipLaunchKernelGGL(k_msm_scatter_lds, dim3(p.CH, p.W), dim3(SORT_BLK), sort_lds, st, p, b.dig, b.start, b.blkcnt, b.sorted);
   }

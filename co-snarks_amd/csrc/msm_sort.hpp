@@ -167,6 +167,14 @@ __device__ __forceinline__ void l2_load_rank(const SortRec<REC>* __restrict__ in
 #endif
 
 bool msm_sort_two_level(const MsmParams& p);
+// Which scatter msm_sort_launch runs for p: decided in this one place, so that the device self-test of the stage (selftest_dev.hip
+// csh_selftest_msm_sort_dev) reports the path that ran and not a second copy of the rule. rec4 / per_partition: two-level mode only.
+struct SortPath {
+  bool two_level;      // level 1 by partition + level 2 by the low bucket byte; false: k_msm_scatter_lds
+  bool rec4;           // 4-byte intermediate records (rec_pack<1>), false: 8-byte
+  bool per_partition;  // level 2 with one block per partition (k_msm_scatter_l2), false: tile-parallel (k_msm_scatter_l2t)
+};
+SortPath msm_sort_path(const MsmParams& p);
 // Launches hist -> colscan -> scan -> scatter on `st`. ev (nullable): records ev[1] after the histogram, ev[2] after
 // the scan, ev[3] after the scatter.
 int msm_sort_launch(const MsmParams& p, const SortBuffers& b, hipStream_t st, hipEvent_t* ev);

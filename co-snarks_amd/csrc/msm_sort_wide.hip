@@ -36,7 +36,9 @@ constexpr int W2_TILE = L2_TILE;
 constexpr uint32_t WCODE_ZERO = 0xFFFFFFFFu;
 
 // Signed-digit codes of scalar i: code[w] = (bucket - 1) | negative << 31, WCODE_ZERO for a zero digit. Same recoding as k_msm_digits /
-// for_each_digit (uniform c-bit windows; the table rows are 2^(c w) P). The window width CB is a template parameter: digit w sits at
+// for_each_digit (uniform c-bit windows; the table rows are 2^(c w) P); pinned on the device by tests/test_gpu_msm_sort.py, which runs
+// this stage alone (selftest_dev.hip csh_selftest_msm_sort_dev) against tests/msm_sort_ref.py, at the same edge scalars as k_msm_digits
+// for every scalar field. The window width CB is a template parameter: digit w sits at
 // the compile-time bit offset w CB, so it is ONE funnel shift of two limbs (v_alignbit_b32) instead of a shift of the whole scalar by a
 // run-time count after every digit -- the recoding dropped from ~440 to ~130 instructions per scalar, and it runs twice (k_wide_hist1,
 // k_wide_scatter1: 2^24 scalars, level 1 1.53 -> see profiles/r06_* for the measured effect).

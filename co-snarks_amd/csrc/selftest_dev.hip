@@ -1,6 +1,6 @@
 // Device-executed self-test hooks for the arithmetic that exists on the device only: curve_quad.hpp (one XYZZ point over a DPP
 // quad) and curve_pair.hpp (one Fp2 value over a lane pair), plus a launcher of the real window-reduction and fold-tree kernels
-// on bucket arrays the caller chooses, and host-pointer entry points around the two fused launchers that end a witness map
+// on bucket arrays the caller chooses, a runner of the MSM sort stage alone (digits, bucket offsets, bucket lists copied back), and host-pointer entry points around the two fused launchers that end a witness map
 // (vec_ops.hip), which the C ABI reaches only through csh_groth16_h_dev. The kernels here are compiled with the device form of the limb-bound contract
 // (field29.hpp, CSH_CHECK_BOUNDS_DEVICE): a violated operand bound is counted in g_bound_record, never trapped; every entry
 // point hands the record back and clears it. Test infrastructure; not declared in include/cosnarks_hip.h.
@@ -355,6 +355,75 @@ int msm_tail_t(int form, const void* affine_pts, const uint8_t* neg, size_t npts
   return msm_tail_selftest_t<Cfg>(dense.data(), NB, S, form, out_xyzz);
 }
 
+// ---- the sort stage alone -------------------------------------------------------------------------------------------------------
+// Plan, scratch and launches are the product's own (msm_plan, msm_sort_bytes, GroupOps::sort = msm_sort_stage<Fr> as msm.hip instantiates
+// it: no kernel of the stage gets a second home here); this only uploads the scalars, fills the scratch with 0xFF bytes (the arena of
+// a real call is dirty too: nothing may rely on what a buffer held before) and copies the stage's three outputs back.
+enum : int {
+  SI_C = 0, SI_W, SI_WIDE, SI_NB, SI_L, SI_LN, SI_DIG_G, SI_DIG_WP, SI_REMAP_N, SI_REMAP_STRIDE, SI_REMAP_OFF,  // digit half + remap
+  SI_SRT_N, SI_SRT_W, SI_SRT_WIDE,                                                                               // sort half
+  SI_PATH,           // 0 single-level, 1 two-level, 2 wide
+  SI_REC_BYTES,      // intermediate record of the two-level / wide path: 4 or 8 (0: single-level)
+  SI_PER_PARTITION,  // two-level: 1 = level 2 with one block per partition
+  SI_WIDE_LB,        // wide: log2 buckets per level-2 partition
+  SI_CH, SI_CHUNK_LEN,  // chunks and scalars (wide) / entries (plain) per chunk
+  SI_WORDS = 24
+};
+int msm_sort_selftest(csh_curve_t curve, const uint64_t* scalars, size_t n, int mont, const uint64_t* table, uint32_t* info, uint32_t* start, size_t start_words,
+                      uint32_t* nlanes, uint32_t* sorted, size_t sorted_words) {
+  const GroupOps* G = group_ops(curve, CSH_G1);
+  if (!G) return CSH_ERR_INVALID;
+  CSH_REQUIRE(scalars && info, "selftest_msm_sort: NULL argument");
+  CSH_REQUIRE(n >= 1 && n <= (size_t(1) << 24), "selftest_msm_sort: n out of range");
+  CSH_TRY(ensure_device());  // the planner reads the device's SIMD count
+  MsmTable tb{};
+  if (table) {
+    CSH_REQUIRE(table[0] >= 2 && table[0] <= 22 && table[1] >= 1, "selftest_msm_sort: table window width or rows out of range");
+    tb = MsmTable{(int)table[0], 0, (size_t)table[2], (size_t)table[3]};
+    CSH_REQUIRE(table[1] <= (uint64_t)windows_for(G->scalar_bits, tb.c), "selftest_msm_sort: more table rows than windows");
+    tb.rows = (int)table[1];
+    CSH_REQUIRE(table[3] <= table[2] && n <= table[2] - table[3], "selftest_msm_sort: offset + n exceeds the table's stride");
+    // entry ids fit 31 bits (bit 31 is the sign), as msm_use_table demands of a handle
+    CSH_REQUIRE((uint64_t)tb.stride * tb.rows < (uint64_t(1) << 31) && (uint64_t)n * tb.rows < (uint64_t(1) << 31), "selftest_msm_sort: table ids exceed 31 bits");
+  }
+  const MsmPlan plan = msm_plan(n, G->scalar_bits, mont ? 1 : 0, 1, table ? &tb : nullptr);
+  const MsmParams &p = plan.srt, &pd = plan.dig;
+  const bool wide = msm_sort_is_wide(p);
+  CSH_REQUIRE(p.c <= 16 || wide, "selftest_msm_sort: windows wider than 16 bits need one table row per window");
+  memset(info, 0, SI_WORDS * sizeof(uint32_t));
+  info[SI_C] = (uint32_t)pd.c, info[SI_W] = (uint32_t)pd.W, info[SI_WIDE] = (uint32_t)pd.wide, info[SI_NB] = p.NB, info[SI_L] = p.L, info[SI_LN] = p.Ln;
+  info[SI_DIG_G] = pd.dig_g, info[SI_DIG_WP] = pd.dig_wp, info[SI_REMAP_N] = p.remap_n, info[SI_REMAP_STRIDE] = p.remap_stride, info[SI_REMAP_OFF] = p.remap_off;
+  info[SI_SRT_N] = p.n, info[SI_SRT_W] = (uint32_t)p.W, info[SI_SRT_WIDE] = (uint32_t)p.wide;
+  if (wide) {
+    const WidePlan wp = msm_wide_plan(p, pd);
+    info[SI_PATH] = 2, info[SI_REC_BYTES] = wp.rec4 ? 4 : 8, info[SI_WIDE_LB] = wp.lb, info[SI_CH] = wp.CH, info[SI_CHUNK_LEN] = wp.chunk_tiles * 512;
+  } else {
+    const SortPath sp = msm_sort_path(p);
+    info[SI_PATH] = sp.two_level ? 1 : 0, info[SI_REC_BYTES] = sp.two_level ? (sp.rec4 ? 4 : 8) : 0, info[SI_PER_PARTITION] = sp.per_partition ? 1 : 0;
+    info[SI_CH] = p.CH, info[SI_CHUNK_LEN] = p.chunk_len;
+  }
+  if (!start && !nlanes && !sorted) return CSH_OK;  // the plan only: the caller sizes its buffers from it
+  const size_t nstart = ((size_t)p.NB + 2) * p.W, nsorted = (size_t)p.n * p.W;
+  CSH_REQUIRE(start && nlanes && sorted && start_words >= nstart && sorted_words >= nsorted, "selftest_msm_sort: output buffers too small");
+  DevMem dsc;
+  CSH_TRY(dsc.alloc(32 * n));
+  CSH_HIP(hipMemcpy(dsc.p, scalars, 32 * n, hipMemcpyHostToDevice));
+  hipStream_t st = resolve_stream(nullptr);
+  Arena& ar = arena_for(st);
+  const size_t bytes = msm_sort_bytes(p, pd);
+  CSH_TRY(ar.reserve(bytes));
+  CSH_HIP(hipMemset(ar.base, 0xFF, bytes));
+  CSH_HIP(hipDeviceSynchronize());  // upload and fill ran on the null stream, the stage runs on the thread's own
+  SortOut so{};
+  CSH_TRY(G->sort(p, pd, dsc.as<uint64_t>(), st, ar, &so, nullptr));
+  CSH_HIP(hipGetLastError());
+  CSH_HIP(hipStreamSynchronize(st));
+  CSH_HIP(hipMemcpy(start, so.start, nstart * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  CSH_HIP(hipMemcpy(nlanes, so.nlanes, (size_t)p.W * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  CSH_HIP(hipMemcpy(sorted, so.sorted, nsorted * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  return CSH_OK;
+}
+
 // ---- the two fused forms a witness map ends with (vec_ops.hip: vec_mul_sub_dev, rep3_local_mul_sub_dev) ----------------------------------
 // Host pointers in and out around the product launcher `launch(subtrahend, out, stream)`: no kernel of its own. alias: the subtrahend is
 // uploaded into the output buffer and the launcher is handed that buffer for both, as csh_groth16_h_dev does; otherwise the output
@@ -446,6 +515,16 @@ int csh_selftest_msm_tail_dev(int curve, int group, int form, const void* affine
                               const uint32_t* bucket_off, size_t nocc, uint32_t NB, uint32_t S, void* out_xyzz) {
   CSH_TRY(ensure_device());
   ST_GROUP_DISPATCH(curve, group, (msm_tail_t<Cfg>(form, affine_pts, neg, npts, bucket_ids, bucket_off, nocc, NB, S, out_xyzz)));
+}
+
+// The MSM sort stage alone (digits -> counting sort; plain single-level, plain two-level or wide, as msm_plan and the tune knobs decide)
+// on n >= 1 host scalars of the curve's scalar field (BN254 Fr, BLS12-381 Fr, Grumpkin = BN254 Fq, BLS12-377 Fr). table: NULL, or
+// {c, rows, stride, offset} of fixed-base tables as in MsmTable. info: 24 words, the plan that ran (SI_* above). With start, nlanes and
+// sorted all NULL only info is filled; otherwise start = [W'][NB + 2], nlanes = [W'], sorted = [W'][n'] words (W' = info[SI_SRT_W],
+// n' = info[SI_SRT_N]) as the bucket stage would read them.
+int csh_selftest_msm_sort_dev(int curve, const uint64_t* scalars, size_t n, int mont, const uint64_t* table, uint32_t* info, uint32_t* start, size_t start_words,
+                              uint32_t* nlanes, uint32_t* sorted, size_t sorted_words) {
+  return msm_sort_selftest((csh_curve_t)curve, scalars, n, mont, table, info, start, start_words, nlanes, sorted, sorted_words);
 }
 
 // out = a * b - c through csh::vec_mul_sub_dev (k_vec_mul_sub), n elements, host pointers. c_aliases_out: c travels in the output buffer.
