@@ -31,6 +31,11 @@ from .bindings import (  # noqa: F401
     fr_bytes,
     groth16_h,
     have_device,
+    HonkMemoryRecords,
+    honk_lookup_operands,
+    honk_perm_operands,
+    honk_w4_records,
+    honk_z_perm_place,
     lib,
     lib_path,
     lincomb,

@@ -614,6 +614,71 @@ def poly_lincomb(curve: int, protocol: int, party: int, shares, share_lens, shar
     return out
 
 
+class HonkMemoryRecords:
+    """The memory-record rows of an UltraHonk proving key (memory_read_records, memory_write_records and the rows of
+    memory_records_shared) as uint32 lists on the device, uploaded once. The contract of csh_honk_w4_records_dev is checked here, on the
+    host: every index is below n and occurs once, within a list or across lists."""
+
+    def __init__(self, n: int, read=(), write=(), shared=()):
+        lists = [np.ascontiguousarray(np.asarray(v, dtype=np.int64).reshape(-1)) for v in (read, write, shared)]
+        every = np.concatenate(lists)
+        if every.size and (every.min() < 0 or every.max() >= n):
+            raise CoSnarksHipError("honk memory records: an index is outside 0 .. n - 1")
+        if np.unique(every).size != every.size:
+            raise CoSnarksHipError("honk memory records: an index occurs twice (a duplicate would be a race on the device)")
+        self.n = int(n)
+        self.counts = [int(v.size) for v in lists]
+        self.bufs = [DeviceBuffer.from_host(v.astype(np.uint32)) if v.size else None for v in lists]
+
+
+def honk_w4_records(curve: int, protocol: int, party: int, w, w4, n: int, etas, records: "HonkMemoryRecords", type_share=None, stream=None):
+    """csh_honk_w4_records_dev: w = the DeviceBuffers w_l, w_r, w_o (n shares); w4 (n shares) in place, returned; etas = eta_1, eta_2,
+    eta_3 on the host; type_share = the DeviceBuffer of the shared records' type shares (None without shared records)."""
+    et = _u64(etas)
+    assert len(w) == 3 and et.size == 12 and records.n == n
+    nr, nw, ns = records.counts
+    _check(lib().csh_honk_w4_records_dev(curve, C.c_uint32(protocol), C.c_uint32(party), _devptr_array(w), _devptr(w4), C.c_size_t(n), _p(et),
+                                         _devptr(records.bufs[0]), C.c_size_t(nr), _devptr(records.bufs[1]), C.c_size_t(nw),
+                                         _devptr(records.bufs[2]), _devptr(type_share), C.c_size_t(ns), _stream(stream)))
+    return w4
+
+
+def honk_lookup_operands(curve: int, protocol: int, party: int, shares, public, n: int, challenges, outs, stream=None):
+    """csh_honk_lookup_operands_dev: shares = the DeviceBuffers w_l, w_r, w_o, lookup_read_tags (n shares); public = q_r, q_m, q_c, q_o,
+    table_1..4, q_lookup (n elements); challenges = beta, gamma on the host; outs = the DeviceBuffers prod, sel, which are returned."""
+    ch = _u64(challenges)
+    assert len(shares) == 4 and len(public) == 9 and len(outs) == 2 and ch.size == 8
+    _check(lib().csh_honk_lookup_operands_dev(curve, C.c_uint32(protocol), C.c_uint32(party), _devptr_array(shares), _devptr_array(public),
+                                              C.c_size_t(n), _p(ch), _devptr_array(outs), _stream(stream)))
+    return outs
+
+
+def _honk_ranges(ranges):
+    flat = [int(x) for r in (ranges or ()) for x in r]
+    return ((C.c_size_t * len(flat))(*flat) if flat else None), len(flat) // 2
+
+
+def honk_perm_operands(curve: int, protocol: int, party: int, shares, public, n: int, domain_size: int, ranges, challenges, outs, stream=None):
+    """csh_honk_perm_operands_dev: shares = the DeviceBuffers w_l, w_r, w_o, w_4 (n shares); public = id_1..4, sigma_1..4 (n elements);
+    ranges = the active ranges [(start, end), ...] or None; challenges = beta, gamma on the host; outs = the DeviceBuffers n_1..4, d_1..4
+    (m shares each), which are returned."""
+    ch = _u64(challenges)
+    assert len(shares) == 4 and len(public) == 8 and len(outs) == 8 and ch.size == 8
+    rg, nr = _honk_ranges(ranges)
+    _check(lib().csh_honk_perm_operands_dev(curve, C.c_uint32(protocol), C.c_uint32(party), _devptr_array(shares), _devptr_array(public),
+                                            C.c_size_t(n), C.c_size_t(domain_size), rg, C.c_size_t(nr), _p(ch), _devptr_array(outs),
+                                            _stream(stream)))
+    return outs
+
+
+def honk_z_perm_place(curve: int, protocol: int, party: int, mul, z, n: int, domain_size: int, ranges, stream=None):
+    """csh_honk_z_perm_place_dev: mul (m shares) -> every element of z (n shares), which is returned; ranges as honk_perm_operands."""
+    rg, nr = _honk_ranges(ranges)
+    _check(lib().csh_honk_z_perm_place_dev(curve, C.c_uint32(protocol), C.c_uint32(party), _devptr(mul), _devptr(z), C.c_size_t(n),
+                                           C.c_size_t(domain_size), rg, C.c_size_t(nr), _stream(stream)))
+    return z
+
+
 def rep3_local_mul_vec(curve: int, lhs_ab, rhs_ab, mask=None):
     l, r = _u64(lhs_ab), _u64(rhs_ab)
     n = l.size // 8

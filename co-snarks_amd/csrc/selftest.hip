@@ -14,6 +14,7 @@
 #include "field29.hpp"
 #include "field_scan.hpp"
 #include "fr_entry.hpp"
+#include "honk_oink.hpp"
 #include "mle_fold.hpp"
 #include "msm_digits.hpp"
 #include "plonk_quot.hpp"
@@ -641,6 +642,73 @@ static int plonk_rounds_host_t(int entry, const uint64_t* aux, size_t n, uint32_
   return CSH_ERR_INVALID;
 }
 
+// Host run of the Oink stretches (honk_oink.hip) with the limb-bound checks on: the argument structs are filled in by the functions the
+// launchers use and every flat index goes through the ho_*_at() function its kernel calls -- on host arrays.
+//   entry 0 w4 records: in = w_l, w_r, w_o (n shares), type_share; idx = the read, write and shared lists, counts their lengths;
+//                       scalars = eta_1, eta_2, eta_3; out[0] = w_4, in place
+//   entry 1 lookup:     in = w_l, w_r, w_o, tags (n shares), then q_r, q_m, q_c, q_o, table_1..4, q_lookup (n elements); scalars = beta,
+//                       gamma; out = prod, sel
+//   entry 2 perm:       in = w_l, w_r, w_o, w_4 (n shares), then id_1..4, sigma_1..4; scalars = beta, gamma; out = n_1..4, d_1..4 (m shares)
+//   entry 3 place:      in[0] = mul (m shares); out[0] = z (n shares)
+template <class F>
+static int honk_oink_host_t(int entry, size_t n, size_t domain_size, uint32_t protocol, uint32_t party, const uint64_t* const* in,
+                            const uint32_t* const* idx, const size_t* counts, const size_t* ranges, size_t num_ranges, const uint64_t* scalars,
+                            uint64_t* const* out) {
+  const PqGeom rows{n, protocol + 1, pq_pub_comp(protocol, party)};
+  switch (entry) {
+    case 0: {
+      if (!idx || !counts || counts[0] + counts[1] + counts[2] > n) return CSH_ERR_INVALID;
+      HoW4Args<F> a;
+      for (int k = 0; k < 3; ++k) a.w[k] = (const F*)in[k];
+      a.w4 = (F*)out[0];
+      a.read_idx = idx[0], a.write_idx = idx[1], a.shared_idx = idx[2];
+      a.type_share = (const F*)in[3];
+      a.n = n, a.n_read = (uint32_t)counts[0], a.n_write = (uint32_t)counts[1], a.n_shared = (uint32_t)counts[2];
+      ho_w4_consts(a, scalars);
+      a.g = PqGeom{counts[0] + counts[1] + counts[2], rows.ncomp, rows.pub_comp};
+      for (size_t e = 0; e < a.g.values(); ++e) ho_w4_at(a, e);
+      return CSH_OK;
+    }
+    case 1: {
+      HoLookupArgs<F> a;
+      HoSelArgs<F> s;
+      a.g = s.g = rows;
+      for (int k = 0; k < 3; ++k) a.w[k] = (const F*)in[k], a.q[k] = (const F*)in[4 + k];
+      a.qo = (const F*)in[7];
+      for (int k = 0; k < 4; ++k) a.tab[k] = (const F*)in[8 + k];
+      a.prod = (F*)out[0];
+      ho_lookup_consts(a, scalars);
+      s.tag = (const F*)in[3], s.qlookup = (const F*)in[12], s.sel = (F*)out[1], s.one = F::one();
+      for (size_t e = 0; e < rows.values(); ++e) ho_lookup_prod_at(a, e);
+      for (size_t e = 0; e < rows.values(); ++e) ho_lookup_sel_at(s, e);
+      return CSH_OK;
+    }
+    case 2: {
+      HoPermArgs<F> a;
+      CSH_TRY(ho_ranges(a.R, ranges, num_ranges, n, domain_size, "selftest_honk_oink"));
+      a.g = PqGeom{(size_t)a.R.active - 1, rows.ncomp, rows.pub_comp};
+      for (int k = 0; k < 4; ++k) a.w[k] = (const F*)in[k];
+      a.betad = fr_to_rprime(fr_load<F>(scalars)), a.gamma = fr_load<F>(scalars + 4);
+      for (int half = 0; half < 2; ++half) {
+        for (int k = 0; k < 4; ++k) a.pub[k] = (const F*)in[4 + 4 * half + k], a.out[k] = (F*)out[4 * half + k];
+        for (size_t e = 0; e < a.g.values(); ++e) ho_perm_at(a, e);
+      }
+      return CSH_OK;
+    }
+    case 3: {
+      HoPlaceArgs<F> a;
+      CSH_TRY(ho_ranges(a.R, ranges, num_ranges, n, domain_size, "selftest_honk_oink"));
+      a.mul = (const F*)in[0], a.z = (F*)out[0];
+      a.one = F::one();
+      a.domain_size = (uint32_t)domain_size;
+      a.g = rows;
+      for (size_t e = 0; e < rows.values(); ++e) ho_place_at(a, e);
+      return CSH_OK;
+    }
+  }
+  return CSH_ERR_INVALID;
+}
+
 extern "C" {
 
 int csh_selftest_plonk_quot_host(int field_of, int stage, const uint64_t* gen, size_t N, uint32_t protocol, uint32_t party, const uint64_t* const* in,
@@ -653,6 +721,13 @@ int csh_selftest_plonk_rounds_host(int field_of, int entry, const uint64_t* aux,
                                    const uint64_t* const* in, const size_t* lens, const uint64_t* scalars, size_t ks, size_t kp, uint64_t* const* out) {
   if (!out || protocol > 1 || party > 2 || entry < 0 || entry > 3 || (entry == 0 && (!aux || n < 8 || (n & (n - 1))))) return CSH_ERR_INVALID;
   return FR_CALL(field_of, plonk_rounds_host_t<F>(entry, aux, n, protocol, party, in, lens, scalars, ks, kp, out));
+}
+
+int csh_selftest_honk_oink_host(int field_of, int entry, size_t n, size_t domain_size, uint32_t protocol, uint32_t party, const uint64_t* const* in,
+                                const uint32_t* const* idx, const size_t* counts, const size_t* ranges, size_t num_ranges, const uint64_t* scalars,
+                                uint64_t* const* out) {
+  if (!in || !out || protocol > 1 || party > 2 || entry < 0 || entry > 3 || (entry != 3 && !scalars) || n < 1 || n > FR_MAX_N) return CSH_ERR_INVALID;
+  return FR_CALL(field_of, honk_oink_host_t<F>(entry, n, domain_size, protocol, party, in, idx, counts, ranges, num_ranges, scalars, out));
 }
 
 int csh_selftest_mle_fold_host(int field_of, const uint64_t* in, size_t n, uint32_t ncomp, int tile_log, const uint64_t* u, size_t m,

@@ -650,6 +650,144 @@ inline std::vector<typename P::Fr> plain_compute_wxiw(const PlonkRound5Inputs<ty
 }
 }  // namespace detail
 
+// What the whole-trace loops of the Oink prover read (co-noir/co-ultrahonk/src/co_oink/co_oink_prover.rs:98-504; plain twin
+// co-noir/ultrahonk/src/oink/oink_prover.rs): of the proving key the witness and precomputed polynomials (circuit_size elements each;
+// w_4 may be shorter, :133-137 resize it), the memory-record rows, final_active_wire_idx and the active ranges (empty: none); of the
+// transcript eta_1..3, beta, gamma.
+template <class Fr>
+struct HonkOinkInputs {
+  size_t circuit_size = 0, final_active_wire_idx = 0;
+  std::vector<std::pair<size_t, size_t>> active_ranges;
+  std::vector<Fr> w_l, w_r, w_o, w_4, lookup_read_tags;
+  std::vector<Fr> q_r, q_m, q_c, q_o, table_1, table_2, table_3, table_4, q_lookup;
+  std::vector<Fr> id[4], sigma[4];
+  std::vector<uint32_t> memory_read_records, memory_write_records;
+  std::vector<std::pair<uint32_t, Fr>> memory_records_shared;  // (row, type share)
+  Fr eta_1, eta_2, eta_3, beta, gamma;
+};
+
+namespace detail {
+inline std::vector<size_t> honk_flat_ranges(const std::vector<std::pair<size_t, size_t>>& ranges) {
+  std::vector<size_t> flat;
+  for (const auto& r : ranges) flat.push_back(r.first), flat.push_back(r.second);
+  return flat;
+}
+// add_ram_rom_memory_records_to_wire_4 (co_oink_prover.rs:119-160) for the plain driver, device-resident from the upload to memory.w_4:
+// the clone + resize of :133-137 as csh_poly_lincomb_dev (one share term, coefficient one, out_len = n), then csh_honk_w4_records_dev.
+// The contract of that entry -- every row below n, no row twice -- is checked here, where the lists are uploaded.
+template <class P>
+inline std::vector<typename P::Fr> plain_compute_w4(const HonkOinkInputs<typename P::Fr>& in) {
+  using Fr = typename P::Fr;
+  const size_t n = in.circuit_size;
+  if (n == 0 || in.w_l.size() != n || in.w_r.size() != n || in.w_o.size() != n || in.w_4.size() > n) throw Error("compute_w4: w_l, w_r, w_o have circuit_size elements, w_4 at most");
+  std::vector<uint32_t> shared_rows;
+  std::vector<Fr> type_shares;
+  for (const auto& r : in.memory_records_shared) shared_rows.push_back(r.first), type_shares.push_back(r.second);
+  std::vector<bool> seen(n, false);
+  const std::vector<uint32_t>* lists[3] = {&in.memory_read_records, &in.memory_write_records, &shared_rows};
+  for (const auto* list : lists)
+    for (uint32_t row : *list) {
+      if (row >= n || seen[row]) throw Error("compute_w4: a memory record is outside the trace or occurs twice");
+      seen[row] = true;
+    }
+  DevicePool pool;
+  const uint64_t* w[3] = {pool.up(in.w_l), pool.up(in.w_r), pool.up(in.w_o)};
+  const uint64_t* src[1] = {pool.up(in.w_4)};
+  const size_t len = in.w_4.size();
+  const Fr one = Fr::one();
+  uint64_t* w4 = pool.fresh(sizeof(Fr) * n);
+  check(csh_poly_lincomb_dev(P::ID, 0, 0, src, &len, (const uint64_t*)&one, 1, nullptr, nullptr, nullptr, 0, nullptr, w4, n, nullptr), "csh_poly_lincomb_dev");
+  const Fr etas[3] = {in.eta_1, in.eta_2, in.eta_3};
+  check(csh_honk_w4_records_dev(P::ID, 0, 0, w, w4, n, (const uint64_t*)etas, (const uint32_t*)pool.up(in.memory_read_records), in.memory_read_records.size(),
+                                (const uint32_t*)pool.up(in.memory_write_records), in.memory_write_records.size(), (const uint32_t*)pool.up(shared_rows),
+                                pool.up(type_shares), shared_rows.size(), nullptr),
+        "csh_honk_w4_records_dev");
+  std::vector<Fr> out(n);
+  check(csh_memcpy_d2h(out.data(), w4, sizeof(Fr) * n), "csh_memcpy_d2h");
+  return out;
+}
+// compute_logderivative_inverses (co_oink_prover.rs:229-293) for the plain driver, device-resident from the upload to lookup_inverses:
+// csh_honk_lookup_operands_dev, the mul_many of :278 as csh_vec_mul_dev, batch_invert_leaking_zeros as csh_vec_batch_inverse_dev (a zero
+// stays zero). This is the co-prover's selector form, (1 - q_lookup) tag + q_lookup times the product; the plain prover
+// (oink_prover.rs) instead skips a row unless q_lookup or the tag is one, which is the same when both are 0 or 1.
+template <class P>
+inline std::vector<typename P::Fr> plain_compute_logderivative_inverses(const HonkOinkInputs<typename P::Fr>& in) {
+  using Fr = typename P::Fr;
+  const size_t n = in.circuit_size;
+  const std::vector<Fr>* shares[4] = {&in.w_l, &in.w_r, &in.w_o, &in.lookup_read_tags};
+  const std::vector<Fr>* publics[9] = {&in.q_r, &in.q_m, &in.q_c, &in.q_o, &in.table_1, &in.table_2, &in.table_3, &in.table_4, &in.q_lookup};
+  DevicePool pool;
+  const uint64_t *sp[4], *pp[9];
+  for (int j = 0; j < 4; ++j) {
+    if (n == 0 || shares[j]->size() != n) throw Error("compute_logderivative_inverses: every polynomial has circuit_size elements");
+    sp[j] = pool.up(*shares[j]);
+  }
+  for (int j = 0; j < 9; ++j) {
+    if (publics[j]->size() != n) throw Error("compute_logderivative_inverses: every polynomial has circuit_size elements");
+    pp[j] = pool.up(*publics[j]);
+  }
+  uint64_t* op[2] = {pool.fresh(sizeof(Fr) * n), pool.fresh(sizeof(Fr) * n)};
+  const Fr challenges[2] = {in.beta, in.gamma};
+  check(csh_honk_lookup_operands_dev(P::ID, 0, 0, sp, pp, n, (const uint64_t*)challenges, op, nullptr), "csh_honk_lookup_operands_dev");
+  uint64_t* inv = pool.fresh(sizeof(Fr) * n);
+  check(csh_vec_mul_dev(P::ID, op[0], op[1], inv, n, nullptr), "csh_vec_mul_dev");
+  check(csh_vec_batch_inverse_dev(P::ID, inv, inv, n, nullptr, nullptr), "csh_vec_batch_inverse_dev");
+  std::vector<Fr> out(n);
+  check(csh_memcpy_d2h(out.data(), inv, sizeof(Fr) * n), "csh_memcpy_d2h");
+  return out;
+}
+// compute_grand_product (co_oink_prover.rs:382-507) for the plain driver, device-resident from the upload to z_perm:
+// csh_honk_perm_operands_dev, the products of the four numerators and of the four denominators as csh_vec_mul_dev, their running
+// products (array_prod_mul: csh_vec_prefix_prod_dev), the denominators' inverses (batch_invert: csh_vec_batch_inverse_dev), the last
+// product and csh_honk_z_perm_place_dev. w_4 is memory.w_4, what compute_w4 returned.
+template <class P>
+inline std::vector<typename P::Fr> plain_compute_grand_product(const HonkOinkInputs<typename P::Fr>& in, const std::vector<typename P::Fr>& w_4) {
+  using Fr = typename P::Fr;
+  const size_t n = in.circuit_size, domain_size = in.final_active_wire_idx + 1;
+  const std::vector<Fr>* shares[4] = {&in.w_l, &in.w_r, &in.w_o, &w_4};
+  DevicePool pool;
+  const uint64_t *sp[4], *pp[8];
+  for (int j = 0; j < 4; ++j) {
+    if (n < 2 || shares[j]->size() != n || in.id[j].size() != n || in.sigma[j].size() != n) throw Error("compute_grand_product: every polynomial has circuit_size >= 2 elements");
+    sp[j] = pool.up(*shares[j]), pp[j] = pool.up(in.id[j]), pp[4 + j] = pool.up(in.sigma[j]);
+  }
+  const std::vector<size_t> ranges = honk_flat_ranges(in.active_ranges);
+  size_t active = domain_size;
+  if (!in.active_ranges.empty()) {
+    active = 0;
+    for (const auto& r : in.active_ranges) active += r.second > r.first ? r.second - r.first : 0;
+  }
+  if (active == 0 || active > n) throw Error("compute_grand_product: the active domain must have 1 .. circuit_size indices");
+  const size_t m = active - 1, mm = m ? m : 1;
+  uint64_t* op[8];
+  for (auto& o : op) o = pool.fresh(sizeof(Fr) * mm);
+  const Fr challenges[2] = {in.beta, in.gamma};
+  check(csh_honk_perm_operands_dev(P::ID, 0, 0, sp, pp, n, domain_size, ranges.data(), in.active_ranges.size(), (const uint64_t*)challenges, op, nullptr),
+        "csh_honk_perm_operands_dev");
+  auto mul = [&](const uint64_t* x, const uint64_t* y) {  // mul_many
+    uint64_t* o = pool.fresh(sizeof(Fr) * mm);
+    check(csh_vec_mul_dev(P::ID, x, y, o, m, nullptr), "csh_vec_mul_dev");
+    return o;
+  };
+  uint64_t *quot = nullptr, *zeros = pool.fresh(sizeof(uint64_t));
+  if (m) {  // a one-row active domain has no quotient: z_perm is zeros and the one
+    uint64_t *num = mul(mul(op[0], op[1]), mul(op[2], op[3])), *den = mul(mul(op[4], op[5]), mul(op[6], op[7]));
+    check(csh_vec_prefix_prod_dev(P::ID, num, num, m, nullptr), "csh_vec_prefix_prod_dev");
+    check(csh_vec_prefix_prod_dev(P::ID, den, den, m, nullptr), "csh_vec_prefix_prod_dev");
+    check(csh_vec_batch_inverse_dev(P::ID, den, den, m, zeros, nullptr), "csh_vec_batch_inverse_dev");
+    quot = mul(num, den);
+  }
+  uint64_t* z = pool.fresh(sizeof(Fr) * n);
+  check(csh_honk_z_perm_place_dev(P::ID, 0, 0, quot, z, n, domain_size, ranges.data(), in.active_ranges.size(), nullptr), "csh_honk_z_perm_place_dev");
+  std::vector<Fr> out(n);
+  uint64_t zero_count = 0;
+  check(csh_memcpy_d2h(out.data(), z, sizeof(Fr) * n), "csh_memcpy_d2h");
+  if (m) check(csh_memcpy_d2h(&zero_count, zeros, sizeof zero_count), "csh_memcpy_d2h");
+  if (zero_count) throw Error("Cannot invert zero");
+  return out;
+}
+}  // namespace detail
+
 // ---- plain drivers (co-plonk/src/mpc/plain.rs, co-noir-common/src/mpc/plain.rs) -----------------------------------
 template <class P>
 struct PlainPlonkDriver {
@@ -699,6 +837,13 @@ struct PlainPlonkDriver {
   static PlonkPolyEval<Fr> compute_z(const PlonkDomains<P>& domains, const PlonkRound2Inputs<Fr>& in) { return detail::plain_compute_z<P>(domains, in); }
   static std::vector<Fr> compute_r_wxi(const PlonkRound5Inputs<Fr>& in) { return detail::plain_compute_r_wxi<P>(in); }
   static std::vector<Fr> compute_wxiw(const PlonkRound5Inputs<Fr>& in) { return detail::plain_compute_wxiw<P>(in); }
+  // The Oink phase of UltraHonk (co-ultrahonk/src/co_oink/co_oink_prover.rs): add_ram_rom_memory_records_to_wire_4 (:119-160) -> memory.w_4;
+  // compute_logderivative_inverses (:229-293) -> lookup_inverses; compute_grand_product (:382-507) -> z_perm. Device-only chains of the
+  // csh_honk_* entries and the scans. The Rep3 and Shamir drivers have none here: their mul_many and array_prod_mul are the network's;
+  // the entries themselves take every share type
+  static std::vector<Fr> compute_w4(const HonkOinkInputs<Fr>& in) { return detail::plain_compute_w4<P>(in); }
+  static std::vector<Fr> compute_logderivative_inverses(const HonkOinkInputs<Fr>& in) { return detail::plain_compute_logderivative_inverses<P>(in); }
+  static std::vector<Fr> compute_grand_product(const HonkOinkInputs<Fr>& in, const std::vector<Fr>& w_4) { return detail::plain_compute_grand_product<P>(in, w_4); }
   // co-plonk plain.rs:127-140 / co-noir plain.rs:240-252: every element's own inverse() there
   static std::vector<Fr> inv_vec(std::vector<Fr> a) {
     if (detail::batch_inverse<P>(a)) throw Error("Cannot invert zero");

@@ -473,6 +473,61 @@ int csh_poly_lincomb_dev(csh_curve_t field_of, uint32_t protocol, uint32_t party
                          const uint64_t* public_coeffs /* host, kp elements */, size_t kp, const uint64_t* const0 /* host, may be NULL */,
                          uint64_t* out_dev, size_t out_len, void* stream);
 
+/* ---- co-noir UltraHonk, the Oink phase: w_4 memory records, lookup and z_perm operands, z_perm placement ----
+ * The four loops over the whole trace of co-noir/co-ultrahonk/src/co_oink/co_oink_prover.rs (plain twin:
+ * co-noir/ultrahonk/src/oink/oink_prover.rs) that sit between a commitment and csh_vec_mul_dev / csh_vec_prefix_prod_dev /
+ * csh_vec_batch_inverse_dev. Affine in the shares with public coefficients, so no network round. protocol, party_id and the
+ * add_with_public rule are those of the PLONK rounds 2 / 5 section above: protocol 0 = plain / Shamir (ncomp 1), 1 = Rep3 (ncomp 2,
+ * {a, b} interleaved); a public value ("x (+) v") goes to component a for protocol 0 and Rep3 party 0, to b for Rep3 party 1, nowhere
+ * for Rep3 party 2. Challenges are host pointers read during the call, arkworks-Montgomery. Stream-ordered: no host synchronisation.
+ * Outputs are canonical. CSH_ERR_INVALID before any device work: a NULL pointer where one is required, a protocol outside 0..1 or a
+ * party outside 0..2, a size outside the stated range, malformed ranges, and any output range that overlaps an input range or another
+ * output of the same call.
+ * Active ranges (entries 3 and 4): `ranges` is a host array of 2 num_ranges values [start_j, end_j), num_ranges <= 32 (one per
+ * non-empty trace block, co-builder/src/keys/plain_proving_key.rs:137-142); every range is non-empty, start_j >= end_(j-1), end <= n.
+ * A = sum (end_j - start_j) and idx(t) is the t-th index of the concatenated ranges (ActiveRegionData::get_idx); with num_ranges = 0,
+ * idx(t) = t and A = domain_size (= final_active_wire_idx + 1). m = A - 1. The kernels derive idx from the ranges, which travel as kernel
+ * arguments with their prefix counts: no index list is uploaded or read. */
+/* add_ram_rom_memory_records_to_wire_4 + compute_w4_inner, co_oink_prover.rs:98-160. w_dev[0..3) = w_l, w_r, w_o (n shares), w4_dev (n
+ * shares) in place, etas = eta_1, eta_2, eta_3. The index lists are uint32_t arrays on the device (proving-key data, uploaded once). For
+ * a read record r: w4[r] += eta_1 w_l[r] + eta_2 w_r[r] + eta_3 w_o[r]; for a write record the same, then (+) 1; for shared record j the
+ * same, then + type_share[j] (n_shared shares). One launch covers all n_read + n_write + n_shared records; with all three counts zero the
+ * call does nothing. CONTRACT: every index is < n and no index occurs twice in the call, within a list or across lists -- a duplicate
+ * would be a race; whoever uploads the lists checks them. The reference's clone + resize of w_4 (:133-137) is csh_poly_lincomb_dev with
+ * one share term of coefficient one and out_len = n. */
+int csh_honk_w4_records_dev(csh_curve_t field_of, uint32_t protocol, uint32_t party_id, const uint64_t* const* w_dev /* 3 */, uint64_t* w4_dev,
+                            size_t n, const uint64_t* etas /* host, 3 elements */, const uint32_t* read_idx_dev, size_t n_read,
+                            const uint32_t* write_idx_dev, size_t n_write, const uint32_t* shared_idx_dev, const uint64_t* type_share_dev,
+                            size_t n_shared, void* stream);
+/* compute_logderivative_inverses + compute_lookup_term + compute_table_term, co_oink_prover.rs:162-293. shares_dev[0..4) = w_l, w_r, w_o,
+ * lookup_read_tags (n shares); public_dev[0..9) = q_r, q_m, q_c, q_o, table_1, table_2, table_3, table_4, q_lookup (n elements);
+ * challenges = beta, gamma (beta^2, beta^3 are derived here); out_dev[0..2) = prod, sel (n shares); 1 <= n <= 2^28. With sh(w)[i] = w[i + 1]
+ * and zero at the last row (Polynomial::shifted, co-noir-common/src/polynomials/polynomial.rs:170-176):
+ *   read[i]  = (w_l[i] + q_r[i] sh(w_l)[i]) (+) gamma + beta (w_r[i] + q_m[i] sh(w_r)[i]) + beta^2 (w_o[i] + q_c[i] sh(w_o)[i]) (+) beta^3 q_o[i]
+ *   write[i] = table_1[i] + gamma + beta table_2[i] + beta^2 table_3[i] + beta^3 table_4[i]            (public)
+ *   prod[i]  = write[i] read[i]                                                                     (mul_with_public)
+ *   sel[i]   = ((1 - q_lookup[i]) tag[i]) (+) q_lookup[i]
+ * The caller's mul_many(prod, sel) and batch_invert_leaking_zeros are csh_vec_mul_dev (or the Rep3 product) and
+ * csh_vec_batch_inverse_dev, which keeps a zero as zero. */
+int csh_honk_lookup_operands_dev(csh_curve_t field_of, uint32_t protocol, uint32_t party_id, const uint64_t* const* shares_dev /* 4 */,
+                                 const uint64_t* const* public_dev /* 9 */, size_t n, const uint64_t* challenges /* host, 2 elements */,
+                                 uint64_t* const* out_dev /* 2 */, void* stream);
+/* batched_grand_product_num_denom x 4, co_oink_prover.rs:344-451. shares_dev[0..4) = w_l, w_r, w_o, w_4 (n shares); public_dev[0..8) =
+ * id_1..id_4, sigma_1..sigma_4 (n elements); challenges = beta, gamma; out_dev[0..8) = n_1..n_4, d_1..d_4 (m shares each). For t < m and
+ * j = idx(t):  n_k[t] = w_k[j] (+) (beta id_k[j] + gamma),  d_k[t] = w_k[j] (+) (beta sigma_k[j] + gamma). 2 <= n <= 2^28,
+ * 1 <= domain_size <= n; m = 0 does nothing. */
+int csh_honk_perm_operands_dev(csh_curve_t field_of, uint32_t protocol, uint32_t party_id, const uint64_t* const* shares_dev /* 4 */,
+                               const uint64_t* const* public_dev /* 8 */, size_t n, size_t domain_size, const size_t* ranges /* host */,
+                               size_t num_ranges, const uint64_t* challenges /* host, 2 elements */, uint64_t* const* out_dev /* 8 */,
+                               void* stream);
+/* The tail of compute_grand_product, co_oink_prover.rs:472-504: mul_dev (m shares, the quotients numerator / denominator) -> z_dev (n
+ * shares, every element written; it need not be initialised and may not overlap mul_dev). The result is what the reference leaves: zeros;
+ * z[1] = the trivial share of one (0 (+) 1); then z[idx(t + 1)] = mul[t] for t < m, which overwrites z[1] when idx(t + 1) = 1; then, with
+ * ranges, z[i] = z[start_(r+1)] for i < domain_size inside a gap [end_r, start_(r+1)). Computed as a gather: each element is written by
+ * one lane. 2 <= n <= 2^28, 1 <= domain_size <= n; mul_dev may be NULL when m = 0. */
+int csh_honk_z_perm_place_dev(csh_curve_t field_of, uint32_t protocol, uint32_t party_id, const uint64_t* mul_dev, uint64_t* z_dev, size_t n,
+                              size_t domain_size, const size_t* ranges /* host */, size_t num_ranges, void* stream);
+
 /* Rep3 correlated masks generated on the device ("next" row f2): out[i] = from_be_bytes_mod_order(a_i) -
  * from_be_bytes_mod_order(b_i), a_i / b_i = the 32-byte chunks number elem_offset{1,2} + i of the ChaCha12 keystreams
  * of seed1 (own key) and seed2 (previous party's key): byte-compatible with Rep3Rand::masking_field_elements_vec

@@ -10,5 +10,7 @@
 mod cold;
 pub mod drivers;
 pub use drivers::{hip_fast_msm, HipPlainUltraHonkDriver, HipRep3UltraHonkDriver, HipShamirUltraHonkDriver};
+pub mod oink;
+pub use oink::{hip_lookup_operands, hip_perm_operands, hip_w4_records, hip_z_perm_place, DevMemoryRecords};
 pub mod scans;
 pub use scans::{hip_batch_inverse, hip_batched_polys_dev, hip_eval_poly, hip_prefix_product, hip_factor_roots};
