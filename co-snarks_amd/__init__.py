@@ -34,6 +34,8 @@ from .bindings import (  # noqa: F401
     HonkMemoryRecords,
     honk_lookup_operands,
     honk_perm_operands,
+    honk_pow_table,
+    honk_sumcheck_accumulate,
     honk_w4_records,
     honk_z_perm_place,
     lib,

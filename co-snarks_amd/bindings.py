@@ -679,6 +679,43 @@ def honk_z_perm_place(curve: int, protocol: int, party: int, mul, z, n: int, dom
     return z
 
 
+HONK_SUMCHECK_COLUMNS = 36        # witness (8), shifted witness (5), precomputed (23): the order of include/cosnarks_hip.h
+HONK_SUMCHECK_ACC_ELEMS = 57      # 6 + 5 + 6 + 3 + 5 + 5 + 3 + 6 + 6 + 6 + 6
+HONK_MAX_EDGE_END = 1 << 28
+
+
+def honk_sumcheck_accumulate(curve: int, cols, edge_begin: int, edge_end: int, params, acc=None, scaling=None, scaling_stride: int = 1, stream=None):
+    """csh_honk_sumcheck_accumulate_dev: cols = the 36 DeviceBuffers (or device addresses) in the header's order; elements
+    [edge_begin, edge_end) of each are read; params = beta, gamma, public_input_delta on the host; scaling = the DeviceBuffer of the
+    gate-separator products (honk_pow_table) read at (e >> 1) * scaling_stride, or None for the factor one. acc (57 elements, made here
+    unless given) is returned. The column count and the range rules are checked here, before the call."""
+    if len(cols) != HONK_SUMCHECK_COLUMNS:
+        raise CoSnarksHipError("honk_sumcheck_accumulate: %d columns, not %d" % (len(cols), HONK_SUMCHECK_COLUMNS))
+    if edge_begin < 0 or edge_begin % 2 or edge_end % 2 or not edge_begin < edge_end <= HONK_MAX_EDGE_END:
+        raise CoSnarksHipError("honk_sumcheck_accumulate: edge_begin and edge_end must be even, edge_begin < edge_end <= 2^28")
+    if scaling is not None and not 1 <= scaling_stride <= HONK_MAX_EDGE_END:
+        raise CoSnarksHipError("honk_sumcheck_accumulate: scaling_stride must be 1 .. 2^28")
+    pr = _u64(params)
+    assert pr.size == 12
+    if acc is None:
+        acc = DeviceBuffer(32 * HONK_SUMCHECK_ACC_ELEMS)
+    _check(lib().csh_honk_sumcheck_accumulate_dev(curve, _devptr_array(cols), C.c_size_t(edge_begin), C.c_size_t(edge_end), _devptr(scaling),
+                                                  C.c_size_t(scaling_stride), _p(pr), _devptr(acc), _stream(stream)))
+    return acc
+
+
+def honk_pow_table(curve: int, betas, out=None, stream=None):
+    """csh_honk_pow_table_dev: betas = m host elements, 0 <= m <= 28 -> the DeviceBuffer of the 2^m products (made here unless given)."""
+    b = _u64(betas) if betas is not None and len(betas) else None
+    m = 0 if b is None else b.size // 4
+    if (b is not None and b.size != 4 * m) or m > 28:
+        raise CoSnarksHipError("honk_pow_table: m must be 0 .. 28 elements of 4 words")
+    if out is None:
+        out = DeviceBuffer(32 << m)
+    _check(lib().csh_honk_pow_table_dev(curve, _p(b), C.c_size_t(m), _devptr(out), _stream(stream)))
+    return out
+
+
 def rep3_local_mul_vec(curve: int, lhs_ab, rhs_ab, mask=None):
     l, r = _u64(lhs_ab), _u64(rhs_ab)
     n = l.size // 8

@@ -15,6 +15,7 @@
 #include "field_scan.hpp"
 #include "fr_entry.hpp"
 #include "honk_oink.hpp"
+#include "honk_relations.hpp"
 #include "mle_fold.hpp"
 #include "msm_digits.hpp"
 #include "plonk_quot.hpp"
@@ -709,6 +710,39 @@ static int honk_oink_host_t(int entry, size_t n, size_t domain_size, uint32_t pr
   return CSH_ERR_INVALID;
 }
 
+// Host run of the sumcheck round (honk_relations.hip) with the limb-bound checks on: the argument struct is filled in by the function the
+// launcher uses, and for each of the six points one set of eleven running sums takes every edge of the range through
+// hr_accumulate_edge(), the function a lane of k_hr_accumulate calls -- one lane's grid-stride loop with as many passes as the range has
+// edges. acc = 57 elements, written as k_hr_finish writes them.
+template <class F>
+static int honk_relations_host_t(const uint64_t* const* cols, size_t edge_begin, size_t edge_end, const uint64_t* scaling, size_t scaling_stride,
+                                 const uint64_t* params, uint64_t* acc_out) {
+  using LZ = typename LazyOf<F>::type;
+  HrArgs<F> a;
+  for (int c = 0; c < HR_COLS; ++c) a.col[c] = (const F*)cols[c];
+  a.scaling = (const F*)scaling, a.scaling_stride = scaling_stride;
+  a.edge_begin = edge_begin, a.n_edges = (edge_end - edge_begin) / 2;
+  hr_consts(a, params);
+  for (int k = 0; k < HR_POINTS; ++k) {
+    LZ acc[HR_SUBRELATIONS];
+    for (int s = 0; s < HR_SUBRELATIONS; ++s) acc[s] = LZ::zero();
+    for (size_t j = 0; j < a.n_edges; ++j) hr_accumulate_edge<15>(a, j, k, acc);
+    for (int s = 0; s < HR_SUBRELATIONS; ++s)
+      if (k < hr_acc_len(s)) ((F*)acc_out)[hr_acc_off(s) + k] = acc[s].canonical_narrow().pack();
+  }
+  return CSH_OK;
+}
+template <class F>
+static int honk_pow_table_host_t(const uint64_t* betas, size_t m, uint64_t* out) {
+  HrPowArgs<F> a;
+  memset(&a, 0, sizeof a);
+  for (size_t b = 0; b < m; ++b) a.betad[b] = fr_to_rprime(fr_load<F>(betas + 4 * b));
+  a.one = F::one();
+  a.out = (F*)out, a.count = size_t(1) << m, a.m = (uint32_t)m;
+  for (size_t i = 0; i < a.count; ++i) a.out[i] = hr_pow_at(a, i);
+  return CSH_OK;
+}
+
 extern "C" {
 
 int csh_selftest_plonk_quot_host(int field_of, int stage, const uint64_t* gen, size_t N, uint32_t protocol, uint32_t party, const uint64_t* const* in,
@@ -728,6 +762,16 @@ int csh_selftest_honk_oink_host(int field_of, int entry, size_t n, size_t domain
                                 uint64_t* const* out) {
   if (!in || !out || protocol > 1 || party > 2 || entry < 0 || entry > 3 || (entry != 3 && !scalars) || n < 1 || n > FR_MAX_N) return CSH_ERR_INVALID;
   return FR_CALL(field_of, honk_oink_host_t<F>(entry, n, domain_size, protocol, party, in, idx, counts, ranges, num_ranges, scalars, out));
+}
+
+int csh_selftest_honk_relations_host(int field_of, const uint64_t* const* cols, size_t edge_begin, size_t edge_end, const uint64_t* scaling,
+                                     size_t scaling_stride, const uint64_t* params, uint64_t* acc_out) {
+  if (!cols || !params || !acc_out || (edge_begin & 1) || (edge_end & 1) || edge_begin >= edge_end || (scaling && !scaling_stride)) return CSH_ERR_INVALID;
+  return FR_CALL(field_of, honk_relations_host_t<F>(cols, edge_begin, edge_end, scaling, scaling_stride, params, acc_out));
+}
+int csh_selftest_honk_pow_table_host(int field_of, const uint64_t* betas, size_t m, uint64_t* out) {
+  if (!out || (m && !betas) || m > 20) return CSH_ERR_INVALID;
+  return FR_CALL(field_of, honk_pow_table_host_t<F>(betas, m, out));
 }
 
 int csh_selftest_mle_fold_host(int field_of, const uint64_t* in, size_t n, uint32_t ncomp, int tile_log, const uint64_t* u, size_t m,

@@ -788,6 +788,192 @@ inline std::vector<typename P::Fr> plain_compute_grand_product(const HonkOinkInp
 }
 }  // namespace detail
 
+// What a sumcheck round of the plain UltraHonk prover reads between two folds (co-noir/ultrahonk/src/decider/sumcheck/
+// sumcheck_round_prover.rs:224-255): the 36 columns of subrelations 0 .. 10 in the order of csh_honk_sumcheck_accumulate_dev (witness
+// w_l, w_r, w_o, w_4, z_perm, lookup_inverses, lookup_read_counts, lookup_read_tags; shifted w_l, w_r, w_o, w_4, z_perm; precomputed q_m,
+// q_c, q_l, q_r, q_o, q_4, q_arith, q_delta_range, q_lookup, sigma_1..4, id_1..4, table_1..4, lagrange_first, lagrange_last), the relation
+// parameters, and the state of GateSeparatorPolynomial (decider/types.rs:44-112).
+constexpr size_t HONK_SUMCHECK_COLUMNS = 36, HONK_ACC_ELEMS = 57, HONK_SUBRELATIONS = 11, HONK_BATCHED_RELATION_PARTIAL_LENGTH = 8;
+constexpr size_t HONK_ACC_LENGTHS[HONK_SUBRELATIONS] = {6, 5, 6, 3, 5, 5, 3, 6, 6, 6, 6};
+template <class Fr>
+struct HonkRelationParameters {
+  Fr beta, gamma, public_input_delta;
+};
+template <class Fr>
+struct HonkGateSeparator {
+  std::vector<Fr> betas;
+  size_t log_num_monomials = 0;  // beta_products has 2^log_num_monomials elements
+  Fr partial_evaluation_result = Fr::one();
+  size_t current_element_idx = 0, periodicity = 2;
+  void partially_evaluate(const Fr& u) {  // types.rs:96-102
+    partial_evaluation_result = Fr::mul(partial_evaluation_result, Fr::add(Fr::one(), Fr::mul(u, Fr::sub(betas[current_element_idx], Fr::one()))));
+    ++current_element_idx;
+    periodicity *= 2;
+  }
+};
+template <class Fr>
+using HonkAccumulators = std::array<Fr, HONK_ACC_ELEMS>;  // the eleven accumulators back to back, HONK_ACC_LENGTHS
+
+namespace detail {
+template <class Fr>
+inline void honk_check_round(const std::vector<std::vector<Fr>>& cols, size_t edge_begin, size_t edge_end, const HonkGateSeparator<Fr>* gs) {
+  if (cols.size() != HONK_SUMCHECK_COLUMNS) throw Error("compute_round_accumulators: 36 columns");
+  if ((edge_begin & 1) || (edge_end & 1) || edge_begin >= edge_end) throw Error("compute_round_accumulators: an even, non-empty range");
+  for (const auto& c : cols)
+    if (c.size() < edge_end) throw Error("compute_round_accumulators: a column is shorter than the range");
+  if (gs && (gs->log_num_monomials > 28 || gs->betas.size() < gs->log_num_monomials || ((edge_end >> 1) - 1) * gs->periodicity >= (size_t(1) << gs->log_num_monomials)))
+    throw Error("compute_round_accumulators: the gate separator's table is shorter than the range reads");
+}
+// The loop of compute_univariate_inner (:239-252) on the device: the columns go up, beta_products is made there
+// (csh_honk_pow_table_dev), csh_honk_sumcheck_accumulate_dev, 57 elements come back. gs == nullptr: the factor one
+// (compute_virtual_contribution, :388-421).
+template <class P>
+inline HonkAccumulators<typename P::Fr> plain_round_accumulators(const std::vector<std::vector<typename P::Fr>>& cols, size_t edge_begin, size_t edge_end,
+                                                                 const HonkGateSeparator<typename P::Fr>* gs, const HonkRelationParameters<typename P::Fr>& params) {
+  using Fr = typename P::Fr;
+  honk_check_round(cols, edge_begin, edge_end, gs);
+  DevicePool pool;
+  const uint64_t* dc[HONK_SUMCHECK_COLUMNS];
+  for (size_t c = 0; c < HONK_SUMCHECK_COLUMNS; ++c) dc[c] = pool.up(cols[c]);
+  uint64_t* table = nullptr;
+  if (gs) {
+    table = pool.fresh(sizeof(Fr) << gs->log_num_monomials);
+    check(csh_honk_pow_table_dev(P::ID, (const uint64_t*)gs->betas.data(), gs->log_num_monomials, table, nullptr), "csh_honk_pow_table_dev");
+  }
+  uint64_t* acc = pool.fresh(sizeof(Fr) * HONK_ACC_ELEMS);
+  const Fr pr[3] = {params.beta, params.gamma, params.public_input_delta};
+  check(csh_honk_sumcheck_accumulate_dev(P::ID, dc, edge_begin, edge_end, table, gs ? gs->periodicity : 1, (const uint64_t*)pr, acc, nullptr),
+        "csh_honk_sumcheck_accumulate_dev");
+  HonkAccumulators<Fr> out;
+  check(csh_memcpy_d2h(out.data(), acc, sizeof(Fr) * HONK_ACC_ELEMS), "csh_memcpy_d2h");
+  return out;
+}
+template <class Fr>
+inline std::vector<Fr> honk_beta_products(const std::vector<Fr>& betas, size_t log_num_monomials) {  // types.rs:53-67
+  std::vector<Fr> out(size_t(1) << log_num_monomials, Fr::one());
+  for (size_t i = 0; i < log_num_monomials; ++i) {
+    const size_t index = size_t(1) << i;
+    out[index] = betas[i];
+    for (size_t j = 1; j < index; ++j) out[index + j] = Fr::mul(out[j], betas[i]);
+  }
+  return out;
+}
+// The same loop in plain C++ on one host thread, the relations in the scalar shape of verify_accumulate at each of the points 0 .. 5: what
+// the mirror test holds the device against, and the host column of tools/honk_relations_probe.py.
+template <class Fr>
+inline HonkAccumulators<Fr> host_round_accumulators(const std::vector<std::vector<Fr>>& cols, size_t edge_begin, size_t edge_end, const HonkGateSeparator<Fr>* gs,
+                                                    const HonkRelationParameters<Fr>& params) {
+  honk_check_round(cols, edge_begin, edge_end, gs);
+  const std::vector<Fr> table = gs ? honk_beta_products(gs->betas, gs->log_num_monomials) : std::vector<Fr>();
+  const Fr one = Fr::one(), two = Fr::add(one, one), three = Fr::add(two, one), neg_half = Fr::sub(Fr::zero(), Fr::inv(two));
+  const Fr beta = params.beta, gamma = params.gamma;
+  Fr acc[HONK_SUBRELATIONS][6];
+  for (auto& a : acc)
+    for (auto& x : a) x = Fr::zero();
+  auto both_zero = [&](size_t c, size_t e) { return cols[c][e].is_zero() && cols[c][e + 1].is_zero(); };
+  for (size_t e = edge_begin; e < edge_end; e += 2) {
+    const Fr sf = gs ? table[(e >> 1) * gs->periodicity] : one;
+    const bool do_arith = !both_zero(19, e), do_delta = !both_zero(20, e), do_lookup = !(both_zero(21, e) && both_zero(6, e));
+    const bool do_perm = !(cols[4][e] == cols[12][e] && cols[4][e + 1] == cols[12][e + 1]);
+    Fr v[HONK_SUMCHECK_COLUMNS], delta[HONK_SUMCHECK_COLUMNS];
+    for (size_t c = 0; c < HONK_SUMCHECK_COLUMNS; ++c) v[c] = cols[c][e], delta[c] = Fr::sub(cols[c][e + 1], cols[c][e]);
+    for (int k = 0; k < 6; ++k) {
+      if (k)
+        for (size_t c = 0; c < HONK_SUMCHECK_COLUMNS; ++c) v[c] = Fr::add(v[c], delta[c]);  // extend_from of two points
+      auto add = [&](int s, const Fr& x) { acc[s][k] = Fr::add(acc[s][k], x); };
+      const Fr &w_l = v[0], &w_r = v[1], &w_o = v[2], &w_4 = v[3], &z = v[4], &inv = v[5], &counts = v[6], &tag = v[7];
+      const Fr &w_ls = v[8], &w_rs = v[9], &w_os = v[10], &w_4s = v[11], &zs = v[12];
+      const Fr &q_m = v[13], &q_c = v[14], &q_l = v[15], &q_r = v[16], &q_o = v[17], &q_4 = v[18], &qa = v[19], &q_delta = v[20], &q_lookup = v[21];
+      if (do_arith) {
+        Fr t = Fr::mul(Fr::mul(Fr::sub(qa, three), Fr::mul(Fr::mul(q_m, w_r), w_l)), neg_half);
+        t = Fr::add(t, Fr::add(Fr::add(Fr::mul(q_l, w_l), Fr::mul(q_r, w_r)), Fr::add(Fr::mul(q_o, w_o), Fr::add(Fr::mul(q_4, w_4), q_c))));
+        t = Fr::add(t, Fr::mul(Fr::sub(qa, one), w_4s));
+        add(0, Fr::mul(Fr::mul(t, qa), sf));
+        Fr u = Fr::add(Fr::sub(Fr::add(w_l, w_4), w_ls), q_m);
+        u = Fr::mul(Fr::mul(Fr::mul(u, Fr::sub(qa, two)), Fr::sub(qa, one)), qa);
+        add(1, Fr::mul(u, sf));
+      }
+      if (do_perm) {
+        Fr num = sf, den = sf;
+        for (int j = 0; j < 4; ++j) {
+          const Fr wg = Fr::add(v[j], gamma);
+          num = Fr::mul(num, Fr::add(Fr::mul(v[26 + j], beta), wg));
+          den = Fr::mul(den, Fr::add(Fr::mul(v[22 + j], beta), wg));
+        }
+        const Fr pit = Fr::add(Fr::mul(v[35], params.public_input_delta), zs);
+        add(2, Fr::sub(Fr::mul(Fr::add(z, v[34]), num), Fr::mul(pit, den)));
+        add(3, Fr::mul(Fr::mul(v[35], zs), sf));
+      }
+      if (do_lookup) {
+        const Fr b2 = Fr::mul(beta, beta), b3 = Fr::mul(b2, beta);
+        const Fr read = Fr::add(Fr::add(Fr::add(Fr::add(w_l, gamma), Fr::mul(q_r, w_ls)), Fr::mul(Fr::add(Fr::mul(q_m, w_rs), w_r), beta)),
+                                Fr::add(Fr::mul(Fr::add(Fr::mul(q_c, w_os), w_o), b2), Fr::mul(q_o, b3)));
+        const Fr write = Fr::add(Fr::add(Fr::add(v[30], gamma), Fr::mul(v[31], beta)), Fr::add(Fr::mul(v[32], b2), Fr::mul(v[33], b3)));
+        const Fr exists = Fr::sub(Fr::add(tag, q_lookup), Fr::mul(tag, q_lookup));
+        add(4, Fr::mul(Fr::sub(Fr::mul(Fr::mul(read, write), inv), exists), sf));
+        add(5, Fr::sub(Fr::mul(Fr::mul(write, inv), q_lookup), Fr::mul(Fr::mul(read, inv), counts)));
+        add(6, Fr::mul(Fr::sub(Fr::mul(tag, tag), tag), sf));
+      }
+      if (do_delta) {
+        const Fr* hi[4] = {&w_r, &w_o, &w_4, &w_ls};
+        const Fr* lo[4] = {&w_l, &w_r, &w_o, &w_4};
+        for (int j = 0; j < 4; ++j) {
+          const Fr d = Fr::sub(*hi[j], *lo[j]), a1 = Fr::sub(d, one), a2 = Fr::sub(d, two);
+          const Fr t = Fr::mul(Fr::sub(Fr::mul(a1, a1), one), Fr::sub(Fr::mul(a2, a2), one));
+          add(7 + j, Fr::mul(Fr::mul(t, q_delta), sf));
+        }
+      }
+    }
+  }
+  HonkAccumulators<Fr> out;
+  size_t at = 0;
+  for (size_t s = 0; s < HONK_SUBRELATIONS; ++s)
+    for (size_t i = 0; i < HONK_ACC_LENGTHS[s]; ++i) out[at++] = acc[s][i];
+  return out;
+}
+// Univariate::extend_from (univariate.rs:57-178) to `size` points: the polynomial of degree < len through the points 0 .. len - 1, which
+// is what each of the reference's four branches evaluates
+template <class Fr>
+inline std::vector<Fr> honk_extend_from(const Fr* poly, size_t len, size_t size) {
+  std::vector<Fr> out(poly, poly + len);
+  auto small = [](long x) { return x >= 0 ? Fr::from_u64((uint64_t)x) : Fr::sub(Fr::zero(), Fr::from_u64((uint64_t)-x)); };
+  for (size_t x = len; x < size; ++x) {
+    Fr total = Fr::zero();
+    for (size_t i = 0; i < len; ++i) {
+      Fr num = Fr::one(), den = Fr::one();
+      for (size_t j = 0; j < len; ++j)
+        if (j != i) num = Fr::mul(num, small((long)x - (long)j)), den = Fr::mul(den, small((long)i - (long)j));
+      total = Fr::add(total, Fr::mul(Fr::mul(poly[i], num), Fr::inv(den)));
+    }
+    out.push_back(total);
+  }
+  return out;
+}
+// batch_over_relations_univariates (:109-122) for subrelations 0 .. 10: scale by first_scalar = 1 and alphas[0..10), extend each
+// accumulator to BATCHED_RELATION_PARTIAL_LENGTH, multiply by the extended [1, beta_i] and by partial_evaluation_result -- except
+// lookup.r1, the linearly dependent subrelation -- and sum
+template <class Fr>
+inline std::array<Fr, HONK_BATCHED_RELATION_PARTIAL_LENGTH> honk_batch_over_relations(const HonkAccumulators<Fr>& acc, const std::vector<Fr>& alphas,
+                                                                                       const HonkGateSeparator<Fr>& gs) {
+  if (alphas.size() < HONK_SUBRELATIONS - 1 || gs.current_element_idx >= gs.betas.size()) throw Error("compute_univariate: ten alphas and a current gate challenge");
+  const Fr pow[2] = {Fr::one(), gs.betas[gs.current_element_idx]};
+  const std::vector<Fr> random = honk_extend_from(pow, 2, HONK_BATCHED_RELATION_PARTIAL_LENGTH);
+  std::array<Fr, HONK_BATCHED_RELATION_PARTIAL_LENGTH> result;
+  for (auto& x : result) x = Fr::zero();
+  size_t at = 0;
+  for (size_t s = 0; s < HONK_SUBRELATIONS; ++s) {
+    std::vector<Fr> scaled(acc.begin() + at, acc.begin() + at + HONK_ACC_LENGTHS[s]);
+    at += HONK_ACC_LENGTHS[s];
+    if (s)
+      for (auto& x : scaled) x = Fr::mul(x, alphas[s - 1]);
+    const std::vector<Fr> ext = honk_extend_from(scaled.data(), scaled.size(), HONK_BATCHED_RELATION_PARTIAL_LENGTH);
+    for (size_t i = 0; i < HONK_BATCHED_RELATION_PARTIAL_LENGTH; ++i)
+      result[i] = Fr::add(result[i], s == 5 ? ext[i] : Fr::mul(Fr::mul(ext[i], random[i]), gs.partial_evaluation_result));
+  }
+  return result;
+}
+}  // namespace detail
+
 // ---- plain drivers (co-plonk/src/mpc/plain.rs, co-noir-common/src/mpc/plain.rs) -----------------------------------
 template <class P>
 struct PlainPlonkDriver {
@@ -844,6 +1030,20 @@ struct PlainPlonkDriver {
   static std::vector<Fr> compute_w4(const HonkOinkInputs<Fr>& in) { return detail::plain_compute_w4<P>(in); }
   static std::vector<Fr> compute_logderivative_inverses(const HonkOinkInputs<Fr>& in) { return detail::plain_compute_logderivative_inverses<P>(in); }
   static std::vector<Fr> compute_grand_product(const HonkOinkInputs<Fr>& in, const std::vector<Fr>& w_4) { return detail::plain_compute_grand_product<P>(in, w_4); }
+  // The sumcheck round of UltraHonk between two folds (ultrahonk/src/decider/sumcheck/sumcheck_round_prover.rs): the loop of
+  // compute_univariate_inner (:239-252) for subrelations 0 .. 10 over the edges [edge_begin, edge_end) on the device
+  // (csh_honk_pow_table_dev, csh_honk_sumcheck_accumulate_dev) -> the eleven accumulators; gate_separator == nullptr is the factor one of
+  // compute_virtual_contribution (:388-421). compute_univariate finishes on the host as batch_over_relations_univariates does (:109-122)
+  // -> the round univariate at the points 0 .. 7. The five remaining relations are the caller's.
+  static HonkAccumulators<Fr> compute_round_accumulators(const std::vector<std::vector<Fr>>& cols, size_t edge_begin, size_t edge_end,
+                                                         const HonkGateSeparator<Fr>* gate_separator, const HonkRelationParameters<Fr>& params) {
+    return detail::plain_round_accumulators<P>(cols, edge_begin, edge_end, gate_separator, params);
+  }
+  static std::array<Fr, HONK_BATCHED_RELATION_PARTIAL_LENGTH> compute_univariate(const std::vector<std::vector<Fr>>& cols, size_t round_size,
+                                                                                 const HonkGateSeparator<Fr>& gate_separator,
+                                                                                 const HonkRelationParameters<Fr>& params, const std::vector<Fr>& alphas) {
+    return detail::honk_batch_over_relations(compute_round_accumulators(cols, 0, round_size, &gate_separator, params), alphas, gate_separator);
+  }
   // co-plonk plain.rs:127-140 / co-noir plain.rs:240-252: every element's own inverse() there
   static std::vector<Fr> inv_vec(std::vector<Fr> a) {
     if (detail::batch_inverse<P>(a)) throw Error("Cannot invert zero");

@@ -528,6 +528,46 @@ int csh_honk_perm_operands_dev(csh_curve_t field_of, uint32_t protocol, uint32_t
 int csh_honk_z_perm_place_dev(csh_curve_t field_of, uint32_t protocol, uint32_t party_id, const uint64_t* mul_dev, uint64_t* z_dev, size_t n,
                               size_t domain_size, const size_t* ranges /* host */, size_t num_ranges, void* stream);
 
+/* ---- co-noir UltraHonk, the sumcheck round: relation accumulators over the edges, the gate-separator table ----
+ * What sits between two csh_mle_fold_dev calls of a device-resident UltraHonk prover (plain field: the `ultrahonk` crate's prover and
+ * PlainUltraHonkDriver). Elements are arkworks-Montgomery, 4 words each, one component. Scalars are host pointers read during the call.
+ * Stream-ordered: no host synchronisation, scratch from the stream's workspace; the column pointers travel as kernel arguments, nothing
+ * is copied to the device for them. Outputs are canonical. CSH_ERR_INVALID before any device work: a NULL pointer where one is required,
+ * a field other than BN254 / BLS12-381 / BLS12-377 Fr, a range or size outside the stated rules, an output that overlaps an input. */
+/* The loop body of SumcheckProverRound::compute_univariate_inner, co-noir/ultrahonk/src/decider/sumcheck/sumcheck_round_prover.rs:224-255,
+ * for edge_idx in (edge_begin..edge_end).step_by(2), restricted to subrelations 0 .. 10 of the batching order (relations/mod.rs:134-145):
+ * UltraArithmeticRelation (ultra_arithmetic_relation.rs:126-175), UltraPermutationRelation (permutation_relation.rs:93-167),
+ * LogDerivLookupRelation (logderiv_lookup_relation.rs:77-183, :266-309), DeltaRangeConstraintRelation
+ * (delta_range_constraint_relation.rs:112-177). The elliptic, memory, non-native field and Poseidon2 relations, and the batching of the
+ * accumulators into the round univariate (:109-122), stay with the caller.
+ * cols_dev[0..36), in this order (part of the ABI):
+ *   witness (8)          w_l, w_r, w_o, w_4, z_perm, lookup_inverses, lookup_read_counts, lookup_read_tags
+ *   shifted witness (5)  w_l, w_r, w_o, w_4, z_perm  -- vectors of their own, as the reference folds them separately from round 1 on; in
+ *                        round 0 a caller may pass `ptr + 1 element` where the length allows
+ *   precomputed (23)     q_m, q_c, q_l, q_r, q_o, q_4, q_arith, q_delta_range, q_lookup, sigma_1..4, id_1..4, table_1..4, lagrange_first,
+ *                        lagrange_last
+ * edge_begin and edge_end are even, edge_begin < edge_end <= 2^28; elements [edge_begin, edge_end) of every column are read. The scaling
+ * factor of edge e is scaling_dev[(e >> 1) * scaling_stride] (1 <= scaling_stride <= 2^28), or one for every edge when scaling_dev is NULL.
+ * params = beta, gamma, public_input_delta. acc_dev[0..57) = the eleven accumulators back to back: arith.r0 (6), arith.r1 (5), perm.r0 (6),
+ * perm.r1 (3), lookup.r0 (5), lookup.r1 (5), lookup.r2 (3), delta.r0 .. r3 (6 each); entry i of an accumulator is its evaluation at the
+ * point i; every element is written. acc_dev may not overlap a column or the scaling elements that are read.
+ * Per edge: extend_from of the pair col[e], col[e + 1] gives v0 + k (v1 - v0) at the point k; the scaling factor multiplies every
+ * subrelation except lookup.r1 (the linearly dependent one); and the reference's skips are part of the result -- arith is left out when
+ * q_arith is zero at both ends, perm when z_perm == z_perm_shift at both ends, lookup when q_lookup and lookup_read_counts are zero at both
+ * ends, delta when q_delta_range is zero at both ends -- so the words are the reference's on data that does not satisfy the circuit too.
+ * The three callers of the reference: the round loop is [0, round_size) with scaling_dev = beta_products and scaling_stride = periodicity;
+ * compute_disabled_contribution (:340-386) is the last two or four elements; compute_virtual_contribution (:388-421) is [0, 2) with
+ * scaling_dev = NULL. */
+int csh_honk_sumcheck_accumulate_dev(csh_curve_t field_of, const uint64_t* const* cols_dev /* host array of 36 device ptrs */, size_t edge_begin,
+                                     size_t edge_end, const uint64_t* scaling_dev, size_t scaling_stride,
+                                     const uint64_t* params /* host, 3 elements */, uint64_t* acc_dev /* 57 elements */, void* stream);
+/* GateSeparatorPolynomial::new's beta_products, co-noir/ultrahonk/src/decider/types.rs:53-67: out[i] = the product of betas[b] over the
+ * set bits b of i, out[0] = 1; 0 <= m <= 28, out_dev holds 2^m elements. The scaling table of csh_honk_sumcheck_accumulate_dev, made where
+ * it is read. partially_evaluate and partially_evaluate_with_padding (:96-112) are a few scalar operations per round and stay with the
+ * caller. */
+int csh_honk_pow_table_dev(csh_curve_t field_of, const uint64_t* betas /* host, m elements */, size_t m, uint64_t* out_dev /* 2^m elements */,
+                           void* stream);
+
 /* Rep3 correlated masks generated on the device ("next" row f2): out[i] = from_be_bytes_mod_order(a_i) -
  * from_be_bytes_mod_order(b_i), a_i / b_i = the 32-byte chunks number elem_offset{1,2} + i of the ChaCha12 keystreams
  * of seed1 (own key) and seed2 (previous party's key): byte-compatible with Rep3Rand::masking_field_elements_vec
