@@ -36,6 +36,7 @@ from .bindings import (  # noqa: F401
     honk_perm_operands,
     honk_pow_table,
     honk_sumcheck_accumulate,
+    honk_sumcheck_accumulate_gates,
     honk_w4_records,
     honk_z_perm_place,
     lib,

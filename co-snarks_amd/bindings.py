@@ -704,6 +704,33 @@ def honk_sumcheck_accumulate(curve: int, cols, edge_begin: int, edge_end: int, p
     return acc
 
 
+HONK_GATES_COLUMNS = 19           # w (4), shifted w (4), q_m .. q_4 (6), the five gate selectors: the order of include/cosnarks_hip.h
+HONK_GATES_PARAMS = 8             # eta_1..3, curve_b, mat_internal_diag_m_1[0..4)
+HONK_GATES_ACC_ELEMS = 110        # 2 * 6 + 6 * 6 + 6 + 4 * 7 + 4 * 7
+
+
+def honk_sumcheck_accumulate_gates(curve: int, cols, edge_begin: int, edge_end: int, params, acc=None, scaling=None, scaling_stride: int = 1,
+                                   stream=None):
+    """csh_honk_sumcheck_accumulate_gates_dev: cols = the 19 DeviceBuffers (or device addresses) in the header's order; params = eta_1,
+    eta_2, eta_3, curve_b and the four internal diagonal values on the host (8 elements); range and scaling as honk_sumcheck_accumulate.
+    acc (110 elements, made here unless given) is returned. The column count, the parameter count and the range rules are checked here,
+    before the call."""
+    if len(cols) != HONK_GATES_COLUMNS:
+        raise CoSnarksHipError("honk_sumcheck_accumulate_gates: %d columns, not %d" % (len(cols), HONK_GATES_COLUMNS))
+    if edge_begin < 0 or edge_begin % 2 or edge_end % 2 or not edge_begin < edge_end <= HONK_MAX_EDGE_END:
+        raise CoSnarksHipError("honk_sumcheck_accumulate_gates: edge_begin and edge_end must be even, edge_begin < edge_end <= 2^28")
+    if scaling is not None and not 1 <= scaling_stride <= HONK_MAX_EDGE_END:
+        raise CoSnarksHipError("honk_sumcheck_accumulate_gates: scaling_stride must be 1 .. 2^28")
+    pr = _u64(params)
+    if pr.size != 4 * HONK_GATES_PARAMS:
+        raise CoSnarksHipError("honk_sumcheck_accumulate_gates: %d parameter words, not %d elements of 4" % (pr.size, HONK_GATES_PARAMS))
+    if acc is None:
+        acc = DeviceBuffer(32 * HONK_GATES_ACC_ELEMS)
+    _check(lib().csh_honk_sumcheck_accumulate_gates_dev(curve, _devptr_array(cols), C.c_size_t(edge_begin), C.c_size_t(edge_end), _devptr(scaling),
+                                                        C.c_size_t(scaling_stride), _p(pr), _devptr(acc), _stream(stream)))
+    return acc
+
+
 def honk_pow_table(curve: int, betas, out=None, stream=None):
     """csh_honk_pow_table_dev: betas = m host elements, 0 <= m <= 28 -> the DeviceBuffer of the 2^m products (made here unless given)."""
     b = _u64(betas) if betas is not None and len(betas) else None

@@ -16,6 +16,7 @@
 #include "fr_entry.hpp"
 #include "honk_oink.hpp"
 #include "honk_relations.hpp"
+#include "honk_gates.hpp"
 #include "mle_fold.hpp"
 #include "msm_digits.hpp"
 #include "plonk_quot.hpp"
@@ -732,6 +733,33 @@ static int honk_relations_host_t(const uint64_t* const* cols, size_t edge_begin,
   }
   return CSH_OK;
 }
+// Host run of the sumcheck round's other five relations (honk_gates.hip) with the limb-bound checks on: the argument struct is filled in by
+// the function the launcher uses, and for each group and each of its points one set of running sums takes every edge of the range through
+// hg_accumulate_edge(), the function a lane of k_hg_accumulate calls. acc = 110 elements, written where k_hg_finish writes them.
+template <int G, class F>
+static void honk_gates_group_host(const HgArgs<F>& a, F* acc_out) {
+  using LZ = typename LazyOf<F>::type;
+  using GR = HgGroup<G>;
+  for (int k = 0; k < GR::POINTS; ++k) {
+    LZ acc[GR::SUMS];
+    for (int s = 0; s < GR::SUMS; ++s) acc[s] = LZ::zero();
+    for (size_t j = 0; j < a.n_edges; ++j) hg_accumulate_edge<G>(a, j, k, acc);
+    for (int s = 0; s < GR::SUMS; ++s) acc_out[GR::off(s) + k] = acc[s].canonical_narrow().pack();
+  }
+}
+template <class F>
+static int honk_gates_host_t(const uint64_t* const* cols, size_t edge_begin, size_t edge_end, const uint64_t* scaling, size_t scaling_stride,
+                             const uint64_t* params, uint64_t* acc_out) {
+  HgArgs<F> a;
+  for (int c = 0; c < HG_COLS; ++c) a.col[c] = (const F*)cols[c];
+  a.scaling = (const F*)scaling, a.scaling_stride = scaling_stride;
+  a.edge_begin = edge_begin, a.n_edges = (edge_end - edge_begin) / 2;
+  hg_consts(a, params);
+  honk_gates_group_host<HG_EN>(a, (F*)acc_out);
+  honk_gates_group_host<HG_MEM>(a, (F*)acc_out);
+  honk_gates_group_host<HG_POS>(a, (F*)acc_out);
+  return CSH_OK;
+}
 template <class F>
 static int honk_pow_table_host_t(const uint64_t* betas, size_t m, uint64_t* out) {
   HrPowArgs<F> a;
@@ -768,6 +796,11 @@ int csh_selftest_honk_relations_host(int field_of, const uint64_t* const* cols, 
                                      size_t scaling_stride, const uint64_t* params, uint64_t* acc_out) {
   if (!cols || !params || !acc_out || (edge_begin & 1) || (edge_end & 1) || edge_begin >= edge_end || (scaling && !scaling_stride)) return CSH_ERR_INVALID;
   return FR_CALL(field_of, honk_relations_host_t<F>(cols, edge_begin, edge_end, scaling, scaling_stride, params, acc_out));
+}
+int csh_selftest_honk_gates_host(int field_of, const uint64_t* const* cols, size_t edge_begin, size_t edge_end, const uint64_t* scaling,
+                                 size_t scaling_stride, const uint64_t* params, uint64_t* acc_out) {
+  if (!cols || !params || !acc_out || (edge_begin & 1) || (edge_end & 1) || edge_begin >= edge_end || (scaling && !scaling_stride)) return CSH_ERR_INVALID;
+  return FR_CALL(field_of, honk_gates_host_t<F>(cols, edge_begin, edge_end, scaling, scaling_stride, params, acc_out));
 }
 int csh_selftest_honk_pow_table_host(int field_of, const uint64_t* betas, size_t m, uint64_t* out) {
   if (!out || (m && !betas) || m > 20) return CSH_ERR_INVALID;

@@ -814,6 +814,22 @@ struct HonkGateSeparator {
 template <class Fr>
 using HonkAccumulators = std::array<Fr, HONK_ACC_ELEMS>;  // the eleven accumulators back to back, HONK_ACC_LENGTHS
 
+// The other five relations of the round (elliptic, memory, non-native field, Poseidon2 external and internal: subrelations 11 .. 27 of
+// relations/mod.rs:134-145): the 19 columns in the order of csh_honk_sumcheck_accumulate_gates_dev (w_l, w_r, w_o, w_4; shifted w_l, w_r,
+// w_o, w_4; q_m, q_c, q_l, q_r, q_o, q_4; q_elliptic, q_memory, q_nnf, q_poseidon2_external, q_poseidon2_internal), their eight parameters
+// and their seventeen accumulators. With the first eleven these are the 28 of accumulate_relation_univariates
+// (sumcheck_round_prover.rs:160-222), batched with NUM_ALPHAS = 27 challenges.
+constexpr size_t HONK_GATES_COLUMNS = 19, HONK_GATES_ACC_ELEMS = 110, HONK_GATES_SUBRELATIONS = 17, HONK_NUM_ALPHAS = 27;
+constexpr size_t HONK_GATES_ACC_LENGTHS[HONK_GATES_SUBRELATIONS] = {6, 6, 6, 6, 6, 6, 6, 6, 6, 7, 7, 7, 7, 7, 7, 7, 7};
+template <class Fr>
+struct HonkGateParameters {
+  Fr eta_1, eta_2, eta_3;
+  Fr curve_b;                               // HonkCurve::get_curve_b of the embedded curve
+  std::array<Fr, 4> mat_internal_diag_m_1;  // of the Poseidon2 internal matrix
+};
+template <class Fr>
+using HonkGateAccumulators = std::array<Fr, HONK_GATES_ACC_ELEMS>;  // the seventeen accumulators back to back, HONK_GATES_ACC_LENGTHS
+
 namespace detail {
 template <class Fr>
 inline void honk_check_round(const std::vector<std::vector<Fr>>& cols, size_t edge_begin, size_t edge_end, const HonkGateSeparator<Fr>* gs) {
@@ -972,6 +988,168 @@ inline std::array<Fr, HONK_BATCHED_RELATION_PARTIAL_LENGTH> honk_batch_over_rela
   }
   return result;
 }
+template <class Fr>
+inline void honk_check_round_gates(const std::vector<std::vector<Fr>>& cols, size_t edge_begin, size_t edge_end, const HonkGateSeparator<Fr>* gs) {
+  if (cols.size() != HONK_GATES_COLUMNS) throw Error("compute_round_accumulators_gates: 19 columns");
+  if ((edge_begin & 1) || (edge_end & 1) || edge_begin >= edge_end) throw Error("compute_round_accumulators_gates: an even, non-empty range");
+  for (const auto& c : cols)
+    if (c.size() < edge_end) throw Error("compute_round_accumulators_gates: a column is shorter than the range");
+  if (gs && (gs->log_num_monomials > 28 || gs->betas.size() < gs->log_num_monomials || ((edge_end >> 1) - 1) * gs->periodicity >= (size_t(1) << gs->log_num_monomials)))
+    throw Error("compute_round_accumulators_gates: the gate separator's table is shorter than the range reads");
+}
+// The same loop for subrelations 11 .. 27 on the device: csh_honk_sumcheck_accumulate_gates_dev, 110 elements come back
+template <class P>
+inline HonkGateAccumulators<typename P::Fr> plain_round_accumulators_gates(const std::vector<std::vector<typename P::Fr>>& cols, size_t edge_begin, size_t edge_end,
+                                                                           const HonkGateSeparator<typename P::Fr>* gs,
+                                                                           const HonkGateParameters<typename P::Fr>& params) {
+  using Fr = typename P::Fr;
+  honk_check_round_gates(cols, edge_begin, edge_end, gs);
+  DevicePool pool;
+  const uint64_t* dc[HONK_GATES_COLUMNS];
+  for (size_t c = 0; c < HONK_GATES_COLUMNS; ++c) dc[c] = pool.up(cols[c]);
+  uint64_t* table = nullptr;
+  if (gs) {
+    table = pool.fresh(sizeof(Fr) << gs->log_num_monomials);
+    check(csh_honk_pow_table_dev(P::ID, (const uint64_t*)gs->betas.data(), gs->log_num_monomials, table, nullptr), "csh_honk_pow_table_dev");
+  }
+  uint64_t* acc = pool.fresh(sizeof(Fr) * HONK_GATES_ACC_ELEMS);
+  const Fr pr[8] = {params.eta_1, params.eta_2, params.eta_3, params.curve_b, params.mat_internal_diag_m_1[0], params.mat_internal_diag_m_1[1],
+                    params.mat_internal_diag_m_1[2], params.mat_internal_diag_m_1[3]};
+  check(csh_honk_sumcheck_accumulate_gates_dev(P::ID, dc, edge_begin, edge_end, table, gs ? gs->periodicity : 1, (const uint64_t*)pr, acc, nullptr),
+        "csh_honk_sumcheck_accumulate_gates_dev");
+  HonkGateAccumulators<Fr> out;
+  check(csh_memcpy_d2h(out.data(), acc, sizeof(Fr) * HONK_GATES_ACC_ELEMS), "csh_memcpy_d2h");
+  return out;
+}
+// The same loop in plain C++ on one host thread, the five relations in the scalar shape of each file's verify_accumulate at each of the
+// points 0 .. 6 (elliptic_relation.rs:163-240, memory_relation.rs:360-561, non_native_field_relation.rs:179-269,
+// poseidon2_external_relation.rs:207-281, poseidon2_internal_relation.rs:202-270): what the mirror test holds the device against, and
+// the host column of tools/honk_gates_probe.py
+template <class Fr>
+inline HonkGateAccumulators<Fr> host_round_accumulators_gates(const std::vector<std::vector<Fr>>& cols, size_t edge_begin, size_t edge_end,
+                                                              const HonkGateSeparator<Fr>* gs, const HonkGateParameters<Fr>& params) {
+  honk_check_round_gates(cols, edge_begin, edge_end, gs);
+  const std::vector<Fr> table = gs ? honk_beta_products(gs->betas, gs->log_num_monomials) : std::vector<Fr>();
+  auto mul = [](const Fr& x, const Fr& y) { return Fr::mul(x, y); };
+  auto add = [](const Fr& x, const Fr& y) { return Fr::add(x, y); };
+  auto sub = [](const Fr& x, const Fr& y) { return Fr::sub(x, y); };
+  auto pow5 = [&](const Fr& x) { const Fr x2 = mul(x, x); return mul(mul(x2, x2), x); };
+  const Fr one = Fr::one();
+  Fr limb_size = one, sublimb_shift = one;
+  for (int i = 0; i < 68; ++i) limb_size = add(limb_size, limb_size);
+  for (int i = 0; i < 14; ++i) sublimb_shift = add(sublimb_shift, sublimb_shift);
+  Fr acc[HONK_GATES_SUBRELATIONS][7];
+  for (auto& a : acc)
+    for (auto& x : a) x = Fr::zero();
+  auto both_zero = [&](size_t c, size_t e) { return cols[c][e].is_zero() && cols[c][e + 1].is_zero(); };
+  for (size_t e = edge_begin; e < edge_end; e += 2) {
+    const Fr sf = gs ? table[(e >> 1) * gs->periodicity] : one;
+    const bool do_elliptic = !both_zero(14, e), do_memory = !both_zero(15, e), do_nnf = !both_zero(16, e), do_ext = !both_zero(17, e), do_int = !both_zero(18, e);
+    if (!(do_elliptic || do_memory || do_nnf || do_ext || do_int)) continue;
+    Fr v[HONK_GATES_COLUMNS], delta[HONK_GATES_COLUMNS];
+    for (size_t c = 0; c < HONK_GATES_COLUMNS; ++c) v[c] = cols[c][e], delta[c] = sub(cols[c][e + 1], cols[c][e]);
+    for (int k = 0; k < 7; ++k) {
+      if (k)
+        for (size_t c = 0; c < HONK_GATES_COLUMNS; ++c) v[c] = add(v[c], delta[c]);  // extend_from of two points
+      auto put = [&](int s, const Fr& x) { acc[s][k] = add(acc[s][k], x); };
+      const Fr &w_1 = v[0], &w_2 = v[1], &w_3 = v[2], &w_4 = v[3], &w_1s = v[4], &w_2s = v[5], &w_3s = v[6], &w_4s = v[7];
+      const Fr &q_m = v[8], &q_c = v[9], &q_1 = v[10], &q_2 = v[11], &q_3 = v[12], &q_4 = v[13];
+      if (do_elliptic) {
+        const Fr &x_1 = w_2, &y_1 = w_3, &x_2 = w_1s, &y_2 = w_4s, &y_3 = w_3s, &x_3 = w_2s, &q_sign = q_1;
+        const Fr x_diff = sub(x_2, x_1), y1_sqr = mul(y_1, y_1), y1y2 = mul(mul(y_1, y_2), q_sign);
+        const Fr x_add = add(add(sub(sub(mul(add(add(x_3, x_2), x_1), mul(x_diff, x_diff)), mul(y_2, y_2)), y1_sqr), y1y2), y1y2);
+        const Fr qes = mul(v[14], sf), q_double = mul(qes, q_m), q_add = sub(qes, q_double);
+        const Fr y1_plus_y3 = add(y_1, y_3);
+        const Fr y_add = add(mul(y1_plus_y3, x_diff), mul(sub(x_3, x_1), sub(mul(y_2, q_sign), y_1)));
+        const Fr x1_mul_3 = add(add(x_1, x_1), x_1), x_pow_4_mul_3 = mul(sub(y1_sqr, params.curve_b), x1_mul_3);
+        const Fr y1_sqr_mul_2 = add(y1_sqr, y1_sqr), y1_sqr_mul_4 = add(y1_sqr_mul_2, y1_sqr_mul_2);
+        const Fr x_double = sub(mul(add(add(x_3, x_1), x_1), y1_sqr_mul_4), add(add(x_pow_4_mul_3, x_pow_4_mul_3), x_pow_4_mul_3));
+        const Fr y_double = sub(mul(mul(x1_mul_3, x_1), sub(x_1, x_3)), mul(add(y_1, y_1), y1_plus_y3));
+        put(0, add(mul(x_add, q_add), mul(x_double, q_double)));
+        put(1, add(mul(y_add, q_add), mul(y_double, q_double)));
+      }
+      if (do_memory) {
+        const Fr partial = add(add(add(mul(w_3, params.eta_3), mul(w_2, params.eta_2)), mul(w_1, params.eta_1)), q_c);
+        const Fr record = sub(partial, w_4);
+        const Fr neg_index_delta = sub(w_1, w_1s), index_delta_is_zero = add(neg_index_delta, one);
+        const Fr monotone = add(mul(neg_index_delta, neg_index_delta), neg_index_delta);
+        const Fr qms = mul(v[15], sf), q12 = mul(q_1, q_2), q12ms = mul(q12, qms), q3ms = mul(q_3, qms);
+        put(3, mul(mul(index_delta_is_zero, sub(w_4s, w_4)), q12ms));
+        put(4, mul(monotone, q12ms));
+        const Fr next = sub(add(add(mul(w_3s, params.eta_3), mul(w_2s, params.eta_2)), mul(w_1s, params.eta_1)), w_4s);
+        put(5, mul(mul(mul(index_delta_is_zero, sub(w_3s, w_3)), add(next, one)), q3ms));
+        put(6, mul(monotone, q3ms));
+        put(7, mul(add(mul(next, next), next), q3ms));
+        const Fr timestamp = sub(mul(index_delta_is_zero, sub(w_2s, w_2)), w_3);
+        Fr identity = add(add(mul(record, q12), mul(timestamp, mul(q_4, q_1))), mul(record, mul(q_m, q_1)));
+        identity = mul(identity, qms);  // memory_relation.rs:557; the RAM term below has the factor already
+        put(2, add(identity, mul(add(mul(record, record), record), q3ms)));
+      }
+      if (do_nnf) {
+        Fr lo = add(mul(w_1, w_2s), mul(w_1s, w_2));
+        Fr gate_2 = mul(sub(add(mul(w_1, w_4), mul(w_2, w_3)), w_3s), limb_size);
+        gate_2 = mul(add(sub(gate_2, w_4s), lo), q_4);
+        const Fr hi = add(mul(lo, limb_size), mul(w_1s, w_2s));
+        const Fr gate_1 = mul(sub(hi, add(w_3, w_4)), q_3);
+        const Fr gate_3 = mul(sub(add(hi, w_4), add(w_3s, w_4s)), q_m);
+        const Fr identity = mul(add(add(gate_1, gate_2), gate_3), q_2);
+        Fr la_1 = mul(w_2s, sublimb_shift), la_2 = mul(w_3s, sublimb_shift);
+        for (const Fr* t : {&w_1s, &w_3, &w_2}) la_1 = mul(add(la_1, *t), sublimb_shift);
+        for (const Fr* t : {&w_2s, &w_1s, &w_4}) la_2 = mul(add(la_2, *t), sublimb_shift);
+        la_1 = mul(sub(add(la_1, w_1), w_4), q_4);
+        la_2 = mul(sub(add(la_2, w_3), w_4s), q_m);
+        put(8, mul(mul(add(identity, mul(add(la_1, la_2), q_3)), v[16]), sf));
+      }
+      if (do_ext) {
+        const Fr u_1 = pow5(add(w_1, q_1)), u_2 = pow5(add(w_2, q_2)), u_3 = pow5(add(w_3, q_3)), u_4 = pow5(add(w_4, q_4));
+        const Fr t_0 = add(u_1, u_2), t_1 = add(u_3, u_4), t_2 = add(add(u_2, u_2), t_1), t_3 = add(add(u_4, u_4), t_0);
+        const Fr t_1x2 = add(t_1, t_1), t_0x2 = add(t_0, t_0);
+        const Fr v_4 = add(add(t_1x2, t_1x2), t_3), v_2 = add(add(t_0x2, t_0x2), t_2), v_1 = add(t_3, v_2), v_3 = add(t_2, v_4);
+        const Fr qs = mul(v[17], sf);
+        put(9, mul(sub(v_1, w_1s), qs)), put(10, mul(sub(v_2, w_2s), qs)), put(11, mul(sub(v_3, w_3s), qs)), put(12, mul(sub(v_4, w_4s), qs));
+      }
+      if (do_int) {
+        const Fr u[4] = {pow5(add(w_1, q_1)), w_2, w_3, w_4};
+        const Fr total = add(add(u[0], u[1]), add(u[2], u[3])), qs = mul(v[18], sf);
+        for (int i = 0; i < 4; ++i) put(13 + i, mul(sub(add(mul(u[i], params.mat_internal_diag_m_1[i]), total), v[4 + i]), qs));
+      }
+    }
+  }
+  HonkGateAccumulators<Fr> out;
+  size_t at = 0;
+  for (size_t s = 0; s < HONK_GATES_SUBRELATIONS; ++s)
+    for (size_t i = 0; i < HONK_GATES_ACC_LENGTHS[s]; ++i) out[at++] = acc[s][i];
+  return out;
+}
+// batch_over_relations_univariates (:109-122) over all 28 accumulators: AllRelationAcc::scale with first_scalar = 1 and alphas[0..27) in
+// the order arith, perm, lookup, delta, elliptic, memory, nnf, poseidon2 external, poseidon2 internal (relations/mod.rs:134-145), then
+// extend_and_batch_univariates (:147-198): every accumulator extended to BATCHED_RELATION_PARTIAL_LENGTH; all but lookup.r1 -- so all
+// seventeen of the second entry, linearly independent in each of the five files -- take the extended [1, beta_i] and
+// partial_evaluation_result
+template <class Fr>
+inline std::array<Fr, HONK_BATCHED_RELATION_PARTIAL_LENGTH> honk_batch_over_all_relations(const HonkAccumulators<Fr>& acc, const HonkGateAccumulators<Fr>& gates,
+                                                                                           const std::vector<Fr>& alphas, const HonkGateSeparator<Fr>& gs) {
+  if (alphas.size() < HONK_NUM_ALPHAS || gs.current_element_idx >= gs.betas.size()) throw Error("compute_univariate_all: 27 alphas and a current gate challenge");
+  const Fr pow[2] = {Fr::one(), gs.betas[gs.current_element_idx]};
+  const std::vector<Fr> random = honk_extend_from(pow, 2, HONK_BATCHED_RELATION_PARTIAL_LENGTH);
+  std::array<Fr, HONK_BATCHED_RELATION_PARTIAL_LENGTH> result;
+  for (auto& x : result) x = Fr::zero();
+  size_t at = 0;
+  for (size_t s = 0; s < HONK_SUBRELATIONS + HONK_GATES_SUBRELATIONS; ++s) {
+    const bool first = s < HONK_SUBRELATIONS;
+    const size_t len = first ? HONK_ACC_LENGTHS[s] : HONK_GATES_ACC_LENGTHS[s - HONK_SUBRELATIONS];
+    if (s == HONK_SUBRELATIONS) at = 0;
+    const Fr* from = first ? acc.data() + at : gates.data() + at;
+    std::vector<Fr> scaled(from, from + len);
+    at += len;
+    if (s)
+      for (auto& x : scaled) x = Fr::mul(x, alphas[s - 1]);
+    const std::vector<Fr> ext = honk_extend_from(scaled.data(), scaled.size(), HONK_BATCHED_RELATION_PARTIAL_LENGTH);
+    for (size_t i = 0; i < HONK_BATCHED_RELATION_PARTIAL_LENGTH; ++i)
+      result[i] = Fr::add(result[i], s == 5 ? ext[i] : Fr::mul(Fr::mul(ext[i], random[i]), gs.partial_evaluation_result));
+  }
+  return result;
+}
 }  // namespace detail
 
 // ---- plain drivers (co-plonk/src/mpc/plain.rs, co-noir-common/src/mpc/plain.rs) -----------------------------------
@@ -1034,7 +1212,7 @@ struct PlainPlonkDriver {
   // compute_univariate_inner (:239-252) for subrelations 0 .. 10 over the edges [edge_begin, edge_end) on the device
   // (csh_honk_pow_table_dev, csh_honk_sumcheck_accumulate_dev) -> the eleven accumulators; gate_separator == nullptr is the factor one of
   // compute_virtual_contribution (:388-421). compute_univariate finishes on the host as batch_over_relations_univariates does (:109-122)
-  // -> the round univariate at the points 0 .. 7. The five remaining relations are the caller's.
+  // -> the univariate of subrelations 0 .. 10 at the points 0 .. 7. The five remaining relations: compute_round_accumulators_gates below.
   static HonkAccumulators<Fr> compute_round_accumulators(const std::vector<std::vector<Fr>>& cols, size_t edge_begin, size_t edge_end,
                                                          const HonkGateSeparator<Fr>* gate_separator, const HonkRelationParameters<Fr>& params) {
     return detail::plain_round_accumulators<P>(cols, edge_begin, edge_end, gate_separator, params);
@@ -1043,6 +1221,20 @@ struct PlainPlonkDriver {
                                                                                  const HonkGateSeparator<Fr>& gate_separator,
                                                                                  const HonkRelationParameters<Fr>& params, const std::vector<Fr>& alphas) {
     return detail::honk_batch_over_relations(compute_round_accumulators(cols, 0, round_size, &gate_separator, params), alphas, gate_separator);
+  }
+  // The other five relations of the round, subrelations 11 .. 27 (elliptic, memory, non-native field, Poseidon2 external and internal),
+  // over the same range on the device (csh_honk_sumcheck_accumulate_gates_dev) -> the seventeen accumulators. compute_univariate_all is
+  // the reference's round univariate: both entries, then batch_over_relations_univariates over all 28 accumulators with 27 alphas.
+  static HonkGateAccumulators<Fr> compute_round_accumulators_gates(const std::vector<std::vector<Fr>>& gate_cols, size_t edge_begin, size_t edge_end,
+                                                                   const HonkGateSeparator<Fr>* gate_separator, const HonkGateParameters<Fr>& params) {
+    return detail::plain_round_accumulators_gates<P>(gate_cols, edge_begin, edge_end, gate_separator, params);
+  }
+  static std::array<Fr, HONK_BATCHED_RELATION_PARTIAL_LENGTH> compute_univariate_all(const std::vector<std::vector<Fr>>& cols, const std::vector<std::vector<Fr>>& gate_cols,
+                                                                                     size_t round_size, const HonkGateSeparator<Fr>& gate_separator,
+                                                                                     const HonkRelationParameters<Fr>& params, const HonkGateParameters<Fr>& gate_params,
+                                                                                     const std::vector<Fr>& alphas) {
+    return detail::honk_batch_over_all_relations(compute_round_accumulators(cols, 0, round_size, &gate_separator, params),
+                                                 compute_round_accumulators_gates(gate_cols, 0, round_size, &gate_separator, gate_params), alphas, gate_separator);
   }
   // co-plonk plain.rs:127-140 / co-noir plain.rs:240-252: every element's own inverse() there
   static std::vector<Fr> inv_vec(std::vector<Fr> a) {

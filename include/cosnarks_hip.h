@@ -538,8 +538,9 @@ int csh_honk_z_perm_place_dev(csh_curve_t field_of, uint32_t protocol, uint32_t 
  * for edge_idx in (edge_begin..edge_end).step_by(2), restricted to subrelations 0 .. 10 of the batching order (relations/mod.rs:134-145):
  * UltraArithmeticRelation (ultra_arithmetic_relation.rs:126-175), UltraPermutationRelation (permutation_relation.rs:93-167),
  * LogDerivLookupRelation (logderiv_lookup_relation.rs:77-183, :266-309), DeltaRangeConstraintRelation
- * (delta_range_constraint_relation.rs:112-177). The elliptic, memory, non-native field and Poseidon2 relations, and the batching of the
- * accumulators into the round univariate (:109-122), stay with the caller.
+ * (delta_range_constraint_relation.rs:112-177). The elliptic, memory, non-native field and Poseidon2 relations are
+ * csh_honk_sumcheck_accumulate_gates_dev below; the batching of the accumulators into the round univariate (:109-122) stays with the
+ * caller.
  * cols_dev[0..36), in this order (part of the ABI):
  *   witness (8)          w_l, w_r, w_o, w_4, z_perm, lookup_inverses, lookup_read_counts, lookup_read_tags
  *   shifted witness (5)  w_l, w_r, w_o, w_4, z_perm  -- vectors of their own, as the reference folds them separately from round 1 on; in
@@ -561,6 +562,30 @@ int csh_honk_z_perm_place_dev(csh_curve_t field_of, uint32_t protocol, uint32_t 
 int csh_honk_sumcheck_accumulate_dev(csh_curve_t field_of, const uint64_t* const* cols_dev /* host array of 36 device ptrs */, size_t edge_begin,
                                      size_t edge_end, const uint64_t* scaling_dev, size_t scaling_stride,
                                      const uint64_t* params /* host, 3 elements */, uint64_t* acc_dev /* 57 elements */, void* stream);
+/* The same loop body (sumcheck_round_prover.rs:224-255, and its callers :340-386 and :388-421) for subrelations 11 .. 27 of the batching
+ * order (relations/mod.rs:134-145): EllipticRelation (elliptic_relation.rs:81-161), MemoryRelation (memory_relation.rs:145-358),
+ * NonNativeFieldRelation (non_native_field_relation.rs:85-177), Poseidon2ExternalRelation (poseidon2_external_relation.rs:121-205) and
+ * Poseidon2InternalRelation (poseidon2_internal_relation.rs:118-200). With csh_honk_sumcheck_accumulate_dev these are the 28 accumulators
+ * of accumulate_relation_univariates (:160-222).
+ * cols_dev[0..19), in this order (part of the ABI):
+ *   witness (4)          w_l, w_r, w_o, w_4
+ *   shifted witness (4)  w_l, w_r, w_o, w_4
+ *   precomputed (6)      q_m, q_c, q_l, q_r, q_o, q_4
+ *   gate selectors (5)   q_elliptic, q_memory, q_nnf, q_poseidon2_external, q_poseidon2_internal
+ * The first fourteen are vectors a caller passes to csh_honk_sumcheck_accumulate_dev too. The range, scaling, stream, workspace and overlap
+ * rules are that entry's, and so are the three callers. params = eta_1, eta_2, eta_3, curve_b (the constant of the embedded curve
+ * y^2 = x^3 + curve_b; HonkCurve::get_curve_b), and the four mat_internal_diag_m_1 values of the Poseidon2 internal matrix: none is
+ * built into the library, which is generic over the field. acc_dev[0..110) = seventeen accumulators back to back: elliptic.r0, r1 (6
+ * each), memory.r0 .. r5 (6 each), nnf.r0 (6), poseidon2_external.r0 .. r3 (7 each), poseidon2_internal.r0 .. r3 (7 each); entry i of an
+ * accumulator is its evaluation at the point i; every element is written. The scaling factor multiplies every subrelation (all seventeen
+ * are linearly independent).
+ * Skips are per edge and part of the result: each relation is left out when its own selector -- q_elliptic, q_memory, q_nnf,
+ * q_poseidon2_external, q_poseidon2_internal -- is zero at both ends of the edge. Every one of these selectors multiplies its whole
+ * relation (in memory.r0 the RAM consistency term is added after the product by q_memory * scaling, memory_relation.rs:347-353, and has
+ * the factor already), so a skip omits zeros only and the words are the reference's on any data. */
+int csh_honk_sumcheck_accumulate_gates_dev(csh_curve_t field_of, const uint64_t* const* cols_dev /* host array of 19 device ptrs */,
+                                           size_t edge_begin, size_t edge_end, const uint64_t* scaling_dev, size_t scaling_stride,
+                                           const uint64_t* params /* host, 8 elements */, uint64_t* acc_dev /* 110 elements */, void* stream);
 /* GateSeparatorPolynomial::new's beta_products, co-noir/ultrahonk/src/decider/types.rs:53-67: out[i] = the product of betas[b] over the
  * set bits b of i, out[0] = 1; 0 <= m <= 28, out_dev holds 2^m elements. The scaling table of csh_honk_sumcheck_accumulate_dev, made where
  * it is read. partially_evaluate and partially_evaluate_with_padding (:96-112) are a few scalar operations per round and stay with the

@@ -13,6 +13,6 @@ pub use drivers::{hip_fast_msm, HipPlainUltraHonkDriver, HipRep3UltraHonkDriver,
 pub mod oink;
 pub use oink::{hip_lookup_operands, hip_perm_operands, hip_w4_records, hip_z_perm_place, DevMemoryRecords};
 pub mod sumcheck;
-pub use sumcheck::{hip_compute_univariate, hip_pow_table, UltraAccumulators};
+pub use sumcheck::{gate_params, hip_compute_univariate, hip_compute_univariate_all, hip_compute_univariate_gates, hip_pow_table, AllAccumulators, GateAccumulators, UltraAccumulators};
 pub mod scans;
 pub use scans::{hip_batch_inverse, hip_batched_polys_dev, hip_eval_poly, hip_prefix_product, hip_factor_roots};
