@@ -793,6 +793,47 @@ size_t msm_bucket_bytes(const MsmParams* pp) {
   return sizing.off;
 }
 
+// The views of one window group into the sort stage's outputs and the bucket stage's scratch, up to the per-bucket sums
+template <class Cfg>
+struct BucketSumViews {
+  const uint32_t *start, *nlanes, *sorted;
+  LazyPt<Cfg>*partial, *dense;
+  uint32_t *giant, *big;  // the group's giant queue ([0] = count, [1] = sliced, list from [2]) and its sliced buckets
+  LazyPt<Cfg>* gscratch;
+};
+// The launches of a bucket stage up to the per-bucket sums, for nw windows: the accumulation (pair: two lanes per point, the G2 groups
+// only), then k_msm_merge or, fused, k_msm_mark_giant (the reduction then folds a bucket's partial slots itself: qbucket_merged /
+// pbucket_merged), then the two launches of the oversized buckets. The one home of these launches: bucket_group runs them for the
+// product, msm_buckets_selftest_t for the device unit test of the stage. ev (nullable): records ev[4] after the accumulation.
+template <class Cfg>
+int bucket_sums_launch(const Affine<typename Cfg::Fq>* bases, const MsmParams& p, const BucketSumViews<Cfg>& v, uint32_t max_lanes, uint32_t giant_blocks, int nw,
+                       bool pair, bool fused, hipStream_t st, hipEvent_t* ev) {
+  {
+    const int tb = tune().acc_blk.load(std::memory_order_relaxed);
+    const int blk = (tb == 64 || tb == 128) ? tb : ACC_BLK;
+    if constexpr (Cfg::PAIR) {
+      if (pair) {
+        const dim3 ag((2 * max_lanes + blk - 1) / blk, nw), ab(blk);
+        hipLaunchKernelGGL(k_msm_accum_pair<Cfg>, ag, ab, 0, st, bases, p, v.start, v.nlanes, v.sorted, v.partial, v.giant);
+      }
+    }
+    if (!(Cfg::PAIR && pair)) {
+      const dim3 ag((max_lanes + blk - 1) / blk, nw), ab(blk);
+      hipLaunchKernelGGL(k_msm_accum<Cfg>, ag, ab, 0, st, bases, p, v.start, v.nlanes, v.sorted, v.partial, v.giant);
+    }
+  }
+  if (ev) CSH_HIP(hipEventRecord(ev[4], st));
+  if (fused)
+    hipLaunchKernelGGL(k_msm_mark_giant<Cfg>, dim3((p.NB + 255) / 256, nw), dim3(256), 0, st, p, v.start, v.giant, v.giant + 2, v.big);
+  else
+    hipLaunchKernelGGL(k_msm_merge<Cfg>, dim3((p.NB + MERGE_Q - 1) / MERGE_Q, nw), dim3(MERGE_BLK), 0, st, p, v.start, v.partial, v.dense, v.giant, v.giant + 2, v.big);
+  // buckets with > MERGE_CAP partials (heavily repeated scalars): block-wide tree, grid-stride over the queue; the few with >= GIANT_BIG
+  // partials (a witness's "1"s, a repeated value) are summed in GIANT_SLICES slices by one block each first (blocks past the count return)
+  hipLaunchKernelGGL(k_msm_giant_slices<Cfg>, dim3(GIANT_SLICES, GIANT_ROWS), dim3(256), 0, st, p, v.start, v.partial, v.giant, v.big, v.gscratch);
+  hipLaunchKernelGGL(k_msm_merge_giant<Cfg>, dim3(giant_blocks), dim3(256), 0, st, p, v.start, v.partial, v.dense, v.giant, v.giant + 2, v.big, v.gscratch);
+  return CSH_OK;
+}
+
 // accumulate -> merge -> reduce -> fold tree -> window sums for windows [w0, w0 + nw) on `st`; `group` picks the giant queue.
 // ev (nullable): records ev[4] after the accumulation.
 template <class Cfg>
@@ -803,42 +844,23 @@ int bucket_group(const void* points, const MsmParams& p_all, const SortOut& so, 
   p.wide = p_all.wide > w0 ? p_all.wide - w0 : 0;
   const size_t len = (size_t)p.NB + 2;
   const uint32_t* start = so.start + len * w0;
-  const uint32_t* nlanes = so.nlanes + w0;
-  const uint32_t* sorted = so.sorted + (size_t)p.n * w0;
   LazyPt<Cfg>* partial = bb.partial + (size_t)p.tmax * w0;
   LazyPt<Cfg>* segres = bb.segres + (size_t)p.S * w0;
   LazyPt<Cfg>* dense = bb.dense + (size_t)(p.NB + 1) * w0;
   LazyPt<Cfg>* fold_a = bb.fold_a + (size_t)bb.fold_n1 * w0;
   LazyPt<Cfg>* fold_b = bb.fold_b + (size_t)bb.fold_n1 * w0;
-  uint32_t* giant = bb.giant + (2 * (size_t)bb.max_giant + 2) * group;
-  uint32_t* big = bb.big + (size_t)2 * GIANT_BIG_CAP * group;
-  LazyPt<Cfg>* gscratch = bb.gscratch + (size_t)GIANT_BIG_CAP * GIANT_SLICES * group;
-  const Affine<Fq>* bases = reinterpret_cast<const Affine<Fq>*>(points);
-  {
-    const int tb = tune().acc_blk.load(std::memory_order_relaxed);
-    const int blk = (tb == 64 || tb == 128) ? tb : ACC_BLK;
-    // tune "msm_variant" bit 1: two lanes per point on the G2 groups (curve_pair.hpp). Measured a wash against whole points
-    // per lane (profiles/archive/r02_g_pair_stages.log): one wave of multiply-add code already saturates the SIMD's integer pipe, so
-    // the second wave the smaller footprint buys has nothing to fill. Kept for A/B runs and covered by the GPU parity suite.
-    // Round 3: on BLS12-381 G2 the lane pair IS the default (304 VGPRs, no VGPR spills, against 419 + 6 spills): the whole-point kernel
-    // measured 7.13 .. 7.85 ms at 2^20 from box to box (its accumulation-register traffic makes it the more sensitive one), the pair
-    // 7.24 .. 7.49, and 29.1 against 30.9 ms at 2^22 on the last box (profiles/archive/r03_c_g2_acc_forms.log, r03_v_g2_acc_forms.log). Bit 1
-    // selects the other form of the group's default.
-    bool pair = false;
-    if constexpr (Cfg::PAIR) pair = Cfg::PAIR_ACC_DEFAULT != ((tune().msm_variant.load(std::memory_order_relaxed) & 2) != 0);
-    if constexpr (Cfg::PAIR) {
-      if (pair) {
-        const dim3 ag((2 * bb.max_lanes + blk - 1) / blk, nw), ab(blk);
-        hipLaunchKernelGGL(k_msm_accum_pair<Cfg>, ag, ab, 0, st, bases, p, start, nlanes, sorted, partial, giant);
-      }
-    }
-    if (!pair) {
-      const dim3 ag((bb.max_lanes + blk - 1) / blk, nw), ab(blk);
-      hipLaunchKernelGGL(k_msm_accum<Cfg>, ag, ab, 0, st, bases, p, start, nlanes, sorted, partial, giant);
-    }
-  }
-  if (ev) CSH_HIP(hipEventRecord(ev[4], st));
+  const BucketSumViews<Cfg> views{start, so.nlanes + w0, so.sorted + (size_t)p.n * w0, partial, dense, bb.giant + (2 * (size_t)bb.max_giant + 2) * group,
+                                  bb.big + (size_t)2 * GIANT_BIG_CAP * group, bb.gscratch + (size_t)GIANT_BIG_CAP * GIANT_SLICES * group};
   const int variant = tune().msm_variant.load(std::memory_order_relaxed);
+  // tune "msm_variant" bit 1: two lanes per point on the G2 groups (curve_pair.hpp). Measured a wash against whole points
+  // per lane (profiles/archive/r02_g_pair_stages.log): one wave of multiply-add code already saturates the SIMD's integer pipe, so
+  // the second wave the smaller footprint buys has nothing to fill. Kept for A/B runs and covered by the GPU parity suite.
+  // Round 3: on BLS12-381 G2 the lane pair IS the default (304 VGPRs, no VGPR spills, against 419 + 6 spills): the whole-point kernel
+  // measured 7.13 .. 7.85 ms at 2^20 from box to box (its accumulation-register traffic makes it the more sensitive one), the pair
+  // 7.24 .. 7.49, and 29.1 against 30.9 ms at 2^22 on the last box (profiles/archive/r03_c_g2_acc_forms.log, r03_v_g2_acc_forms.log). Bit 1
+  // selects the other form of the group's default.
+  bool pair = false;
+  if constexpr (Cfg::PAIR) pair = Cfg::PAIR_ACC_DEFAULT != ((variant & 2) != 0);
   int form;  // 0 lane-serial, 1 quad, 2 pair
   if constexpr (Cfg::PAIR) form = (variant & 1) ? 1 : ((variant & 4) ? 0 : 2);
   else form = (variant & 1) ? 0 : 1;
@@ -848,14 +870,7 @@ int bucket_group(const void* points, const MsmParams& p_all, const SortOut& so, 
   // dependent chain, while the merge launch does them with one quad per bucket, all buckets at once) and gains 5 % of the tail on
   // BLS12-381 G2 only. Kept as a parity-tested variant; the separate merge launch stays the default.
   const bool fused = form != 0 && (variant & 16) != 0;
-  if (fused)
-    hipLaunchKernelGGL(k_msm_mark_giant<Cfg>, dim3((p.NB + 255) / 256, nw), dim3(256), 0, st, p, start, giant, giant + 2, big);
-  else
-    hipLaunchKernelGGL(k_msm_merge<Cfg>, dim3((p.NB + MERGE_Q - 1) / MERGE_Q, nw), dim3(MERGE_BLK), 0, st, p, start, partial, dense, giant, giant + 2, big);
-  // buckets with > MERGE_CAP partials (heavily repeated scalars): block-wide tree, grid-stride over the queue; the few with >= GIANT_BIG
-  // partials (a witness's "1"s, a repeated value) are summed in GIANT_SLICES slices by one block each first (blocks past the count return)
-  hipLaunchKernelGGL(k_msm_giant_slices<Cfg>, dim3(GIANT_SLICES, GIANT_ROWS), dim3(256), 0, st, p, start, partial, giant, big, gscratch);
-  hipLaunchKernelGGL(k_msm_merge_giant<Cfg>, dim3(bb.giant_blocks), dim3(256), 0, st, p, start, partial, dense, giant, giant + 2, big, gscratch);
+  CSH_TRY((bucket_sums_launch<Cfg>(reinterpret_cast<const Affine<Fq>*>(points), p, views, bb.max_lanes, bb.giant_blocks, nw, pair, fused, st, ev)));
   // Window reduction, three forms of the same segment walk, each with as many segments as fit one round of its waves
   // (reduce_segments): four lanes per point (curve_quad.hpp; the default on the G1 groups: BN254 G1 2^20 tail 0.41 -> 0.33 ms,
   // BLS12-381 G1 0.96 -> 0.80 ms against the lane-serial form at equal launch width, profiles/archive/r02_g_seg_stages3.log), two lanes
@@ -1273,6 +1288,86 @@ int msm_tail_selftest_t(const void* dense_host, uint32_t NB, uint32_t S, int for
   return CSH_OK;
 }
 
+// Test hook (selftest_dev.hip csh_selftest_msm_buckets_dev): the bucket stage up to the per-bucket sums -- bucket_sums_launch, the
+// launches bucket_group runs -- on bucket lists the caller built. B: a handle of the public upload (the stored form of the points is the
+// product's). pp: W (1 .. 4), NB, n, L, Ln (L or 2 L), wide as the caller chose them; tmax and S come from msm_plan_slots, the scratch
+// from bucket_take, as for a real call. start_host [W][NB + 2] and sorted_host [W][n] in the layout of the sort stage; nlanes is
+// computed here (ceil(start[w][NB + 1] / lane_len(p, w))) and, where the caller passes its own, required to be equal. Everything a kernel
+// will index is checked on the host before anything is launched. All scratch starts as 0xFF bytes (the arena of a real call is dirty
+// too). On return the stream is idle and `run` holds the device views (valid until the thread's arena is used again) and the two words of
+// giant_count (queued buckets, sliced buckets). Instantiated with the kernels it launches (CSH_MSM_INSTANTIATE).
+template <class Cfg>
+struct BucketsSelftestRun {
+  MsmParams p;
+  const uint32_t* start;                  // [W][NB + 2], device
+  const LazyPt<Cfg>*partial, *dense;      // [W][tmax], [W][NB + 1]
+  uint32_t giant_count[2];
+};
+template <class Cfg>
+int msm_buckets_selftest_t(const Bases* B, int pair, int fused, const MsmParams* pp, const uint32_t* start_host, const uint32_t* sorted_host,
+                           const uint32_t* nlanes_host, BucketsSelftestRun<Cfg>* run) {
+  using Fq = typename Cfg::Fq;
+  CSH_REQUIRE(B && pp && start_host && sorted_host && run, "msm_buckets_selftest: NULL argument");
+  CSH_REQUIRE(!pair || Cfg::PAIR, "msm_buckets_selftest: the lane pair exists on the G2 groups only");
+  MsmParams p{};
+  p.W = pp->W, p.NB = pp->NB, p.n = pp->n, p.L = pp->L, p.Ln = pp->Ln, p.wide = pp->wide;
+  CSH_REQUIRE(p.W >= 1 && p.W <= 4 && p.NB >= 1 && p.NB <= (1u << 16) && p.n >= 1 && p.n <= (1u << 20), "msm_buckets_selftest: W, NB or n out of range");
+  CSH_REQUIRE(p.L >= 1 && p.L <= 1024 && (p.Ln == p.L || p.Ln == 2 * p.L) && p.wide >= 0 && p.wide <= p.W, "msm_buckets_selftest: L, Ln or wide out of range");
+  CSH_REQUIRE(B->n >= 1 && B->n < (size_t(1) << 31), "msm_buckets_selftest: empty handle");
+  CSH_TRY(ensure_device());
+  int dev = -1;
+  CSH_HIP(hipGetDevice(&dev));
+  CSH_REQUIRE(dev == B->device, "msm_buckets_selftest: the handle lives on another device");
+  const size_t len = (size_t)p.NB + 2;
+  uint32_t nl[MAX_WINDOWS] = {0};
+  for (int w = 0; w < p.W; ++w) {  // every index a kernel will use, checked here
+    const uint32_t* st = start_host + len * w;
+    CSH_REQUIRE(st[0] == 0 && st[1] == 0, "msm_buckets_selftest: start[0] and start[1] must be 0");
+    for (uint32_t b = 1; b <= p.NB; ++b) CSH_REQUIRE(st[b] <= st[b + 1], "msm_buckets_selftest: start is not monotone");
+    const uint32_t total = st[p.NB + 1];
+    CSH_REQUIRE(total <= p.n, "msm_buckets_selftest: a window holds more than n entries");
+    const uint32_t* so = sorted_host + (size_t)p.n * w;
+    for (uint32_t i = 0; i < total; ++i) CSH_REQUIRE((so[i] & 0x7fffffffu) < B->n, "msm_buckets_selftest: an entry id is not below the handle's length");
+    const uint32_t Lw = lane_len(p, w);
+    nl[w] = (total + Lw - 1) / Lw;
+    CSH_REQUIRE(!nlanes_host || nlanes_host[w] == nl[w], "msm_buckets_selftest: nlanes is not ceil(entries / lane length)");
+  }
+  msm_plan_slots(p, p.n);
+  hipStream_t st = resolve_stream(nullptr);
+  Arena& ar = arena_for(st);
+  struct Bufs {
+    uint32_t *start, *nlanes, *sorted;
+    BucketBufs<Cfg> bb;
+  };
+  const auto take = [&](Arena& a) {  // the sort stage's three outputs in front of the bucket stage's scratch
+    Bufs b;
+    b.start = a.take<uint32_t>(len * p.W);
+    b.nlanes = a.take<uint32_t>(MAX_WINDOWS);
+    b.sorted = a.take<uint32_t>((size_t)p.n * p.W);
+    b.bb = bucket_take<Cfg>(p, a);
+    return b;
+  };
+  Arena sizing;  // no memory behind it: take() only advances off
+  take(sizing);
+  CSH_TRY(ar.reserve(sizing.off));
+  CSH_HIP(hipMemset(ar.base, 0xFF, sizing.off));
+  const Bufs d = take(ar);
+  CSH_HIP(hipMemcpy(d.start, start_host, len * p.W * sizeof(uint32_t), hipMemcpyHostToDevice));
+  CSH_HIP(hipMemcpy(d.nlanes, nl, (size_t)p.W * sizeof(uint32_t), hipMemcpyHostToDevice));
+  CSH_HIP(hipMemcpy(d.sorted, sorted_host, (size_t)p.n * p.W * sizeof(uint32_t), hipMemcpyHostToDevice));
+  CSH_HIP(hipDeviceSynchronize());  // fill and uploads ran on the null stream, the stage runs on the thread's own
+  const BucketSumViews<Cfg> views{d.start, d.nlanes, d.sorted, d.bb.partial, d.bb.dense, d.bb.giant, d.bb.big, d.bb.gscratch};
+  CSH_TRY((bucket_sums_launch<Cfg>(reinterpret_cast<const Affine<Fq>*>(B->points), p, views, d.bb.max_lanes, d.bb.giant_blocks, p.W, pair != 0, fused != 0, st, nullptr)));
+  CSH_HIP(hipGetLastError());
+  CSH_HIP(hipStreamSynchronize(st));
+  CSH_HIP(hipMemcpy(run->giant_count, d.bb.giant, sizeof run->giant_count, hipMemcpyDeviceToHost));
+  run->p = p;
+  run->start = d.start;
+  run->partial = d.bb.partial;
+  run->dense = d.bb.dense;
+  return CSH_OK;
+}
+
 // The accumulate kernels are instantiated in their own translation units (msm_accum_*.hip, which define CSH_PIN_MADS 3: the
 // product-scanning Montgomery multiplication with its multiply-add order pinned); the per-configuration units below see them
 // as explicit-instantiation declarations, so their own copy of the field code stays unpinned for the tail kernels.
@@ -1290,6 +1385,7 @@ int msm_tail_selftest_t(const void* dense_host, uint32_t NB, uint32_t S, int for
   KW template int fold_partials_t<CFG>(const void*, size_t, void*);                                                             \
   KW template int repack_bases_t<CFG>(Bases*, hipStream_t);                                                                     \
   KW template int msm_tail_selftest_t<CFG>(const void*, uint32_t, uint32_t, int, void*);                                        \
+  KW template int msm_buckets_selftest_t<CFG>(const Bases*, int, int, const MsmParams*, const uint32_t*, const uint32_t*, const uint32_t*, BucketsSelftestRun<CFG>*); \
   KW template size_t msm_bucket_bytes<CFG>(const MsmParams*);                                                                   \
   KW template int msm_bucket_stage<CFG>(const void*, const MsmParams*, const SortOut*, hipStream_t, Arena*, void*, hipEvent_t*);          \
   KW template int precompute_table_t<CFG>(Bases*, int, int, hipStream_t);                                                            \

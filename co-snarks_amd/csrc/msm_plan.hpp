@@ -150,6 +150,15 @@ struct MsmPlan {
   bool merged;
 };
 
+// partial slots per window of the accumulate kernels (slot = bucket + lane) and the reduction segments the scratch is sized for, from
+// p.NB, p.W and p.L: the one place both are decided -- msm_plan_tail below, and the device unit test of the bucket stage
+// (msm_impl.hpp msm_buckets_selftest_t), which takes its lane length from the caller
+inline void msm_plan_slots(MsmParams& p, uint64_t entries) {
+  const uint32_t max_lanes = (uint32_t)((entries + p.L - 1) / p.L);
+  p.tmax = p.NB + max_lanes + 2;  // partial slots per window: slot = bucket + lane
+  p.S = reduce_segments(p.NB, p.W, 1);
+}
+
 // what both kinds of plan derive from (entries per window, W, NB): lane length, partial slots, reduction segments, sort chunks
 inline void msm_plan_tail(MsmParams& p, uint64_t entries, int occ) {
   p.L = choose_lane_length((size_t)entries, p.W, occ);
@@ -158,9 +167,7 @@ inline void msm_plan_tail(MsmParams& p, uint64_t entries, int occ) {
   // three groups): +6 .. +26 % -- at these sizes the accumulate launch is a dependent chain per lane, and doubling it costs more than the
   // merge saves. One length is the default; tune "msm_variant" bit 6 (64) selects the doubled form (kept parity-tested for A/B).
   p.Ln = (p.wide < p.W && p.L <= 32 && (tune().msm_variant.load(std::memory_order_relaxed) & 64) != 0) ? 2 * p.L : p.L;
-  const uint32_t max_lanes = (uint32_t)((entries + p.L - 1) / p.L);
-  p.tmax = p.NB + max_lanes + 2;  // partial slots per window: slot = bucket + lane
-  p.S = reduce_segments(p.NB, p.W, 1);
+  msm_plan_slots(p, entries);
   uint64_t ch = 512 / (uint64_t)p.W;
   const uint64_t by_size = entries / (2ull * p.NB);
   if (ch > by_size) ch = by_size;

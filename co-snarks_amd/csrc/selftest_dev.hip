@@ -1,6 +1,7 @@
 // Device-executed self-test hooks for the arithmetic that exists on the device only: curve_quad.hpp (one XYZZ point over a DPP
 // quad) and curve_pair.hpp (one Fp2 value over a lane pair), plus a launcher of the real window-reduction and fold-tree kernels
-// on bucket arrays the caller chooses, a runner of the MSM sort stage alone (digits, bucket offsets, bucket lists copied back), and host-pointer entry points around the two fused launchers that end a witness map
+// on bucket arrays the caller chooses, a runner of the MSM sort stage alone (digits, bucket offsets, bucket lists copied back), a runner of
+// the bucket stage up to the per-bucket sums (the accumulate and merge launches of bucket_group on bucket lists the caller chooses), and host-pointer entry points around the two fused launchers that end a witness map
 // (vec_ops.hip), which the C ABI reaches only through csh_groth16_h_dev. The kernels here are compiled with the device form of the limb-bound contract
 // (field29.hpp, CSH_CHECK_BOUNDS_DEVICE): a violated operand bound is counted in g_bound_record, never trapped; every entry
 // point hands the record back and clears it. Test infrastructure; not declared in include/cosnarks_hip.h.
@@ -15,7 +16,9 @@ using namespace csh;
 
 namespace csh {
 // the tail launchers live with the kernels they launch (msm_inst_*.hip): no second instantiation of a k_msm_* kernel here
-#define CSH_ST_TAIL_DECL(CFG) extern template int msm_tail_selftest_t<CFG>(const void*, uint32_t, uint32_t, int, void*);
+#define CSH_ST_TAIL_DECL(CFG)                                                                       \
+  extern template int msm_tail_selftest_t<CFG>(const void*, uint32_t, uint32_t, int, void*); \
+  extern template int msm_buckets_selftest_t<CFG>(const Bases*, int, int, const MsmParams*, const uint32_t*, const uint32_t*, const uint32_t*, BucketsSelftestRun<CFG>*);
 CSH_ST_TAIL_DECL(Bn254G1Cfg)
 CSH_ST_TAIL_DECL(Bn254G2Cfg)
 CSH_ST_TAIL_DECL(Bls381G1Cfg)
@@ -23,6 +26,9 @@ CSH_ST_TAIL_DECL(Bls381G2Cfg)
 CSH_ST_TAIL_DECL(GrumpkinG1Cfg)
 CSH_ST_TAIL_DECL(Bls377G1Cfg)
 CSH_ST_TAIL_DECL(Bls377G2Cfg)
+// selftest_buckets_dev.hip, instantiated there for the seven configurations
+template <class Cfg>
+int st_bucket_export_launch(bool pair, const MsmParams& p, const uint32_t* start, const LazyPt<Cfg>* partial, const LazyPt<Cfg>* dense, LazyPt<Cfg>* out);
 }  // namespace csh
 
 namespace {
@@ -355,6 +361,43 @@ int msm_tail_t(int form, const void* affine_pts, const uint8_t* neg, size_t npts
   return msm_tail_selftest_t<Cfg>(dense.data(), NB, S, form, out_xyzz);
 }
 
+// ---- the bucket stage up to the per-bucket sums --------------------------------------------------------------------------------
+// Fused merge form: the two kernels that call qbucket_merged / pbucket_merged once per bucket live in selftest_buckets_dev.hip, a unit
+// compiled as the product's are (without the limb-bound instrumentation of this one), so that the functions run in the form
+// k_msm_reduce<Cfg, true> and k_msm_reduce_pair<Cfg, true> run them in. out: W * NB lazy points, bucket b of window w at [w * NB + b - 1].
+// Plan words, scratch and launches are the product's (msm_buckets_selftest_t, instantiated next to the kernels, runs bucket_sums_launch
+// as bucket_group does); this adds the export. merge_form 0: dense[w][1 .. NB] as k_msm_merge and k_msm_merge_giant left it; 1 / 2: the
+// two kernels above after k_msm_mark_giant and the giant launches.
+template <class Cfg>
+int msm_buckets_t(const Bases* B, int acc_form, int merge_form, const MsmParams& in, const uint32_t* start, const uint32_t* sorted, const uint32_t* nlanes,
+                  void* out_xyzz, uint32_t* giant_count, uint64_t rec[3]) {
+  using L = typename Cfg::L;
+  using Fq = typename Cfg::Fq;
+  CSH_REQUIRE(acc_form >= 0 && acc_form <= 1 && merge_form >= 0 && merge_form <= 2, "selftest_msm_buckets: unknown form");
+  CSH_REQUIRE(Cfg::PAIR || (acc_form == 0 && merge_form != 2), "selftest_msm_buckets: the lane-pair forms exist on the G2 groups only");
+  BucketsSelftestRun<Cfg> run;
+  CSH_TRY(msm_buckets_selftest_t<Cfg>(B, acc_form, merge_form != 0, &in, start, sorted, nlanes, &run));
+  const MsmParams& p = run.p;
+  const size_t nout = (size_t)p.W * p.NB;
+  DevMem dlazy, dx;
+  CSH_TRY(dx.alloc(nout * sizeof(XYZZ<Fq>)));
+  CSH_TRY(bound_record_clear());
+  if (merge_form == 0) {
+    for (int w = 0; w < p.W; ++w)
+      hipLaunchKernelGGL((k_st_export<L, Fq>), dim3((p.NB + 127) / 128), dim3(128), 0, 0, run.dense + (size_t)w * (p.NB + 1) + 1, p.NB, dx.as<XYZZ<Fq>>() + (size_t)w * p.NB);
+  } else {
+    CSH_TRY(dlazy.alloc(nout * sizeof(LazyPt<Cfg>)));
+    CSH_TRY(st_bucket_export_launch<Cfg>(merge_form == 2, p, run.start, run.partial, run.dense, dlazy.as<LazyPt<Cfg>>()));
+    hipLaunchKernelGGL((k_st_export<L, Fq>), dim3((unsigned)((nout + 127) / 128)), dim3(128), 0, 0, dlazy.as<LazyPt<Cfg>>(), (uint32_t)nout, dx.as<XYZZ<Fq>>());
+  }
+  CSH_HIP(hipGetLastError());
+  CSH_TRY(bound_record_take(rec));
+  CSH_HIP(hipMemcpy(out_xyzz, dx.p, nout * sizeof(XYZZ<Fq>), hipMemcpyDeviceToHost));
+  giant_count[0] = run.giant_count[0];
+  giant_count[1] = run.giant_count[1];
+  return CSH_OK;
+}
+
 // ---- the sort stage alone -------------------------------------------------------------------------------------------------------
 // Plan, scratch and launches are the product's own (msm_plan, msm_sort_bytes, GroupOps::sort = msm_sort_stage<Fr> as msm.hip instantiates
 // it: no kernel of the stage gets a second home here); this only uploads the scalars, fills the scratch with 0xFF bytes (the arena of
@@ -515,6 +558,24 @@ int csh_selftest_msm_tail_dev(int curve, int group, int form, const void* affine
                               const uint32_t* bucket_off, size_t nocc, uint32_t NB, uint32_t S, void* out_xyzz) {
   CSH_TRY(ensure_device());
   ST_GROUP_DISPATCH(curve, group, (msm_tail_t<Cfg>(form, affine_pts, neg, npts, bucket_ids, bucket_off, nocc, NB, S, out_xyzz)));
+}
+
+// The bucket stage up to the per-bucket sums, through the launches bucket_group itself runs (msm_impl.hpp bucket_sums_launch): accumulate
+// (acc_form 0: whole points per lane, 1: a lane pair, G2 only), then k_msm_merge (merge_form 0) or k_msm_mark_giant (1: the bucket sums
+// then come from qbucket_merged, 2: from pbucket_merged, G2 only), then k_msm_giant_slices and k_msm_merge_giant. bases: a handle of
+// csh_bases_upload. start = [W][NB + 2] and sorted = [W][n] host words as the sort stage leaves them (tests/msm_sort_ref.py); nlanes:
+// NULL, or [W] words that must equal what the hook computes. W 1 .. 4, lane lengths L and Ln (L or 2 L; windows from `wide` on take Ln).
+// CSH_ERR_INVALID, before any launch, unless start[0] == start[1] == 0, start is monotone, start[NB + 1] <= n and every id (bit 31 =
+// the sign) is below the handle's length. out_xyzz: bucket b of window w at [w * NB + b - 1], XYZZ points in arkworks words;
+// giant_count: queued buckets, sliced buckets.
+int csh_selftest_msm_buckets_dev(csh_bases_t bases, int acc_form, int merge_form, int W, uint32_t NB, uint32_t n, uint32_t L, uint32_t Ln, int wide,
+                                 const uint32_t* start, const uint32_t* sorted, const uint32_t* nlanes, void* out_xyzz, uint32_t* giant_count, uint64_t rec[3]) {
+  CSH_REQUIRE(bases && start && sorted && out_xyzz && giant_count && rec, "selftest_msm_buckets: NULL argument");
+  CSH_TRY(ensure_device());
+  const Bases* B = reinterpret_cast<const Bases*>(bases);
+  MsmParams in{};
+  in.W = W, in.NB = NB, in.n = n, in.L = L, in.Ln = Ln, in.wide = wide;
+  ST_GROUP_DISPATCH(B->curve, B->group, (msm_buckets_t<Cfg>(B, acc_form, merge_form, in, start, sorted, nlanes, out_xyzz, giant_count, rec)));
 }
 
 // The MSM sort stage alone (digits -> counting sort; plain single-level, plain two-level or wide, as msm_plan and the tune knobs decide)

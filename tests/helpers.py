@@ -107,6 +107,31 @@ def rand_points(curve: cv.Curve, n, r, with_inf=False):
     return pts
 
 
+def known_points(G, n, r):
+    """n points with known discrete logarithms: (points, scalars), pts[i] = scalars[i] * G.gen."""
+    a, b = r.randrange(1, G.order), r.randrange(1, G.order)
+    cur, step = G.mul(G.gen, a), G.mul(G.gen, b)
+    pts, sc = [], []
+    for i in range(n):
+        pts.append(cur)
+        sc.append((a + i * b) % G.order)
+        cur = G.add(cur, step)
+    return pts, sc
+
+
+def xyzz_to_affine(G, arr, n):
+    """n XYZZ points in arkworks words -> oracle affine points; checks the canonical encoding and ZZ^3 == ZZZ^2."""
+    F = G.F
+    out = []
+    for i, (X, Y, ZZ, ZZZ) in enumerate(cv.unpack_points(G, arr, ncoords=4, strict=True)):
+        if F.is_zero(ZZ):
+            out.append(None)
+            continue
+        assert F.eq(F.mul(F.sqr(ZZ), ZZ), F.sqr(ZZZ)), "point %d: ZZ^3 != ZZZ^2" % i
+        out.append((F.mul(X, F.inv(ZZ)), F.mul(Y, F.inv(ZZZ))))
+    return out
+
+
 def jac_to_affine(curve: cv.Curve, limbs):
     """C-ABI Jacobian output -> oracle affine point. Strict: every coordinate component must be < q (canonical Montgomery form)."""
     (X, Y, Z), = cv.unpack_points(curve, np.asarray(limbs), ncoords=3, strict=True)

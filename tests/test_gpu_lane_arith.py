@@ -51,33 +51,14 @@ def _assert_no_bound_violation(rec, what):
         what, n, limb, np.log2(max(limb, 1)), line, _site(line))
 
 
-def _xyzz_to_affine(G, arr, n):
-    """n XYZZ points in arkworks words -> oracle affine points; checks the canonical encoding and ZZ^3 == ZZZ^2."""
-    F = G.F
-    out = []
-    for i, (X, Y, ZZ, ZZZ) in enumerate(cv.unpack_points(G, arr, ncoords=4, strict=True)):
-        if F.is_zero(ZZ):
-            out.append(None)
-            continue
-        assert F.eq(F.mul(F.sqr(ZZ), ZZ), F.sqr(ZZZ)), "point %d: ZZ^3 != ZZZ^2" % i
-        out.append((F.mul(X, F.inv(ZZ)), F.mul(Y, F.inv(ZZZ))))
-    return out
+_xyzz_to_affine = H.xyzz_to_affine                                         # shared with tests/test_gpu_msm_buckets.py
 
 
 def _xyzz_words(hip, curve, group):
     return 2 * hip.point_bytes(H.CURVE_IDS[curve], group) // 8
 
 
-def _known_points(G, n, r):
-    """n points with known discrete logarithms: (points, scalars), pts[i] = scalars[i] * G.gen."""
-    a, b = r.randrange(1, G.order), r.randrange(1, G.order)
-    cur, step = G.mul(G.gen, a), G.mul(G.gen, b)
-    pts, sc = [], []
-    for i in range(n):
-        pts.append(cur)
-        sc.append((a + i * b) % G.order)
-        cur = G.add(cur, step)
-    return pts, sc
+_known_points = H.known_points
 
 
 # ---- 1(a): the recorder itself ----------------------------------------------------------------------------------------------------
