@@ -31,7 +31,19 @@ from .bindings import (  # noqa: F401
     fr_bytes,
     groth16_h,
     have_device,
+    HonkCoBatch,
     HonkMemoryRecords,
+    honk_co_arith,
+    honk_co_delta_finish,
+    honk_co_delta_operands,
+    honk_co_delta_sub_one,
+    honk_co_lookup_finish,
+    honk_co_lookup_mid,
+    honk_co_lookup_operands,
+    honk_co_perm_finish,
+    honk_co_perm_operands,
+    honk_co_perm_operands2,
+    honk_co_select_edges,
     honk_lookup_operands,
     honk_perm_operands,
     honk_pow_table,

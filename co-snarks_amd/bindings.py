@@ -743,6 +743,145 @@ def honk_pow_table(curve: int, betas, out=None, stream=None):
     return out
 
 
+# ---- the sumcheck round on shares (csrc/honk_co_relations.hip): one wrapper per entry of include/cosnarks_hip.h ----------------------
+HONK_CO_POINTS = 7                # batch elements per kept edge
+
+
+class HonkCoBatch:
+    """What the stages of one relation's batch share: the party, the 36 columns (DeviceBuffers, device addresses, or None for a column
+    the stage does not read), the range, the kept edges (edge_idx = the DeviceBuffer of honk_co_select_edges with m = its count, or None
+    for every edge of the range), the scaling table and the host parameters beta, gamma, public_input_delta. The column count and the
+    range rules are checked here, before any call."""
+
+    def __init__(self, curve: int, protocol: int, party: int, cols, edge_begin: int, edge_end: int, edge_idx=None, m=None, scaling=None,
+                 scaling_stride: int = 1, params=None):
+        if len(cols) != HONK_SUMCHECK_COLUMNS:
+            raise CoSnarksHipError("honk_co: %d columns, not %d" % (len(cols), HONK_SUMCHECK_COLUMNS))
+        if protocol not in (0, 1) or party not in (0, 1, 2):
+            raise CoSnarksHipError("honk_co: protocol must be 0 (plain / Shamir) or 1 (Rep3), party 0, 1 or 2")
+        if edge_begin < 0 or edge_begin % 2 or edge_end % 2 or not edge_begin < edge_end <= HONK_MAX_EDGE_END:
+            raise CoSnarksHipError("honk_co: edge_begin and edge_end must be even, edge_begin < edge_end <= 2^28")
+        if scaling is not None and not 1 <= scaling_stride <= HONK_MAX_EDGE_END:
+            raise CoSnarksHipError("honk_co: scaling_stride must be 1 .. 2^28")
+        edges = (edge_end - edge_begin) // 2
+        m = edges if m is None else int(m)
+        if (edge_idx is None and m != edges) or not 0 <= m <= edges:
+            raise CoSnarksHipError("honk_co: m must be the number of edges of the range, or with an edge list at most that")
+        self.curve, self.protocol, self.party, self.cols, self.edge_begin, self.edge_end = curve, protocol, party, list(cols), edge_begin, edge_end
+        self.edge_idx, self.m, self.scaling, self.scaling_stride = edge_idx, m, scaling, scaling_stride
+        self.params = _u64(params) if params is not None else None
+        if self.params is not None and self.params.size != 12:
+            raise CoSnarksHipError("honk_co: params are beta, gamma, public_input_delta (3 elements of 4 words)")
+        self.ncomp = protocol + 1
+
+    def common(self):
+        return (self.curve, C.c_uint32(self.protocol), C.c_uint32(self.party), _devptr_array(self.cols), C.c_size_t(self.edge_begin),
+                C.c_size_t(self.edge_end), _devptr(self.edge_idx), C.c_size_t(self.m))
+
+    def scaled(self):
+        return (_devptr(self.scaling), C.c_size_t(self.scaling_stride))
+
+    def shares(self, count):
+        """a DeviceBuffer of `count` batch vectors (7 m shares each)"""
+        return DeviceBuffer(max(32, 32 * count * HONK_CO_POINTS * self.m * self.ncomp))
+
+    def acc(self, elems, ncomp=None):
+        return DeviceBuffer(32 * elems * (ncomp or self.ncomp))
+
+
+def honk_co_select_edges(curve: int, selector, edge_begin: int, edge_end: int, edge_idx=None, count=None, stream=None):
+    """csh_honk_co_select_edges_dev: selector = the q_arith or q_delta_range column. -> (edge_idx: uint32 per edge of the range, the kept
+    e >> 1 in front; count: one uint32 word), made here unless given. The caller copies the count back."""
+    if edge_begin < 0 or edge_begin % 2 or edge_end % 2 or not edge_begin < edge_end <= HONK_MAX_EDGE_END:
+        raise CoSnarksHipError("honk_co_select_edges: edge_begin and edge_end must be even, edge_begin < edge_end <= 2^28")
+    if edge_idx is None:
+        edge_idx = DeviceBuffer(4 * ((edge_end - edge_begin) // 2))
+    if count is None:
+        count = DeviceBuffer(4)
+    _check(lib().csh_honk_co_select_edges_dev(curve, _devptr(selector), C.c_size_t(edge_begin), C.c_size_t(edge_end), _devptr(edge_idx),
+                                              _devptr(count), _stream(stream)))
+    return edge_idx, count
+
+
+def honk_co_arith(b: HonkCoBatch, mask=None, r0=None, r1=None, stream=None):
+    """csh_honk_co_arith_dev: mask = 7 m elements for Rep3, None for protocol 0. -> (r0: 6 elements, a half share; r1: 5 shares)"""
+    if (b.protocol == 1) != (mask is not None) and b.m:
+        raise CoSnarksHipError("honk_co_arith: the mask vector is required for Rep3 and must be None for protocol 0")
+    r0 = r0 if r0 is not None else b.acc(6, 1)
+    r1 = r1 if r1 is not None else b.acc(5)
+    _check(lib().csh_honk_co_arith_dev(*b.common(), *b.scaled(), _devptr(mask), _devptr(r0), _devptr(r1), _stream(stream)))
+    return r0, r1
+
+
+def honk_co_perm_operands(b: HonkCoBatch, lhs=None, rhs=None, stream=None):
+    """csh_honk_co_perm_operands_dev -> (lhs, rhs), 4 * 7 m shares each"""
+    lhs = lhs if lhs is not None else b.shares(4)
+    rhs = rhs if rhs is not None else b.shares(4)
+    _check(lib().csh_honk_co_perm_operands_dev(*b.common(), _p(b.params), _devptr(lhs), _devptr(rhs), _stream(stream)))
+    return lhs, rhs
+
+
+def honk_co_perm_operands2(b: HonkCoBatch, rhs=None, stream=None):
+    """csh_honk_co_perm_operands2_dev -> rhs, 2 * 7 m shares"""
+    rhs = rhs if rhs is not None else b.shares(2)
+    _check(lib().csh_honk_co_perm_operands2_dev(*b.common(), _p(b.params), _devptr(rhs), _stream(stream)))
+    return rhs
+
+
+def honk_co_perm_finish(b: HonkCoBatch, prod, acc=None, stream=None):
+    """csh_honk_co_perm_finish_dev: prod = 2 * 7 m shares -> acc = perm.r0 (6 shares), perm.r1 (3 shares)"""
+    acc = acc if acc is not None else b.acc(9)
+    _check(lib().csh_honk_co_perm_finish_dev(*b.common(), *b.scaled(), _devptr(prod), _devptr(acc), _stream(stream)))
+    return acc
+
+
+def honk_co_delta_operands(b: HonkCoBatch, lhs=None, stream=None):
+    """csh_honk_co_delta_operands_dev -> lhs, 8 * 7 m shares"""
+    lhs = lhs if lhs is not None else b.shares(8)
+    _check(lib().csh_honk_co_delta_operands_dev(*b.common(), _devptr(lhs), _stream(stream)))
+    return lhs
+
+
+def honk_co_delta_sub_one(curve: int, protocol: int, party: int, sqr, m: int, stream=None):
+    """csh_honk_co_delta_sub_one_dev: (+) -1 on the 8 * 7 m shares of sqr, in place"""
+    if protocol not in (0, 1) or party not in (0, 1, 2) or not 0 <= m <= HONK_MAX_EDGE_END // 2:
+        raise CoSnarksHipError("honk_co_delta_sub_one: protocol 0 or 1, party 0, 1 or 2, m at most 2^27")
+    _check(lib().csh_honk_co_delta_sub_one_dev(curve, C.c_uint32(protocol), C.c_uint32(party), _devptr(sqr), C.c_size_t(m), _stream(stream)))
+    return sqr
+
+
+def honk_co_delta_finish(b: HonkCoBatch, mul, acc=None, stream=None):
+    """csh_honk_co_delta_finish_dev: mul = 4 * 7 m shares -> acc = delta.r0 .. r3 (6 shares each)"""
+    acc = acc if acc is not None else b.acc(24)
+    _check(lib().csh_honk_co_delta_finish_dev(*b.common(), *b.scaled(), _devptr(mul), _devptr(acc), _stream(stream)))
+    return acc
+
+
+def honk_co_lookup_operands(b: HonkCoBatch, read_term=None, inverses=None, stream=None):
+    """csh_honk_co_lookup_operands_dev -> (read_term, inverses), 7 m shares each"""
+    read_term = read_term if read_term is not None else b.shares(1)
+    inverses = inverses if inverses is not None else b.shares(1)
+    _check(lib().csh_honk_co_lookup_operands_dev(*b.common(), _p(b.params), _devptr(read_term), _devptr(inverses), _stream(stream)))
+    return read_term, inverses
+
+
+def honk_co_lookup_mid(b: HonkCoBatch, write_inverse, r0=None, lhs=None, rhs=None, stream=None):
+    """csh_honk_co_lookup_mid_dev: write_inverse = 7 m shares -> (r0: 5 shares; lhs, rhs: 2 * 7 m shares each)"""
+    r0 = r0 if r0 is not None else b.acc(5)
+    lhs = lhs if lhs is not None else b.shares(2)
+    rhs = rhs if rhs is not None else b.shares(2)
+    _check(lib().csh_honk_co_lookup_mid_dev(*b.common(), *b.scaled(), _p(b.params), _devptr(write_inverse), _devptr(r0), _devptr(lhs),
+                                            _devptr(rhs), _stream(stream)))
+    return r0, lhs, rhs
+
+
+def honk_co_lookup_finish(b: HonkCoBatch, mul, acc=None, stream=None):
+    """csh_honk_co_lookup_finish_dev: mul = 2 * 7 m shares -> acc = lookup.r1 (5 shares, no scaling), lookup.r2 (3 shares)"""
+    acc = acc if acc is not None else b.acc(8)
+    _check(lib().csh_honk_co_lookup_finish_dev(*b.common(), *b.scaled(), _p(b.params), _devptr(mul), _devptr(acc), _stream(stream)))
+    return acc
+
+
 def rep3_local_mul_vec(curve: int, lhs_ab, rhs_ab, mask=None):
     l, r = _u64(lhs_ab), _u64(rhs_ab)
     n = l.size // 8

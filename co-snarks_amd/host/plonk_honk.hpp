@@ -1426,4 +1426,191 @@ struct ShamirPlonkDriver {
   }
 };
 
+// ---- the sumcheck round on shares (csrc/honk_co_relations.hip) -------------------------------------------------------------------------
+// accumulate_relation_univariates_batch (co-noir/co-ultrahonk/src/co_decider/co_sumcheck/co_sumcheck_round.rs:140-218) for the arithmetic,
+// permutation, delta-range and lookup relations over one party's state and network: every stretch of local arithmetic is a device stage,
+// T::mul_many is the device's local product plus the party's network round, and arith.r0 is reshared at the end (:292).
+//
+// A network policy is what T::mul_many, T::local_mul_vec's randomness and T::reshare are for one party:
+//   PROTOCOL, party()        the protocol and party_id of the device entries
+//   masks<P>(pool, n)        the n mask elements that local_mul_vec draws, on the device (nullptr for protocol 0)
+//   mul_many<P>(pool, lhs, rhs, n)   device share vectors of n shares -> their product, n shares on the device
+//   reshare(half)            host half shares -> shares (ncomp values each)
+// Protocol 0 with the identity network: one party, the product of the shares is the share of the product.
+struct HonkCoIdentityNet {
+  static constexpr uint32_t PROTOCOL = 0;
+  uint32_t party() const { return 0; }
+  template <class P>
+  const uint64_t* masks(detail::DevicePool&, size_t) {
+    return nullptr;
+  }
+  template <class P>
+  uint64_t* mul_many(detail::DevicePool& pool, const uint64_t* lhs, const uint64_t* rhs, size_t n) {
+    uint64_t* out = pool.fresh(32 * n);
+    check(csh_vec_mul_dev(P::ID, lhs, rhs, out, n, nullptr), "csh_vec_mul_dev");
+    return out;
+  }
+  template <class Fr>
+  std::vector<Fr> reshare(const std::vector<Fr>& half) {
+    return half;
+  }
+};
+// Rep3 (rep3/arithmetic.rs:132-161): masked local products on the device, the half shares to the next party, the previous party's back
+struct HonkCoRep3Net {
+  static constexpr uint32_t PROTOCOL = 1;
+  const LocalNetwork& net;
+  Rep3State& st;
+  uint32_t party() const { return (uint32_t)st.id; }
+  template <class P>
+  const uint64_t* masks(detail::DevicePool& pool, size_t n) {
+    using Fr = typename P::Fr;
+    const UninitBuf<Fr> m = st.rand.template masking_field_elements_vec<Fr>(n);
+    uint64_t* d = pool.fresh(sizeof(Fr) * n);
+    if (n) check(csh_memcpy_h2d(d, m.p, sizeof(Fr) * n), "csh_memcpy_h2d");
+    return d;
+  }
+  template <class Fr>
+  std::vector<Fr> reshare(const std::vector<Fr>& half) {  // reshare_vec: -> {a = mine, b = the previous party's}
+    const size_t bytes = sizeof(Fr) * half.size();
+    Bytes b(bytes);
+    if (bytes) memcpy(b.data(), half.data(), bytes);
+    net.send((net.id() + 1) % 3, std::move(b));
+    const Bytes r = net.recv((net.id() + 2) % 3);
+    if (r.size() != bytes) throw Error("reshare_vec: invalid number of elements received");
+    std::vector<Fr> out(2 * half.size());
+    for (size_t i = 0; i < half.size(); ++i) {
+      out[2 * i] = half[i];
+      memcpy((void*)&out[2 * i + 1], r.data() + sizeof(Fr) * i, sizeof(Fr));
+    }
+    return out;
+  }
+  template <class P>
+  uint64_t* mul_many(detail::DevicePool& pool, const uint64_t* lhs, const uint64_t* rhs, size_t n) {
+    using Fr = typename P::Fr;
+    const uint64_t* mask = masks<P>(pool, n);
+    uint64_t* half = pool.fresh(sizeof(Fr) * n);
+    std::vector<Fr> h(n);
+    if (n) {
+      check(csh_rep3_local_mul_vec_dev(P::ID, lhs, rhs, mask, half, n, nullptr), "csh_rep3_local_mul_vec_dev");
+      check(csh_memcpy_d2h(h.data(), half, sizeof(Fr) * n), "csh_memcpy_d2h");
+    }
+    return pool.up(reshare(h));
+  }
+};
+
+constexpr size_t HONK_CO_POINTS = 7;  // batch elements per kept edge
+// cols: the 36 columns of csh_honk_sumcheck_accumulate_dev as the party holds them -- the 13 witness and shifted-witness columns as shares
+// (ncomp = PROTOCOL + 1 values per element), the 23 precomputed columns public. -> the eleven accumulators back to back as shares,
+// HONK_ACC_ELEMS * ncomp values. gs == nullptr: the factor one.
+template <class P, class Net>
+inline std::vector<typename P::Fr> co_compute_round_accumulators(Net& net, const std::vector<std::vector<typename P::Fr>>& cols, size_t edge_begin, size_t edge_end,
+                                                                 const HonkGateSeparator<typename P::Fr>* gs, const HonkRelationParameters<typename P::Fr>& params) {
+  using Fr = typename P::Fr;
+  const uint32_t protocol = Net::PROTOCOL, party = net.party();
+  const size_t ncomp = protocol + 1, edges = (edge_end - edge_begin) / 2;
+  if (cols.size() != HONK_SUMCHECK_COLUMNS) throw Error("co_compute_round_accumulators: 36 columns");
+  if ((edge_begin & 1) || (edge_end & 1) || edge_begin >= edge_end) throw Error("co_compute_round_accumulators: an even, non-empty range");
+  for (size_t c = 0; c < HONK_SUMCHECK_COLUMNS; ++c)
+    if (cols[c].size() < edge_end * (c < 13 ? ncomp : 1)) throw Error("co_compute_round_accumulators: a column is shorter than the range");
+  if (gs && (gs->log_num_monomials > 28 || gs->betas.size() < gs->log_num_monomials || ((edge_end >> 1) - 1) * gs->periodicity >= (size_t(1) << gs->log_num_monomials)))
+    throw Error("co_compute_round_accumulators: the gate separator's table is shorter than the range reads");
+  detail::DevicePool pool;
+  const uint64_t* dc[HONK_SUMCHECK_COLUMNS];
+  for (size_t c = 0; c < HONK_SUMCHECK_COLUMNS; ++c) dc[c] = pool.up(cols[c]);
+  uint64_t* table = nullptr;
+  const size_t stride = gs ? gs->periodicity : 1;
+  if (gs) {
+    table = pool.fresh(sizeof(Fr) << gs->log_num_monomials);
+    check(csh_honk_pow_table_dev(P::ID, (const uint64_t*)gs->betas.data(), gs->log_num_monomials, table, nullptr), "csh_honk_pow_table_dev");
+  }
+  const Fr pr[3] = {params.beta, params.gamma, params.public_input_delta};
+  const uint64_t* prm = (const uint64_t*)pr;
+  auto shares = [&](size_t vectors, size_t m) { return pool.fresh(sizeof(Fr) * vectors * HONK_CO_POINTS * m * ncomp); };
+  auto down = [&](const uint64_t* d, size_t count) {
+    std::vector<Fr> v(count);
+    check(csh_memcpy_d2h(v.data(), d, sizeof(Fr) * count), "csh_memcpy_d2h");
+    return v;
+  };
+  // fold_and_filter: the edges the arithmetic and the delta-range relation keep
+  uint32_t* list[2];
+  size_t kept[2];
+  for (int r = 0; r < 2; ++r) {
+    list[r] = (uint32_t*)pool.fresh(4 * edges);
+    uint32_t* count = (uint32_t*)pool.fresh(4);
+    check(csh_honk_co_select_edges_dev(P::ID, dc[r ? 20 : 19], edge_begin, edge_end, list[r], count, nullptr), "csh_honk_co_select_edges_dev");
+    uint32_t c = 0;
+    check(csh_memcpy_d2h(&c, count, 4), "csh_memcpy_d2h");
+    kept[r] = c;
+  }
+  std::vector<Fr> out, r0_half;  // out: everything behind arith.r0, which is reshared last
+  out.reserve(HONK_ACC_ELEMS * ncomp);
+  auto append = [&](const std::vector<Fr>& v) { out.insert(out.end(), v.begin(), v.end()); };
+  {  // UltraArithmeticRelation
+    const uint64_t* mask = protocol == 1 ? net.template masks<P>(pool, HONK_CO_POINTS * kept[0]) : nullptr;
+    uint64_t *r0 = pool.fresh(sizeof(Fr) * 6), *r1 = pool.fresh(sizeof(Fr) * 5 * ncomp);
+    check(csh_honk_co_arith_dev(P::ID, protocol, party, dc, edge_begin, edge_end, list[0], kept[0], table, stride, mask, r0, r1, nullptr), "csh_honk_co_arith_dev");
+    r0_half = down(r0, 6);
+    append(down(r1, 5 * ncomp));
+  }
+  {  // UltraPermutationRelation: never skipped
+    const size_t n7 = HONK_CO_POINTS * edges, half = 2 * n7 * ncomp * 4;  // words of half the first product
+    uint64_t *lhs = shares(4, edges), *rhs = shares(4, edges), *rhs2 = shares(2, edges), *acc = pool.fresh(sizeof(Fr) * 9 * ncomp);
+    check(csh_honk_co_perm_operands_dev(P::ID, protocol, party, dc, edge_begin, edge_end, nullptr, edges, prm, lhs, rhs, nullptr), "csh_honk_co_perm_operands_dev");
+    const uint64_t* mul1 = net.template mul_many<P>(pool, lhs, rhs, 4 * n7);
+    const uint64_t* num_den = net.template mul_many<P>(pool, mul1, mul1 + half, 2 * n7);
+    check(csh_honk_co_perm_operands2_dev(P::ID, protocol, party, dc, edge_begin, edge_end, nullptr, edges, prm, rhs2, nullptr), "csh_honk_co_perm_operands2_dev");
+    const uint64_t* prod = net.template mul_many<P>(pool, num_den, rhs2, 2 * n7);
+    check(csh_honk_co_perm_finish_dev(P::ID, protocol, party, dc, edge_begin, edge_end, nullptr, edges, table, stride, prod, acc, nullptr), "csh_honk_co_perm_finish_dev");
+    append(down(acc, 9 * ncomp));
+  }
+  std::vector<Fr> delta;
+  {  // DeltaRangeConstraintRelation
+    const size_t m = kept[1], n7 = HONK_CO_POINTS * m;
+    uint64_t* acc = pool.fresh(sizeof(Fr) * 24 * ncomp);
+    const uint64_t* mul = nullptr;
+    if (m) {
+      uint64_t* lhs = shares(8, m);
+      check(csh_honk_co_delta_operands_dev(P::ID, protocol, party, dc, edge_begin, edge_end, list[1], m, lhs, nullptr), "csh_honk_co_delta_operands_dev");
+      uint64_t* sqr = net.template mul_many<P>(pool, lhs, lhs, 8 * n7);
+      check(csh_honk_co_delta_sub_one_dev(P::ID, protocol, party, sqr, m, nullptr), "csh_honk_co_delta_sub_one_dev");
+      mul = net.template mul_many<P>(pool, sqr, sqr + 4 * n7 * ncomp * 4, 4 * n7);
+    }
+    check(csh_honk_co_delta_finish_dev(P::ID, protocol, party, dc, edge_begin, edge_end, list[1], m, table, stride, mul, acc, nullptr), "csh_honk_co_delta_finish_dev");
+    delta = down(acc, 24 * ncomp);
+  }
+  {  // LogDerivLookupRelation: never skipped
+    const size_t n7 = HONK_CO_POINTS * edges;
+    uint64_t *read_term = shares(1, edges), *inverses = shares(1, edges), *lhs = shares(2, edges), *rhs = shares(2, edges);
+    uint64_t *r0 = pool.fresh(sizeof(Fr) * 5 * ncomp), *acc = pool.fresh(sizeof(Fr) * 8 * ncomp);
+    check(csh_honk_co_lookup_operands_dev(P::ID, protocol, party, dc, edge_begin, edge_end, nullptr, edges, prm, read_term, inverses, nullptr), "csh_honk_co_lookup_operands_dev");
+    const uint64_t* write_inverse = net.template mul_many<P>(pool, read_term, inverses, n7);
+    check(csh_honk_co_lookup_mid_dev(P::ID, protocol, party, dc, edge_begin, edge_end, nullptr, edges, table, stride, prm, write_inverse, r0, lhs, rhs, nullptr),
+          "csh_honk_co_lookup_mid_dev");
+    const uint64_t* mul = net.template mul_many<P>(pool, lhs, rhs, 2 * n7);
+    check(csh_honk_co_lookup_finish_dev(P::ID, protocol, party, dc, edge_begin, edge_end, nullptr, edges, table, stride, prm, mul, acc, nullptr), "csh_honk_co_lookup_finish_dev");
+    append(down(r0, 5 * ncomp));
+    append(down(acc, 8 * ncomp));
+  }
+  append(delta);
+  // AllRelationAccHalfShared::reshare (relations/mod.rs:140-162, co_sumcheck_round.rs:292): the one network message of arith.r0, behind
+  // every relation's rounds as in the reference
+  std::vector<Fr> all = net.reshare(r0_half);
+  all.insert(all.end(), out.begin(), out.end());
+  return all;
+}
+// batch_over_relations_univariates on one party's shares (co_sumcheck_round.rs:121-138): scale and extend_and_batch_univariates are linear
+// in the shares with public coefficients and no public addend, so component by component. -> the 8 shares of the round univariate
+template <class Fr>
+inline std::vector<Fr> co_batch_over_relations(const std::vector<Fr>& acc, size_t ncomp, const std::vector<Fr>& alphas, const HonkGateSeparator<Fr>& gs) {
+  if (acc.size() != HONK_ACC_ELEMS * ncomp) throw Error("co_batch_over_relations: 57 shares");
+  std::vector<Fr> out(HONK_BATCHED_RELATION_PARTIAL_LENGTH * ncomp);
+  for (size_t c = 0; c < ncomp; ++c) {
+    HonkAccumulators<Fr> one;
+    for (size_t i = 0; i < HONK_ACC_ELEMS; ++i) one[i] = acc[i * ncomp + c];
+    const auto res = detail::honk_batch_over_relations(one, alphas, gs);
+    for (size_t i = 0; i < res.size(); ++i) out[i * ncomp + c] = res[i];
+  }
+  return out;
+}
+
 }  // namespace cosnarks

@@ -593,6 +593,98 @@ int csh_honk_sumcheck_accumulate_gates_dev(csh_curve_t field_of, const uint64_t*
 int csh_honk_pow_table_dev(csh_curve_t field_of, const uint64_t* betas /* host, m elements */, size_t m, uint64_t* out_dev /* 2^m elements */,
                            void* stream);
 
+/* ---- co-noir UltraHonk, the sumcheck round on shares: the stretches between the network rounds of four relations ----
+ * The collaborative prover's form of the round above (co-noir/co-ultrahonk/src/co_decider/; paths below are relative to it) for the
+ * arithmetic, permutation, delta-range and log-derivative lookup relations, subrelations 0 .. 10. There a relation is evaluated over a flat
+ * batch of 7 m elements per column (m = the kept edges) and calls T::mul_many -- a local product plus one network round -- between
+ * stretches of local arithmetic. One entry per stretch; the network stays the caller's: the local product is csh_rep3_local_mul_vec_dev
+ * (Rep3) or csh_vec_mul_dev (Shamir, plain), the exchange is the driver's.
+ * protocol, party_id and x (+) v are those of the Oink section. cols_dev[0..36) is the column array of csh_honk_sumcheck_accumulate_dev in
+ * the same order: the 13 witness and shifted-witness columns are shares (ncomp = protocol + 1 values per element), the 23 precomputed
+ * columns are public; a pointer may be NULL for a column the stage does not read (each entry lists what it reads).
+ * The batch is never built: batch element t of a column belongs to kept edge j = t / 7 and point k = t % 7 and is
+ * col[e] + k (col[e + 1] - col[e]) per component, with e = 2 edge_idx_dev[j], or e = edge_begin + 2 j when edge_idx_dev is NULL (every edge
+ * of the range kept, m = (edge_end - edge_begin) / 2). Its scaling element is scaling_dev[(e >> 1) scaling_stride], or one when scaling_dev
+ * is NULL. This is extend_edges + fold_and_filter + add_entities (co_sumcheck/co_sumcheck_round.rs:54-73, types_batch.rs:105-130,
+ * relations/mod.rs:69-80). CONTRACT: the m values of an edge list lie in [edge_begin / 2, edge_end / 2) -- it is what
+ * csh_honk_co_select_edges_dev wrote for the same range.
+ * An operand vector holds its parts back to back in the reference's concatenation order, 7 m shares each: the order is part of the ABI,
+ * as it is what a reference CPU party puts on the wire.
+ * An accumulator is fold_accumulator! (relations/mod.rs:45-57) into zero: entry k = the sum over j of element 7 j + k, cut to the
+ * accumulator's length, ncomp values per entry; every entry is written, with m = 0 as zero. The caller adds the accumulators of successive
+ * batches (MAX_ROUND_SIZE_PER_BATCH, co_sumcheck_round.rs:270-291). Reductions go through LDS and a finishing launch, with the exact
+ * modular addition: the words do not depend on the launch shape. Outputs are canonical. Stream-ordered, no host synchronisation, scratch
+ * from the stream's workspace. edge_begin and edge_end are even, edge_begin < edge_end <= 2^28. params = beta, gamma, public_input_delta on
+ * the host. CSH_ERR_INVALID before any device work: the causes of csh_honk_sumcheck_accumulate_dev and of the Oink entries, an m that does
+ * not fit the range, and an output that overlaps an input or another output. */
+/* can_skip of the two relations that have one: selector_dev = q_arith (relations/ultra_arithmetic_relation.rs:247-249) or q_delta_range
+ * (delta_range_constraint_relation.rs:94-96). An edge is kept unless the selector is zero at both ends. edge_idx_dev receives the kept
+ * e >> 1 ascending (room for (edge_end - edge_begin) / 2 values; the compaction is stable, the order being the wire order), *count_dev
+ * their number, which the caller copies back. Permutation and lookup never skip in the shared prover: they pass no list. */
+int csh_honk_co_select_edges_dev(csh_curve_t field_of, const uint64_t* selector_dev, size_t edge_begin, size_t edge_end, uint32_t* edge_idx_dev,
+                                 uint32_t* count_dev, void* stream);
+/* UltraArithmeticRelation, relations/ultra_arithmetic_relation.rs:88-239, one stage, no network. r0_dev: 6 elements of ONE component, a
+ * half share: local_mul_vec(w_l, w_r) (Rep3: + mask_dev[t], 7 m elements indexed by the batch element t as the reference draws them,
+ * the elements at k = 6 included; protocol 0: the product of the shares, mask_dev NULL) times q_m (q_arith - 3) (-1/2), plus
+ * mul_with_public_to_half_share (q w.a) of q_l w_l, q_r w_r, q_o w_o, q_4 w_4 and (q_arith - 1) w_4_shift, plus q_c
+ * (add_assign_public_half_share: protocol 0, and Rep3 party 0 only), times q_arith and the scaling. The caller reshares r0
+ * (relations/mod.rs:140-162). r1_dev: 5 shares, ((w_l + w_4 - w_l_shift) (+) q_m) (q_arith - 2) (q_arith - 1) q_arith scaling.
+ * Reads w_l, w_r, w_o, w_4, w_l_shift, w_4_shift, q_m, q_c, q_l, q_r, q_o, q_4, q_arith. */
+int csh_honk_co_arith_dev(csh_curve_t field_of, uint32_t protocol, uint32_t party_id, const uint64_t* const* cols_dev, size_t edge_begin,
+                          size_t edge_end, const uint32_t* edge_idx_dev, size_t m, const uint64_t* scaling_dev, size_t scaling_stride,
+                          const uint64_t* mask_dev, uint64_t* r0_dev, uint64_t* r1_dev, void* stream);
+/* UltraPermutationRelation stage (a), relations/permutation_relation.rs:70-146. With wid_k = w_k (+) (beta id_k + gamma) and
+ * wsigma_k = w_k (+) (beta sigma_k + gamma): lhs_dev = [wid_1 | wsigma_1 | wid_3 | wsigma_3], rhs_dev = [wid_2 | wsigma_2 | wid_4 |
+ * wsigma_4], 4 * 7 m shares each. The caller runs mul_many(lhs, rhs), then mul_many of the two halves of the result: [numerator |
+ * denominator] (:147-149). Reads w_l, w_r, w_o, w_4, sigma_1..4, id_1..4. */
+int csh_honk_co_perm_operands_dev(csh_curve_t field_of, uint32_t protocol, uint32_t party_id, const uint64_t* const* cols_dev, size_t edge_begin,
+                                  size_t edge_end, const uint32_t* edge_idx_dev, size_t m, const uint64_t* params, uint64_t* lhs_dev,
+                                  uint64_t* rhs_dev, void* stream);
+/* Stage (b), :226-234: rhs_dev = [z_perm (+) lagrange_first | z_perm_shift (+) lagrange_last public_input_delta], 2 * 7 m shares. The
+ * caller runs mul_many([numerator | denominator], rhs). Reads z_perm, z_perm_shift, lagrange_first, lagrange_last. */
+int csh_honk_co_perm_operands2_dev(csh_curve_t field_of, uint32_t protocol, uint32_t party_id, const uint64_t* const* cols_dev, size_t edge_begin,
+                                   size_t edge_end, const uint32_t* edge_idx_dev, size_t m, const uint64_t* params, uint64_t* rhs_dev,
+                                   void* stream);
+/* Stage (c), :235-246: prod_dev = that product, 2 * 7 m shares. acc_dev[0..9) shares: perm.r0 (6) = the fold of (first half - second
+ * half) scaling, perm.r1 (3) = the fold of lagrange_last z_perm_shift scaling. Reads z_perm_shift, lagrange_last. */
+int csh_honk_co_perm_finish_dev(csh_curve_t field_of, uint32_t protocol, uint32_t party_id, const uint64_t* const* cols_dev, size_t edge_begin,
+                                size_t edge_end, const uint32_t* edge_idx_dev, size_t m, const uint64_t* scaling_dev, size_t scaling_stride,
+                                const uint64_t* prod_dev, uint64_t* acc_dev, void* stream);
+/* DeltaRangeConstraintRelation stage (a), relations/delta_range_constraint_relation.rs:146-177. With D_1 = w_r - w_l, D_2 = w_o - w_r,
+ * D_3 = w_4 - w_o, D_4 = w_l_shift - w_4: lhs_dev = [D_1 (+) -1 | D_2 (+) -1 | D_3 (+) -1 | D_4 (+) -1 | D_1 (+) -2 | .. | D_4 (+) -2],
+ * 8 * 7 m shares. The caller squares it: mul_many(lhs, lhs). Reads w_l, w_r, w_o, w_4, w_l_shift. */
+int csh_honk_co_delta_operands_dev(csh_curve_t field_of, uint32_t protocol, uint32_t party_id, const uint64_t* const* cols_dev, size_t edge_begin,
+                                   size_t edge_end, const uint32_t* edge_idx_dev, size_t m, uint64_t* lhs_dev, void* stream);
+/* Stage (b), :181-183: add_assign_public(-1) on each of the 8 * 7 m shares of sqr_dev, in place. The caller multiplies the two halves.
+ * Reads no column; m <= 2^27. */
+int csh_honk_co_delta_sub_one_dev(csh_curve_t field_of, uint32_t protocol, uint32_t party_id, uint64_t* sqr_dev, size_t m, void* stream);
+/* Stage (c), :187-214: mul_dev = that product, 4 * 7 m shares; every quarter is multiplied by q_delta_range and by the scaling (both
+ * cycled over the quarters) and quarter i folds into delta.r_i: acc_dev[0..24) shares, 6 each. Reads q_delta_range. */
+int csh_honk_co_delta_finish_dev(csh_curve_t field_of, uint32_t protocol, uint32_t party_id, const uint64_t* const* cols_dev, size_t edge_begin,
+                                 size_t edge_end, const uint32_t* edge_idx_dev, size_t m, const uint64_t* scaling_dev, size_t scaling_stride,
+                                 const uint64_t* mul_dev, uint64_t* acc_dev, void* stream);
+/* LogDerivLookupRelation stage (a), relations/logderiv_lookup_relation.rs:92-139, :263-271: read_term_dev = (q_r w_l_shift + w_l) (+) gamma
+ * + beta (q_m w_r_shift + w_r) + beta^2 (q_c w_o_shift + w_o) (+) beta^3 q_o, and inverses_dev = the extended lookup_inverses, so that the
+ * product's second operand exists in memory; 7 m shares each. The caller runs mul_many(read_term, inverses) = write_inverse.
+ * Reads w_l, w_r, w_o, their shifts, q_r, q_m, q_c, q_o, lookup_inverses. */
+int csh_honk_co_lookup_operands_dev(csh_curve_t field_of, uint32_t protocol, uint32_t party_id, const uint64_t* const* cols_dev, size_t edge_begin,
+                                    size_t edge_end, const uint32_t* edge_idx_dev, size_t m, const uint64_t* params, uint64_t* read_term_dev,
+                                    uint64_t* inverses_dev, void* stream);
+/* Stage (b), :77-90, :142-168, :277-295: r0_dev (5 shares) = the fold of (write_term write_inverse - inverse_exists) scaling with
+ * write_term = table_1 + gamma + beta table_2 + beta^2 table_3 + beta^3 table_4 and inverse_exists = (tag - q_lookup tag) (+) q_lookup;
+ * lhs_dev = [write_inverse | read_tag], rhs_dev = [read_counts | read_tag], 2 * 7 m shares each. The caller runs mul_many(lhs, rhs).
+ * Reads table_1..4, lookup_read_tags, lookup_read_counts, q_lookup. */
+int csh_honk_co_lookup_mid_dev(csh_curve_t field_of, uint32_t protocol, uint32_t party_id, const uint64_t* const* cols_dev, size_t edge_begin,
+                               size_t edge_end, const uint32_t* edge_idx_dev, size_t m, const uint64_t* scaling_dev, size_t scaling_stride,
+                               const uint64_t* params, const uint64_t* write_inverse_dev, uint64_t* r0_dev, uint64_t* lhs_dev, uint64_t* rhs_dev,
+                               void* stream);
+/* Stage (c), :272, :296-309: mul_dev = that product, 2 * 7 m shares. acc_dev[0..8) shares: lookup.r1 (5) = the fold of q_lookup
+ * write_term lookup_inverses - mul[0] with NO scaling (the linearly dependent subrelation), lookup.r2 (3) = the fold of (mul[1] -
+ * read_tag) scaling. Reads table_1..4, q_lookup, lookup_inverses, lookup_read_tags. */
+int csh_honk_co_lookup_finish_dev(csh_curve_t field_of, uint32_t protocol, uint32_t party_id, const uint64_t* const* cols_dev, size_t edge_begin,
+                                  size_t edge_end, const uint32_t* edge_idx_dev, size_t m, const uint64_t* scaling_dev, size_t scaling_stride,
+                                  const uint64_t* params, const uint64_t* mul_dev, uint64_t* acc_dev, void* stream);
+
 /* Rep3 correlated masks generated on the device ("next" row f2): out[i] = from_be_bytes_mod_order(a_i) -
  * from_be_bytes_mod_order(b_i), a_i / b_i = the 32-byte chunks number elem_offset{1,2} + i of the ChaCha12 keystreams
  * of seed1 (own key) and seed2 (previous party's key): byte-compatible with Rep3Rand::masking_field_elements_vec
