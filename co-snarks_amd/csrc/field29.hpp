@@ -172,10 +172,16 @@ using Fq29 = FpLazy<Bn254Fq29Params, Bn254Fq>;
 //   CSH_CHECK_BOUNDS_DEVICE (selftest_dev.hip): device code RECORDS and goes on -- the lane-distributed arithmetic
 //   (curve_quad.hpp, curve_pair.hpp) exists on the device only. g_bound_record[0] counts the violating limbs, [1] keeps the
 //   largest offender as |limb| << 16 | site (site = the line of this file that states the violated bound); plain vector
-//   atomics, no trap, no print. The entry points of selftest_dev.hip copy the record back and clear it.
+//   atomics, no trap, no print. The entry points of selftest_dev.hip copy the record back and clear it. A second checked unit
+//   (selftest_ntt_dev.hip) names its own record with CSH_BOUND_RECORD: a code object sees only its own unit's variable.
 // Everywhere else the macro is empty.
+// CSH_SCALAR_BOUND(v, bound, what): the same contract for a scalar whose range no limb check can see (fold_top()'s quotient
+// estimate), same record format (the violating |v| in place of the limb).
 #if defined(CSH_CHECK_BOUNDS_DEVICE)
-__device__ unsigned long long g_bound_record[2];
+#ifndef CSH_BOUND_RECORD
+#define CSH_BOUND_RECORD g_bound_record
+#endif
+__device__ unsigned long long CSH_BOUND_RECORD[2];
 #endif
 #if defined(CSH_CHECK_BOUNDS_DEVICE) && defined(__HIP_DEVICE_COMPILE__)
 #define CSH_LIMB_BOUND(x, bound, what)                                                        \
@@ -184,9 +190,18 @@ __device__ unsigned long long g_bound_record[2];
       const int64_t v__ = (x).l[i__];                                                         \
       const int64_t a__ = v__ < 0 ? -v__ : v__;                                               \
       if (a__ > (int64_t)(bound)) {                                                           \
-        atomicAdd(&g_bound_record[0], 1ull);                                                  \
-        atomicMax(&g_bound_record[1], ((unsigned long long)a__ << 16) | (unsigned long long)(__LINE__ & 0xffff)); \
+        atomicAdd(&CSH_BOUND_RECORD[0], 1ull);                                                \
+        atomicMax(&CSH_BOUND_RECORD[1], ((unsigned long long)a__ << 16) | (unsigned long long)(__LINE__ & 0xffff)); \
       }                                                                                       \
+    }                                                                                         \
+  } while (0)
+#define CSH_SCALAR_BOUND(v, bound, what)                                                      \
+  do {                                                                                        \
+    const int64_t v__ = (v);                                                                  \
+    const int64_t a__ = v__ < 0 ? -v__ : v__;                                                 \
+    if (a__ > (int64_t)(bound)) {                                                             \
+      atomicAdd(&CSH_BOUND_RECORD[0], 1ull);                                                  \
+      atomicMax(&CSH_BOUND_RECORD[1], ((unsigned long long)a__ << 16) | (unsigned long long)(__LINE__ & 0xffff)); \
     }                                                                                         \
   } while (0)
 #elif defined(CSH_CHECK_BOUNDS) && !defined(__HIP_DEVICE_COMPILE__)
@@ -202,8 +217,17 @@ __device__ unsigned long long g_bound_record[2];
       }                                                                                       \
     }                                                                                         \
   } while (0)
+#define CSH_SCALAR_BOUND(v, bound, what)                                                      \
+  do {                                                                                        \
+    const int64_t v__ = (v);                                                                  \
+    if (v__ > (int64_t)(bound) || v__ < -(int64_t)(bound)) {                                  \
+      fprintf(stderr, "FpS bound violation in %s: %lld exceeds %lld\n", what, (long long)v__, (long long)(bound)); \
+      abort();                                                                                \
+    }                                                                                         \
+  } while (0)
 #else
 #define CSH_LIMB_BOUND(x, bound, what) do { } while (0)
+#define CSH_SCALAR_BOUND(v, bound, what) do { } while (0)
 #endif
 // the same for the per-column routines of the product-scanning form: a product visits them 2 NL times with the same operands
 #define CSH_LIMB_BOUND_COL(k, x, bound, what) do { if ((k) == 0) CSH_LIMB_BOUND(x, bound, what); } while (0)
@@ -770,6 +794,7 @@ struct FpS {
     r.l[NL - 1] = l[NL - 1] + c;
     const float inv_t = 1.0f / (float)(LP::MOD[NL - 1] + 1u);
     const int32_t k = (int32_t)floorf((float)r.l[NL - 1] * inv_t);
+    CSH_SCALAR_BOUND(k, 64, "fold_top(k)");
     int64_t cc = 0;
 #pragma unroll
     for (int i = 0; i < NL - 1; ++i) {
