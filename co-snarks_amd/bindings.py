@@ -752,11 +752,13 @@ class HonkCoBatch:
     the stage does not read), the range, the kept edges (edge_idx = the DeviceBuffer of honk_co_select_edges with m = its count, or None
     for every edge of the range), the scaling table and the host parameters beta, gamma, public_input_delta. The column count and the
     range rules are checked here, before any call."""
+    COLUMNS = HONK_SUMCHECK_COLUMNS
+    PARAMS = (3, "beta, gamma, public_input_delta")
 
     def __init__(self, curve: int, protocol: int, party: int, cols, edge_begin: int, edge_end: int, edge_idx=None, m=None, scaling=None,
                  scaling_stride: int = 1, params=None):
-        if len(cols) != HONK_SUMCHECK_COLUMNS:
-            raise CoSnarksHipError("honk_co: %d columns, not %d" % (len(cols), HONK_SUMCHECK_COLUMNS))
+        if len(cols) != self.COLUMNS:
+            raise CoSnarksHipError("honk_co: %d columns, not %d" % (len(cols), self.COLUMNS))
         if protocol not in (0, 1) or party not in (0, 1, 2):
             raise CoSnarksHipError("honk_co: protocol must be 0 (plain / Shamir) or 1 (Rep3), party 0, 1 or 2")
         if edge_begin < 0 or edge_begin % 2 or edge_end % 2 or not edge_begin < edge_end <= HONK_MAX_EDGE_END:
@@ -770,8 +772,8 @@ class HonkCoBatch:
         self.curve, self.protocol, self.party, self.cols, self.edge_begin, self.edge_end = curve, protocol, party, list(cols), edge_begin, edge_end
         self.edge_idx, self.m, self.scaling, self.scaling_stride = edge_idx, m, scaling, scaling_stride
         self.params = _u64(params) if params is not None else None
-        if self.params is not None and self.params.size != 12:
-            raise CoSnarksHipError("honk_co: params are beta, gamma, public_input_delta (3 elements of 4 words)")
+        if self.params is not None and self.params.size != 4 * self.PARAMS[0]:
+            raise CoSnarksHipError("honk_co: params are %s (%d elements of 4 words)" % (self.PARAMS[1], self.PARAMS[0]))
         self.ncomp = protocol + 1
 
     def common(self):
@@ -879,6 +881,106 @@ def honk_co_lookup_finish(b: HonkCoBatch, mul, acc=None, stream=None):
     """csh_honk_co_lookup_finish_dev: mul = 2 * 7 m shares -> acc = lookup.r1 (5 shares, no scaling), lookup.r2 (3 shares)"""
     acc = acc if acc is not None else b.acc(8)
     _check(lib().csh_honk_co_lookup_finish_dev(*b.common(), *b.scaled(), _p(b.params), _devptr(mul), _devptr(acc), _stream(stream)))
+    return acc
+
+
+# ---- the five gate relations on shares (csrc/honk_co_gates.hip): one wrapper per entry of include/cosnarks_hip.h ----------------------
+class HonkCoGatesBatch(HonkCoBatch):
+    """HonkCoBatch over the 19 columns of honk_sumcheck_accumulate_gates (eight share columns, eleven public ones) and its eight host
+    parameters eta_1, eta_2, eta_3, curve_b, mat_internal_diag_m_1[0..4); edge_idx = the list of honk_co_select_edges on the relation's
+    own selector. The same checks, before any call."""
+    COLUMNS = HONK_GATES_COLUMNS
+    PARAMS = (HONK_GATES_PARAMS, "eta_1, eta_2, eta_3, curve_b, mat_internal_diag_m_1[0..4)")
+
+    def need_params(self, what):
+        if self.params is None:
+            raise CoSnarksHipError("%s: the batch has no params" % what)
+        return _p(self.params)
+
+
+def honk_co_ell_operands(b: HonkCoGatesBatch, lhs=None, rhs=None, stream=None):
+    """csh_honk_co_ell_operands_dev -> (lhs, rhs), 7 * 7 m shares each"""
+    lhs = lhs if lhs is not None else b.shares(7)
+    rhs = rhs if rhs is not None else b.shares(7)
+    _check(lib().csh_honk_co_ell_operands_dev(*b.common(), _devptr(lhs), _devptr(rhs), _stream(stream)))
+    return lhs, rhs
+
+
+def honk_co_ell_operands2(b: HonkCoGatesBatch, mul1, lhs=None, rhs=None, stream=None):
+    """csh_honk_co_ell_operands2_dev: mul1 = 7 * 7 m shares -> (lhs, rhs), 5 * 7 m shares each"""
+    par = b.need_params("honk_co_ell_operands2")
+    lhs = lhs if lhs is not None else b.shares(5)
+    rhs = rhs if rhs is not None else b.shares(5)
+    _check(lib().csh_honk_co_ell_operands2_dev(*b.common(), par, _devptr(mul1), _devptr(lhs), _devptr(rhs), _stream(stream)))
+    return lhs, rhs
+
+
+def honk_co_ell_finish(b: HonkCoGatesBatch, mul1, mul2, acc=None, stream=None):
+    """csh_honk_co_ell_finish_dev: mul1 = 7 * 7 m shares, mul2 = 5 * 7 m shares -> acc = elliptic.r0, r1 (6 shares each)"""
+    acc = acc if acc is not None else b.acc(12)
+    _check(lib().csh_honk_co_ell_finish_dev(*b.common(), *b.scaled(), _devptr(mul1), _devptr(mul2), _devptr(acc), _stream(stream)))
+    return acc
+
+
+def honk_co_mem_operands(b: HonkCoGatesBatch, lhs=None, rhs=None, rhs2=None, stream=None):
+    """csh_honk_co_mem_operands_dev -> (lhs, rhs: 6 * 7 m shares each; rhs2: 7 m shares)"""
+    par = b.need_params("honk_co_mem_operands")
+    lhs = lhs if lhs is not None else b.shares(6)
+    rhs = rhs if rhs is not None else b.shares(6)
+    rhs2 = rhs2 if rhs2 is not None else b.shares(1)
+    _check(lib().csh_honk_co_mem_operands_dev(*b.common(), par, _devptr(lhs), _devptr(rhs), _devptr(rhs2), _stream(stream)))
+    return lhs, rhs, rhs2
+
+
+def honk_co_mem_finish(b: HonkCoGatesBatch, mul, mul2, acc=None, stream=None):
+    """csh_honk_co_mem_finish_dev: mul = 6 * 7 m shares, mul2 = 7 m shares -> acc = memory.r0 .. r5 (6 shares each)"""
+    par = b.need_params("honk_co_mem_finish")
+    acc = acc if acc is not None else b.acc(36)
+    _check(lib().csh_honk_co_mem_finish_dev(*b.common(), *b.scaled(), par, _devptr(mul), _devptr(mul2), _devptr(acc), _stream(stream)))
+    return acc
+
+
+def honk_co_nnf_operands(b: HonkCoGatesBatch, lhs=None, rhs=None, stream=None):
+    """csh_honk_co_nnf_operands_dev -> (lhs, rhs), 5 * 7 m shares each"""
+    lhs = lhs if lhs is not None else b.shares(5)
+    rhs = rhs if rhs is not None else b.shares(5)
+    _check(lib().csh_honk_co_nnf_operands_dev(*b.common(), _devptr(lhs), _devptr(rhs), _stream(stream)))
+    return lhs, rhs
+
+
+def honk_co_nnf_finish(b: HonkCoGatesBatch, mul, acc=None, stream=None):
+    """csh_honk_co_nnf_finish_dev: mul = 5 * 7 m shares -> acc = nnf.r0 (6 shares)"""
+    acc = acc if acc is not None else b.acc(6)
+    _check(lib().csh_honk_co_nnf_finish_dev(*b.common(), *b.scaled(), _devptr(mul), _devptr(acc), _stream(stream)))
+    return acc
+
+
+def honk_co_pos_ext_operands(b: HonkCoGatesBatch, s=None, stream=None):
+    """csh_honk_co_pos_ext_operands_dev -> s, 4 * 7 m shares"""
+    s = s if s is not None else b.shares(4)
+    _check(lib().csh_honk_co_pos_ext_operands_dev(*b.common(), _devptr(s), _stream(stream)))
+    return s
+
+
+def honk_co_pos_ext_finish(b: HonkCoGatesBatch, u, acc=None, stream=None):
+    """csh_honk_co_pos_ext_finish_dev: u = s^5, 4 * 7 m shares -> acc = poseidon2_external.r0 .. r3 (7 shares each)"""
+    acc = acc if acc is not None else b.acc(28)
+    _check(lib().csh_honk_co_pos_ext_finish_dev(*b.common(), *b.scaled(), _devptr(u), _devptr(acc), _stream(stream)))
+    return acc
+
+
+def honk_co_pos_int_operands(b: HonkCoGatesBatch, s1=None, stream=None):
+    """csh_honk_co_pos_int_operands_dev -> s1, 7 m shares"""
+    s1 = s1 if s1 is not None else b.shares(1)
+    _check(lib().csh_honk_co_pos_int_operands_dev(*b.common(), _devptr(s1), _stream(stream)))
+    return s1
+
+
+def honk_co_pos_int_finish(b: HonkCoGatesBatch, u1, acc=None, stream=None):
+    """csh_honk_co_pos_int_finish_dev: u1 = s1^5, 7 m shares -> acc = poseidon2_internal.r0 .. r3 (7 shares each)"""
+    par = b.need_params("honk_co_pos_int_finish")
+    acc = acc if acc is not None else b.acc(28)
+    _check(lib().csh_honk_co_pos_int_finish_dev(*b.common(), *b.scaled(), par, _devptr(u1), _devptr(acc), _stream(stream)))
     return acc
 
 

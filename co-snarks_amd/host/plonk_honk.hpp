@@ -1499,6 +1499,213 @@ struct HonkCoRep3Net {
 };
 
 constexpr size_t HONK_CO_POINTS = 7;  // batch elements per kept edge
+namespace detail {
+// What the relations of one party's batch share -- the network policy, the device columns, the range, the gate separator's table -- and
+// one method per relation: its device stages with T::mul_many between them. A method returns the relation's accumulators as shares.
+// up36 / up19 upload the columns of the first four relations (csh_honk_sumcheck_accumulate_dev's order) and of the five gate relations
+// (csh_honk_sumcheck_accumulate_gates_dev's order); a relation is called only after the upload it reads.
+template <class P, class Net>
+struct HonkCoRound {
+  using Fr = typename P::Fr;
+  Net& net;
+  const uint32_t protocol, party;
+  const size_t ncomp, edge_begin, edge_end, edges;
+  const char* what;
+  DevicePool pool;
+  const uint64_t* dc[HONK_SUMCHECK_COLUMNS] = {};
+  const uint64_t* dg[HONK_GATES_COLUMNS] = {};
+  uint64_t* table = nullptr;
+  size_t stride = 1;
+  Fr pr[3], gp[8];
+
+  HonkCoRound(Net& n, size_t b, size_t e, const HonkGateSeparator<Fr>* gs, const char* w)
+      : net(n), protocol(Net::PROTOCOL), party(n.party()), ncomp(Net::PROTOCOL + 1), edge_begin(b), edge_end(e), edges((e - b) / 2), what(w) {
+    if ((edge_begin & 1) || (edge_end & 1) || edge_begin >= edge_end) fail("an even, non-empty range");
+    if (gs && (gs->log_num_monomials > 28 || gs->betas.size() < gs->log_num_monomials || ((edge_end >> 1) - 1) * gs->periodicity >= (size_t(1) << gs->log_num_monomials)))
+      fail("the gate separator's table is shorter than the range reads");
+    if (gs) {
+      stride = gs->periodicity;
+      table = pool.fresh(sizeof(Fr) << gs->log_num_monomials);
+      check(csh_honk_pow_table_dev(P::ID, (const uint64_t*)gs->betas.data(), gs->log_num_monomials, table, nullptr), "csh_honk_pow_table_dev");
+    }
+  }
+  [[noreturn]] void fail(const char* why) const { throw Error(std::string(what) + ": " + why); }
+  // `shared` leading columns hold ncomp values per element
+  void up(const std::vector<std::vector<Fr>>& cols, size_t count, size_t shared, const uint64_t** d, const char* columns) {
+    if (cols.size() != count) fail(columns);
+    for (size_t c = 0; c < count; ++c)
+      if (cols[c].size() < edge_end * (c < shared ? ncomp : 1)) fail("a column is shorter than the range");
+    for (size_t c = 0; c < count; ++c) d[c] = pool.up(cols[c]);
+  }
+  void up36(const std::vector<std::vector<Fr>>& cols, const HonkRelationParameters<Fr>& params) {
+    up(cols, HONK_SUMCHECK_COLUMNS, 13, dc, "36 columns");
+    pr[0] = params.beta, pr[1] = params.gamma, pr[2] = params.public_input_delta;
+  }
+  void up19(const std::vector<std::vector<Fr>>& cols, const HonkGateParameters<Fr>& g) {
+    up(cols, HONK_GATES_COLUMNS, 8, dg, "19 gate columns");
+    gp[0] = g.eta_1, gp[1] = g.eta_2, gp[2] = g.eta_3, gp[3] = g.curve_b;
+    for (size_t i = 0; i < 4; ++i) gp[4 + i] = g.mat_internal_diag_m_1[i];
+  }
+  const uint64_t* prm() const { return (const uint64_t*)pr; }
+  const uint64_t* gprm() const { return (const uint64_t*)gp; }
+  uint64_t* shares(size_t vectors, size_t m) { return pool.fresh(sizeof(Fr) * vectors * HONK_CO_POINTS * m * ncomp); }
+  uint64_t* acc_shares(size_t elems) { return pool.fresh(sizeof(Fr) * elems * ncomp); }
+  std::vector<Fr> down(const uint64_t* d, size_t count) {
+    std::vector<Fr> v(count);
+    check(csh_memcpy_d2h(v.data(), d, sizeof(Fr) * count), "csh_memcpy_d2h");
+    return v;
+  }
+  // part q of a device vector of 7 m shares per part
+  const uint64_t* part(const uint64_t* v, size_t q, size_t m) const { return v + q * HONK_CO_POINTS * m * ncomp * 4; }
+  uint64_t* mul_many(const uint64_t* lhs, const uint64_t* rhs, size_t parts, size_t m) {
+    return net.template mul_many<P>(pool, lhs, rhs, parts * HONK_CO_POINTS * m);
+  }
+  // fold_and_filter: the edges a relation keeps, by its selector
+  struct Kept {
+    uint32_t* list;
+    size_t m;
+  };
+  Kept select(const uint64_t* selector) {
+    Kept k{(uint32_t*)pool.fresh(4 * edges), 0};
+    uint32_t* count = (uint32_t*)pool.fresh(4);
+    check(csh_honk_co_select_edges_dev(P::ID, selector, edge_begin, edge_end, k.list, count, nullptr), "csh_honk_co_select_edges_dev");
+    uint32_t c = 0;
+    check(csh_memcpy_d2h(&c, count, 4), "csh_memcpy_d2h");
+    k.m = c;
+    return k;
+  }
+
+  // UltraArithmeticRelation -> r1 (5 shares); r0_half = the 6 half shares of r0, reshared by the caller at the end of the round
+  std::vector<Fr> arith(std::vector<Fr>& r0_half) {
+    const Kept k = select(dc[19]);
+    const uint64_t* mask = protocol == 1 ? net.template masks<P>(pool, HONK_CO_POINTS * k.m) : nullptr;
+    uint64_t *r0 = pool.fresh(sizeof(Fr) * 6), *r1 = acc_shares(5);
+    check(csh_honk_co_arith_dev(P::ID, protocol, party, dc, edge_begin, edge_end, k.list, k.m, table, stride, mask, r0, r1, nullptr), "csh_honk_co_arith_dev");
+    r0_half = down(r0, 6);
+    return down(r1, 5 * ncomp);
+  }
+  // UltraPermutationRelation: never skipped -> r0 (6), r1 (3)
+  std::vector<Fr> perm() {
+    uint64_t *lhs = shares(4, edges), *rhs = shares(4, edges), *rhs2 = shares(2, edges), *acc = acc_shares(9);
+    check(csh_honk_co_perm_operands_dev(P::ID, protocol, party, dc, edge_begin, edge_end, nullptr, edges, prm(), lhs, rhs, nullptr), "csh_honk_co_perm_operands_dev");
+    const uint64_t* mul1 = mul_many(lhs, rhs, 4, edges);
+    const uint64_t* num_den = mul_many(mul1, part(mul1, 2, edges), 2, edges);
+    check(csh_honk_co_perm_operands2_dev(P::ID, protocol, party, dc, edge_begin, edge_end, nullptr, edges, prm(), rhs2, nullptr), "csh_honk_co_perm_operands2_dev");
+    const uint64_t* prod = mul_many(num_den, rhs2, 2, edges);
+    check(csh_honk_co_perm_finish_dev(P::ID, protocol, party, dc, edge_begin, edge_end, nullptr, edges, table, stride, prod, acc, nullptr), "csh_honk_co_perm_finish_dev");
+    return down(acc, 9 * ncomp);
+  }
+  // DeltaRangeConstraintRelation -> r0 .. r3 (6 each)
+  std::vector<Fr> delta() {
+    const Kept k = select(dc[20]);
+    uint64_t* acc = acc_shares(24);
+    const uint64_t* mul = nullptr;
+    if (k.m) {
+      uint64_t* lhs = shares(8, k.m);
+      check(csh_honk_co_delta_operands_dev(P::ID, protocol, party, dc, edge_begin, edge_end, k.list, k.m, lhs, nullptr), "csh_honk_co_delta_operands_dev");
+      uint64_t* sqr = mul_many(lhs, lhs, 8, k.m);
+      check(csh_honk_co_delta_sub_one_dev(P::ID, protocol, party, sqr, k.m, nullptr), "csh_honk_co_delta_sub_one_dev");
+      mul = mul_many(sqr, part(sqr, 4, k.m), 4, k.m);
+    }
+    check(csh_honk_co_delta_finish_dev(P::ID, protocol, party, dc, edge_begin, edge_end, k.list, k.m, table, stride, mul, acc, nullptr), "csh_honk_co_delta_finish_dev");
+    return down(acc, 24 * ncomp);
+  }
+  // LogDerivLookupRelation: never skipped -> r0 (5), r1 (5), r2 (3)
+  std::vector<Fr> lookup() {
+    uint64_t *read_term = shares(1, edges), *inverses = shares(1, edges), *lhs = shares(2, edges), *rhs = shares(2, edges);
+    uint64_t *r0 = acc_shares(5), *acc = acc_shares(8);
+    check(csh_honk_co_lookup_operands_dev(P::ID, protocol, party, dc, edge_begin, edge_end, nullptr, edges, prm(), read_term, inverses, nullptr), "csh_honk_co_lookup_operands_dev");
+    const uint64_t* write_inverse = mul_many(read_term, inverses, 1, edges);
+    check(csh_honk_co_lookup_mid_dev(P::ID, protocol, party, dc, edge_begin, edge_end, nullptr, edges, table, stride, prm(), write_inverse, r0, lhs, rhs, nullptr),
+          "csh_honk_co_lookup_mid_dev");
+    const uint64_t* mul = mul_many(lhs, rhs, 2, edges);
+    check(csh_honk_co_lookup_finish_dev(P::ID, protocol, party, dc, edge_begin, edge_end, nullptr, edges, table, stride, prm(), mul, acc, nullptr), "csh_honk_co_lookup_finish_dev");
+    std::vector<Fr> out = down(r0, 5 * ncomp);
+    const std::vector<Fr> rest = down(acc, 8 * ncomp);
+    out.insert(out.end(), rest.begin(), rest.end());
+    return out;
+  }
+  // EllipticRelation (csrc/honk_co_gates.hip) -> r0, r1 (6 each). A relation without kept edges makes no network call.
+  std::vector<Fr> elliptic() {
+    const Kept k = select(dg[14]);
+    uint64_t* acc = acc_shares(12);
+    const uint64_t *mul1 = nullptr, *mul2 = nullptr;
+    if (k.m) {
+      uint64_t *lhs = shares(7, k.m), *rhs = shares(7, k.m), *lhs2 = shares(5, k.m), *rhs2 = shares(5, k.m);
+      check(csh_honk_co_ell_operands_dev(P::ID, protocol, party, dg, edge_begin, edge_end, k.list, k.m, lhs, rhs, nullptr), "csh_honk_co_ell_operands_dev");
+      mul1 = mul_many(lhs, rhs, 7, k.m);
+      check(csh_honk_co_ell_operands2_dev(P::ID, protocol, party, dg, edge_begin, edge_end, k.list, k.m, gprm(), mul1, lhs2, rhs2, nullptr), "csh_honk_co_ell_operands2_dev");
+      mul2 = mul_many(lhs2, rhs2, 5, k.m);
+    }
+    check(csh_honk_co_ell_finish_dev(P::ID, protocol, party, dg, edge_begin, edge_end, k.list, k.m, table, stride, mul1, mul2, acc, nullptr), "csh_honk_co_ell_finish_dev");
+    return down(acc, 12 * ncomp);
+  }
+  // MemoryRelation -> r0 .. r5 (6 each); the second product's left operand is part 3 of the first product in place
+  std::vector<Fr> memory() {
+    const Kept k = select(dg[15]);
+    uint64_t* acc = acc_shares(36);
+    const uint64_t *mul = nullptr, *mul2 = nullptr;
+    if (k.m) {
+      uint64_t *lhs = shares(6, k.m), *rhs = shares(6, k.m), *rhs2 = shares(1, k.m);
+      check(csh_honk_co_mem_operands_dev(P::ID, protocol, party, dg, edge_begin, edge_end, k.list, k.m, gprm(), lhs, rhs, rhs2, nullptr), "csh_honk_co_mem_operands_dev");
+      mul = mul_many(lhs, rhs, 6, k.m);
+      mul2 = mul_many(part(mul, 3, k.m), rhs2, 1, k.m);
+    }
+    check(csh_honk_co_mem_finish_dev(P::ID, protocol, party, dg, edge_begin, edge_end, k.list, k.m, table, stride, gprm(), mul, mul2, acc, nullptr), "csh_honk_co_mem_finish_dev");
+    return down(acc, 36 * ncomp);
+  }
+  // NonNativeFieldRelation -> r0 (6)
+  std::vector<Fr> nnf() {
+    const Kept k = select(dg[16]);
+    uint64_t* acc = acc_shares(6);
+    const uint64_t* mul = nullptr;
+    if (k.m) {
+      uint64_t *lhs = shares(5, k.m), *rhs = shares(5, k.m);
+      check(csh_honk_co_nnf_operands_dev(P::ID, protocol, party, dg, edge_begin, edge_end, k.list, k.m, lhs, rhs, nullptr), "csh_honk_co_nnf_operands_dev");
+      mul = mul_many(lhs, rhs, 5, k.m);
+    }
+    check(csh_honk_co_nnf_finish_dev(P::ID, protocol, party, dg, edge_begin, edge_end, k.list, k.m, table, stride, mul, acc, nullptr), "csh_honk_co_nnf_finish_dev");
+    return down(acc, 6 * ncomp);
+  }
+  // x^5 as the reference does it: s s, that squared, then times s
+  const uint64_t* sbox(const uint64_t* s, size_t parts, size_t m) {
+    const uint64_t* u = mul_many(s, s, parts, m);
+    u = mul_many(u, u, parts, m);
+    return mul_many(u, s, parts, m);
+  }
+  // Poseidon2ExternalRelation -> r0 .. r3 (7 each)
+  std::vector<Fr> poseidon2_external() {
+    const Kept k = select(dg[17]);
+    uint64_t* acc = acc_shares(28);
+    const uint64_t* u = nullptr;
+    if (k.m) {
+      uint64_t* s = shares(4, k.m);
+      check(csh_honk_co_pos_ext_operands_dev(P::ID, protocol, party, dg, edge_begin, edge_end, k.list, k.m, s, nullptr), "csh_honk_co_pos_ext_operands_dev");
+      u = sbox(s, 4, k.m);
+    }
+    check(csh_honk_co_pos_ext_finish_dev(P::ID, protocol, party, dg, edge_begin, edge_end, k.list, k.m, table, stride, u, acc, nullptr), "csh_honk_co_pos_ext_finish_dev");
+    return down(acc, 28 * ncomp);
+  }
+  // Poseidon2InternalRelation -> r0 .. r3 (7 each)
+  std::vector<Fr> poseidon2_internal() {
+    const Kept k = select(dg[18]);
+    uint64_t* acc = acc_shares(28);
+    const uint64_t* u = nullptr;
+    if (k.m) {
+      uint64_t* s = shares(1, k.m);
+      check(csh_honk_co_pos_int_operands_dev(P::ID, protocol, party, dg, edge_begin, edge_end, k.list, k.m, s, nullptr), "csh_honk_co_pos_int_operands_dev");
+      u = sbox(s, 1, k.m);
+    }
+    check(csh_honk_co_pos_int_finish_dev(P::ID, protocol, party, dg, edge_begin, edge_end, k.list, k.m, table, stride, gprm(), u, acc, nullptr), "csh_honk_co_pos_int_finish_dev");
+    return down(acc, 28 * ncomp);
+  }
+};
+template <class Fr>
+inline void honk_co_append(std::vector<Fr>& out, const std::vector<Fr>& v) {
+  out.insert(out.end(), v.begin(), v.end());
+}
+}  // namespace detail
+
 // cols: the 36 columns of csh_honk_sumcheck_accumulate_dev as the party holds them -- the 13 witness and shifted-witness columns as shares
 // (ncomp = PROTOCOL + 1 values per element), the 23 precomputed columns public. -> the eleven accumulators back to back as shares,
 // HONK_ACC_ELEMS * ncomp values. gs == nullptr: the factor one.
@@ -1506,96 +1713,48 @@ template <class P, class Net>
 inline std::vector<typename P::Fr> co_compute_round_accumulators(Net& net, const std::vector<std::vector<typename P::Fr>>& cols, size_t edge_begin, size_t edge_end,
                                                                  const HonkGateSeparator<typename P::Fr>* gs, const HonkRelationParameters<typename P::Fr>& params) {
   using Fr = typename P::Fr;
-  const uint32_t protocol = Net::PROTOCOL, party = net.party();
-  const size_t ncomp = protocol + 1, edges = (edge_end - edge_begin) / 2;
-  if (cols.size() != HONK_SUMCHECK_COLUMNS) throw Error("co_compute_round_accumulators: 36 columns");
-  if ((edge_begin & 1) || (edge_end & 1) || edge_begin >= edge_end) throw Error("co_compute_round_accumulators: an even, non-empty range");
-  for (size_t c = 0; c < HONK_SUMCHECK_COLUMNS; ++c)
-    if (cols[c].size() < edge_end * (c < 13 ? ncomp : 1)) throw Error("co_compute_round_accumulators: a column is shorter than the range");
-  if (gs && (gs->log_num_monomials > 28 || gs->betas.size() < gs->log_num_monomials || ((edge_end >> 1) - 1) * gs->periodicity >= (size_t(1) << gs->log_num_monomials)))
-    throw Error("co_compute_round_accumulators: the gate separator's table is shorter than the range reads");
-  detail::DevicePool pool;
-  const uint64_t* dc[HONK_SUMCHECK_COLUMNS];
-  for (size_t c = 0; c < HONK_SUMCHECK_COLUMNS; ++c) dc[c] = pool.up(cols[c]);
-  uint64_t* table = nullptr;
-  const size_t stride = gs ? gs->periodicity : 1;
-  if (gs) {
-    table = pool.fresh(sizeof(Fr) << gs->log_num_monomials);
-    check(csh_honk_pow_table_dev(P::ID, (const uint64_t*)gs->betas.data(), gs->log_num_monomials, table, nullptr), "csh_honk_pow_table_dev");
-  }
-  const Fr pr[3] = {params.beta, params.gamma, params.public_input_delta};
-  const uint64_t* prm = (const uint64_t*)pr;
-  auto shares = [&](size_t vectors, size_t m) { return pool.fresh(sizeof(Fr) * vectors * HONK_CO_POINTS * m * ncomp); };
-  auto down = [&](const uint64_t* d, size_t count) {
-    std::vector<Fr> v(count);
-    check(csh_memcpy_d2h(v.data(), d, sizeof(Fr) * count), "csh_memcpy_d2h");
-    return v;
-  };
-  // fold_and_filter: the edges the arithmetic and the delta-range relation keep
-  uint32_t* list[2];
-  size_t kept[2];
-  for (int r = 0; r < 2; ++r) {
-    list[r] = (uint32_t*)pool.fresh(4 * edges);
-    uint32_t* count = (uint32_t*)pool.fresh(4);
-    check(csh_honk_co_select_edges_dev(P::ID, dc[r ? 20 : 19], edge_begin, edge_end, list[r], count, nullptr), "csh_honk_co_select_edges_dev");
-    uint32_t c = 0;
-    check(csh_memcpy_d2h(&c, count, 4), "csh_memcpy_d2h");
-    kept[r] = c;
-  }
-  std::vector<Fr> out, r0_half;  // out: everything behind arith.r0, which is reshared last
-  out.reserve(HONK_ACC_ELEMS * ncomp);
-  auto append = [&](const std::vector<Fr>& v) { out.insert(out.end(), v.begin(), v.end()); };
-  {  // UltraArithmeticRelation
-    const uint64_t* mask = protocol == 1 ? net.template masks<P>(pool, HONK_CO_POINTS * kept[0]) : nullptr;
-    uint64_t *r0 = pool.fresh(sizeof(Fr) * 6), *r1 = pool.fresh(sizeof(Fr) * 5 * ncomp);
-    check(csh_honk_co_arith_dev(P::ID, protocol, party, dc, edge_begin, edge_end, list[0], kept[0], table, stride, mask, r0, r1, nullptr), "csh_honk_co_arith_dev");
-    r0_half = down(r0, 6);
-    append(down(r1, 5 * ncomp));
-  }
-  {  // UltraPermutationRelation: never skipped
-    const size_t n7 = HONK_CO_POINTS * edges, half = 2 * n7 * ncomp * 4;  // words of half the first product
-    uint64_t *lhs = shares(4, edges), *rhs = shares(4, edges), *rhs2 = shares(2, edges), *acc = pool.fresh(sizeof(Fr) * 9 * ncomp);
-    check(csh_honk_co_perm_operands_dev(P::ID, protocol, party, dc, edge_begin, edge_end, nullptr, edges, prm, lhs, rhs, nullptr), "csh_honk_co_perm_operands_dev");
-    const uint64_t* mul1 = net.template mul_many<P>(pool, lhs, rhs, 4 * n7);
-    const uint64_t* num_den = net.template mul_many<P>(pool, mul1, mul1 + half, 2 * n7);
-    check(csh_honk_co_perm_operands2_dev(P::ID, protocol, party, dc, edge_begin, edge_end, nullptr, edges, prm, rhs2, nullptr), "csh_honk_co_perm_operands2_dev");
-    const uint64_t* prod = net.template mul_many<P>(pool, num_den, rhs2, 2 * n7);
-    check(csh_honk_co_perm_finish_dev(P::ID, protocol, party, dc, edge_begin, edge_end, nullptr, edges, table, stride, prod, acc, nullptr), "csh_honk_co_perm_finish_dev");
-    append(down(acc, 9 * ncomp));
-  }
-  std::vector<Fr> delta;
-  {  // DeltaRangeConstraintRelation
-    const size_t m = kept[1], n7 = HONK_CO_POINTS * m;
-    uint64_t* acc = pool.fresh(sizeof(Fr) * 24 * ncomp);
-    const uint64_t* mul = nullptr;
-    if (m) {
-      uint64_t* lhs = shares(8, m);
-      check(csh_honk_co_delta_operands_dev(P::ID, protocol, party, dc, edge_begin, edge_end, list[1], m, lhs, nullptr), "csh_honk_co_delta_operands_dev");
-      uint64_t* sqr = net.template mul_many<P>(pool, lhs, lhs, 8 * n7);
-      check(csh_honk_co_delta_sub_one_dev(P::ID, protocol, party, sqr, m, nullptr), "csh_honk_co_delta_sub_one_dev");
-      mul = net.template mul_many<P>(pool, sqr, sqr + 4 * n7 * ncomp * 4, 4 * n7);
-    }
-    check(csh_honk_co_delta_finish_dev(P::ID, protocol, party, dc, edge_begin, edge_end, list[1], m, table, stride, mul, acc, nullptr), "csh_honk_co_delta_finish_dev");
-    delta = down(acc, 24 * ncomp);
-  }
-  {  // LogDerivLookupRelation: never skipped
-    const size_t n7 = HONK_CO_POINTS * edges;
-    uint64_t *read_term = shares(1, edges), *inverses = shares(1, edges), *lhs = shares(2, edges), *rhs = shares(2, edges);
-    uint64_t *r0 = pool.fresh(sizeof(Fr) * 5 * ncomp), *acc = pool.fresh(sizeof(Fr) * 8 * ncomp);
-    check(csh_honk_co_lookup_operands_dev(P::ID, protocol, party, dc, edge_begin, edge_end, nullptr, edges, prm, read_term, inverses, nullptr), "csh_honk_co_lookup_operands_dev");
-    const uint64_t* write_inverse = net.template mul_many<P>(pool, read_term, inverses, n7);
-    check(csh_honk_co_lookup_mid_dev(P::ID, protocol, party, dc, edge_begin, edge_end, nullptr, edges, table, stride, prm, write_inverse, r0, lhs, rhs, nullptr),
-          "csh_honk_co_lookup_mid_dev");
-    const uint64_t* mul = net.template mul_many<P>(pool, lhs, rhs, 2 * n7);
-    check(csh_honk_co_lookup_finish_dev(P::ID, protocol, party, dc, edge_begin, edge_end, nullptr, edges, table, stride, prm, mul, acc, nullptr), "csh_honk_co_lookup_finish_dev");
-    append(down(r0, 5 * ncomp));
-    append(down(acc, 8 * ncomp));
-  }
-  append(delta);
+  detail::HonkCoRound<P, Net> round(net, edge_begin, edge_end, gs, "co_compute_round_accumulators");
+  round.up36(cols, params);
+  std::vector<Fr> r0_half;
+  std::vector<Fr> out = round.arith(r0_half);  // everything behind arith.r0, which is reshared last
+  detail::honk_co_append(out, round.perm());
+  const std::vector<Fr> delta = round.delta();
+  detail::honk_co_append(out, round.lookup());
+  detail::honk_co_append(out, delta);
   // AllRelationAccHalfShared::reshare (relations/mod.rs:140-162, co_sumcheck_round.rs:292): the one network message of arith.r0, behind
   // every relation's rounds as in the reference
   std::vector<Fr> all = net.reshare(r0_half);
-  all.insert(all.end(), out.begin(), out.end());
+  detail::honk_co_append(all, out);
+  return all;
+}
+// The same for all nine relations in the order of accumulate_relation_univariates_batch (co_sumcheck_round.rs:140-218): arithmetic,
+// permutation, delta range, elliptic, memory, non-native field, lookup, Poseidon2 external, Poseidon2 internal, so that a reference party
+// sees the reference's sequence of messages. gate_cols: the 19 columns of csh_honk_sumcheck_accumulate_gates_dev, the first eight as
+// shares. -> the 28 accumulators as shares in subrelation order: the eleven of co_compute_round_accumulators (HONK_ACC_ELEMS * ncomp
+// values), then the seventeen of the gate relations (HONK_GATES_ACC_ELEMS * ncomp values).
+template <class P, class Net>
+inline std::vector<typename P::Fr> co_compute_round_accumulators_all(Net& net, const std::vector<std::vector<typename P::Fr>>& cols,
+                                                                     const std::vector<std::vector<typename P::Fr>>& gate_cols, size_t edge_begin, size_t edge_end,
+                                                                     const HonkGateSeparator<typename P::Fr>* gs, const HonkRelationParameters<typename P::Fr>& params,
+                                                                     const HonkGateParameters<typename P::Fr>& gate_params) {
+  using Fr = typename P::Fr;
+  detail::HonkCoRound<P, Net> round(net, edge_begin, edge_end, gs, "co_compute_round_accumulators_all");
+  round.up36(cols, params);
+  round.up19(gate_cols, gate_params);
+  std::vector<Fr> r0_half;
+  std::vector<Fr> first = round.arith(r0_half);
+  detail::honk_co_append(first, round.perm());
+  const std::vector<Fr> delta = round.delta();
+  std::vector<Fr> gates = round.elliptic();
+  detail::honk_co_append(gates, round.memory());
+  detail::honk_co_append(gates, round.nnf());
+  detail::honk_co_append(first, round.lookup());
+  detail::honk_co_append(first, delta);
+  detail::honk_co_append(gates, round.poseidon2_external());
+  detail::honk_co_append(gates, round.poseidon2_internal());
+  std::vector<Fr> all = net.reshare(r0_half);
+  detail::honk_co_append(all, first);
+  detail::honk_co_append(all, gates);
   return all;
 }
 // batch_over_relations_univariates on one party's shares (co_sumcheck_round.rs:121-138): scale and extend_and_batch_univariates are linear
@@ -1608,6 +1767,22 @@ inline std::vector<Fr> co_batch_over_relations(const std::vector<Fr>& acc, size_
     HonkAccumulators<Fr> one;
     for (size_t i = 0; i < HONK_ACC_ELEMS; ++i) one[i] = acc[i * ncomp + c];
     const auto res = detail::honk_batch_over_relations(one, alphas, gs);
+    for (size_t i = 0; i < res.size(); ++i) out[i * ncomp + c] = res[i];
+  }
+  return out;
+}
+// batch_over_relations_univariates over all 28 accumulators on one party's shares: acc = what co_compute_round_accumulators_all returns.
+// -> the 8 shares of the whole round's univariate
+template <class Fr>
+inline std::vector<Fr> co_batch_over_all_relations(const std::vector<Fr>& acc, size_t ncomp, const std::vector<Fr>& alphas, const HonkGateSeparator<Fr>& gs) {
+  if (acc.size() != (HONK_ACC_ELEMS + HONK_GATES_ACC_ELEMS) * ncomp) throw Error("co_batch_over_all_relations: 167 shares");
+  std::vector<Fr> out(HONK_BATCHED_RELATION_PARTIAL_LENGTH * ncomp);
+  for (size_t c = 0; c < ncomp; ++c) {
+    HonkAccumulators<Fr> first;
+    HonkGateAccumulators<Fr> gates;
+    for (size_t i = 0; i < HONK_ACC_ELEMS; ++i) first[i] = acc[i * ncomp + c];
+    for (size_t i = 0; i < HONK_GATES_ACC_ELEMS; ++i) gates[i] = acc[(HONK_ACC_ELEMS + i) * ncomp + c];
+    const auto res = detail::honk_batch_over_all_relations(first, gates, alphas, gs);
     for (size_t i = 0; i < res.size(); ++i) out[i * ncomp + c] = res[i];
   }
   return out;

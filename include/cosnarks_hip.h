@@ -685,6 +685,85 @@ int csh_honk_co_lookup_finish_dev(csh_curve_t field_of, uint32_t protocol, uint3
                                   size_t edge_end, const uint32_t* edge_idx_dev, size_t m, const uint64_t* scaling_dev, size_t scaling_stride,
                                   const uint64_t* params, const uint64_t* mul_dev, uint64_t* acc_dev, void* stream);
 
+/* ---- co-noir UltraHonk, the sumcheck round on shares: the five gate relations ----
+ * The same for the elliptic, memory, non-native field, Poseidon2 external and Poseidon2 internal relations, subrelations 11 .. 27
+ * (csrc/honk_co_gates.hip). Everything said above holds -- the element rule, the edge list, m, the scaling, the concatenation order, the
+ * accumulators, the reductions, the refusals and the overlap rule -- with these differences. cols_dev[0..19) is the column array of
+ * csh_honk_sumcheck_accumulate_gates_dev in the same order: the first eight (w_l, w_r, w_o, w_4 and their shifts) are shares, the other
+ * eleven (q_m, q_c, q_l, q_r, q_o, q_4, q_elliptic, q_memory, q_nnf, q_poseidon2_external, q_poseidon2_internal) are public. params, where
+ * an entry takes it, is the array of that entry too (eta_1, eta_2, eta_3, curve_b, mat_internal_diag_m_1[0..4); 8 elements on the host);
+ * each entry says which of them it reads. The edges of a relation are those kept by csh_honk_co_select_edges_dev on the relation's own
+ * selector (can_skip of relations/elliptic_relation.rs:71-73, memory_relation.rs:113-115, non_native_field_relation.rs:63-65,
+ * poseidon2_external_relation.rs:92-94, poseidon2_internal_relation.rs:93-95). The Poseidon2 accumulators have 7 entries, all others 6:
+ * the element at the point 6 of a batch never reaches a 6-long accumulator. */
+/* EllipticRelation stage (a), relations/elliptic_relation.rs:116-168. With x_1 = w_r, y_1 = w_o, x_2 = w_l_shift, y_2 = w_4_shift,
+ * x_3 = w_r_shift, y_3 = w_o_shift, x_diff = x_2 - x_1, y_diff = q_l y_2 - y_1: lhs_dev = [y_1 | y_2 | y_1 | x_diff | y_1 + y_3 | y_diff |
+ * 3 x_1], rhs_dev = [y_1 | y_2 | y_2 | x_diff | x_diff | x_3 - x_1 | x_1], 7 * 7 m shares each. The caller runs mul1 = mul_many(lhs, rhs).
+ * Reads w_r, w_o, the four shifts, q_l. */
+int csh_honk_co_ell_operands_dev(csh_curve_t field_of, uint32_t protocol, uint32_t party_id, const uint64_t* const* cols_dev, size_t edge_begin,
+                                 size_t edge_end, const uint32_t* edge_idx_dev, size_t m, uint64_t* lhs_dev, uint64_t* rhs_dev, void* stream);
+/* Stage (b), :173-195: mul1_dev = that product. lhs_dev = [x_3 + x_2 + x_1 | mul1[0] (+) -curve_b | x_3 + 2 x_1 | mul1[6] | 2 y_1],
+ * rhs_dev = [mul1[3] | 3 x_1 | 4 mul1[0] | x_1 - x_3 | y_1 + y_3], 5 * 7 m shares each. The caller runs mul2 = mul_many(lhs, rhs).
+ * Reads w_r, w_o, w_l_shift, w_r_shift, w_o_shift; params: curve_b. */
+int csh_honk_co_ell_operands2_dev(csh_curve_t field_of, uint32_t protocol, uint32_t party_id, const uint64_t* const* cols_dev, size_t edge_begin,
+                                  size_t edge_end, const uint32_t* edge_idx_dev, size_t m, const uint64_t* params, const uint64_t* mul1_dev,
+                                  uint64_t* lhs_dev, uint64_t* rhs_dev, void* stream);
+/* Stage (c), :199-252. acc_dev[0..12) shares: elliptic.r0 (6) = the fold of (mul2[0] - mul1[1] - mul1[0] + 2 q_l mul1[2]) qn +
+ * (mul2[2] - 3 mul2[1]) qd, elliptic.r1 (6) = the fold of (mul1[4] + mul1[5]) qn + (mul2[3] - mul2[4]) qd, with the public factors
+ * qd = q_elliptic scaling q_m and qn = q_elliptic scaling - qd (:208-249). Reads q_l, q_m, q_elliptic. */
+int csh_honk_co_ell_finish_dev(csh_curve_t field_of, uint32_t protocol, uint32_t party_id, const uint64_t* const* cols_dev, size_t edge_begin,
+                               size_t edge_end, const uint32_t* edge_idx_dev, size_t m, const uint64_t* scaling_dev, size_t scaling_stride,
+                               const uint64_t* mul1_dev, const uint64_t* mul2_dev, uint64_t* acc_dev, void* stream);
+/* MemoryRelation stage (a), relations/memory_relation.rs:241-357. With record = (w_o eta_3 + w_r eta_2 + w_l eta_1) (+) q_c - w_4 (the
+ * record check, and neg_access_type), next = w_o_shift eta_3 + w_r_shift eta_2 + w_l_shift eta_1 - w_4_shift, nid = w_l - w_l_shift,
+ * idz = nid (+) 1: lhs_dev = [nid | idz | record | idz | next | idz], rhs_dev = [nid | w_4_shift - w_4 | record | w_o_shift - w_o | next |
+ * w_r_shift - w_r], 6 * 7 m shares each, the order of :272-357; rhs2_dev = next (+) 1, 7 m shares (:398). The caller runs
+ * mul = mul_many(lhs, rhs) and mul2 = mul_many(mul[3], rhs2), whose left operand is part 3 of mul in place. Reads the eight share
+ * columns and q_c; params: eta_1, eta_2, eta_3. */
+int csh_honk_co_mem_operands_dev(csh_curve_t field_of, uint32_t protocol, uint32_t party_id, const uint64_t* const* cols_dev, size_t edge_begin,
+                                 size_t edge_end, const uint32_t* edge_idx_dev, size_t m, const uint64_t* params, uint64_t* lhs_dev,
+                                 uint64_t* rhs_dev, uint64_t* rhs2_dev, void* stream);
+/* Stage (b), :370-455: mul_dev = 6 * 7 m shares, mul2_dev = 7 m shares. acc_dev[0..36) shares, memory.r0 .. r5 (6 each), with
+ * qms = q_memory scaling: r1 = mul[1] q_l q_r qms, r2 = (mul[0] + nid) q_l q_r qms, r3 = mul2 q_o qms, r4 = (mul[0] + nid) q_o qms,
+ * r5 = (mul[4] + next) q_o qms, r0 = (record q_l q_r + (mul[5] - w_o) q_4 q_l + record q_m q_l) qms + (mul[2] + record) q_o qms: the RAM
+ * consistency term carries q_memory scaling already and is added after the product (:452-453). Reads the eight share columns, q_m, q_c,
+ * q_l, q_r, q_o, q_4, q_memory; params: eta_1, eta_2, eta_3. */
+int csh_honk_co_mem_finish_dev(csh_curve_t field_of, uint32_t protocol, uint32_t party_id, const uint64_t* const* cols_dev, size_t edge_begin,
+                               size_t edge_end, const uint32_t* edge_idx_dev, size_t m, const uint64_t* scaling_dev, size_t scaling_stride,
+                               const uint64_t* params, const uint64_t* mul_dev, const uint64_t* mul2_dev, uint64_t* acc_dev, void* stream);
+/* NonNativeFieldRelation stage (a), relations/non_native_field_relation.rs:138-150: lhs_dev = [w_l | w_r | w_4 | w_o | w_l_shift],
+ * rhs_dev = [w_r_shift | w_l_shift | w_l | w_r | w_r_shift], 5 * 7 m shares each: the extended columns, so that the product's operands
+ * exist in memory. The caller runs mul = mul_many(lhs, rhs). Reads w_l, w_r, w_o, w_4, w_l_shift, w_r_shift. */
+int csh_honk_co_nnf_operands_dev(csh_curve_t field_of, uint32_t protocol, uint32_t party_id, const uint64_t* const* cols_dev, size_t edge_begin,
+                                 size_t edge_end, const uint32_t* edge_idx_dev, size_t m, uint64_t* lhs_dev, uint64_t* rhs_dev, void* stream);
+/* Stage (b), :154-213: mul_dev = 5 * 7 m shares. acc_dev[0..6) shares = nnf.r0, the fold of ((gate_1 + gate_2 + gate_3) q_r +
+ * (limb_accumulator_1 + limb_accumulator_2) q_o) q_nnf scaling; the constants 2^68 and 2^14 are made on the host per field. Reads the
+ * eight share columns, q_m, q_r, q_o, q_4, q_nnf. */
+int csh_honk_co_nnf_finish_dev(csh_curve_t field_of, uint32_t protocol, uint32_t party_id, const uint64_t* const* cols_dev, size_t edge_begin,
+                               size_t edge_end, const uint32_t* edge_idx_dev, size_t m, const uint64_t* scaling_dev, size_t scaling_stride,
+                               const uint64_t* mul_dev, uint64_t* acc_dev, void* stream);
+/* Poseidon2ExternalRelation stage (a), relations/poseidon2_external_relation.rs:165-174: s_dev = [w_l (+) q_l | w_r (+) q_r | w_o (+) q_o |
+ * w_4 (+) q_4], 4 * 7 m shares. The caller runs the three products of the s-box on vectors it holds: s s, that squared, then times s
+ * (:177-179). Reads w_l, w_r, w_o, w_4, q_l, q_r, q_o, q_4. */
+int csh_honk_co_pos_ext_operands_dev(csh_curve_t field_of, uint32_t protocol, uint32_t party_id, const uint64_t* const* cols_dev, size_t edge_begin,
+                                     size_t edge_end, const uint32_t* edge_idx_dev, size_t m, uint64_t* s_dev, void* stream);
+/* Stage (b), :181-226: u_dev = s^5, 4 * 7 m shares. v = M_E u by the reference's 14 additions; acc_dev[0..28) shares:
+ * poseidon2_external.r0 .. r3, SEVEN entries each, r_i = the fold of (v_i - w_i_shift) q_poseidon2_external scaling. Reads the four
+ * shifts and q_poseidon2_external. */
+int csh_honk_co_pos_ext_finish_dev(csh_curve_t field_of, uint32_t protocol, uint32_t party_id, const uint64_t* const* cols_dev, size_t edge_begin,
+                                   size_t edge_end, const uint32_t* edge_idx_dev, size_t m, const uint64_t* scaling_dev, size_t scaling_stride,
+                                   const uint64_t* u_dev, uint64_t* acc_dev, void* stream);
+/* Poseidon2InternalRelation stage (a), relations/poseidon2_internal_relation.rs:155: s1_dev = w_l (+) q_l, 7 m shares. The caller runs the
+ * three products of the s-box (:159-161). Reads w_l, q_l. */
+int csh_honk_co_pos_int_operands_dev(csh_curve_t field_of, uint32_t protocol, uint32_t party_id, const uint64_t* const* cols_dev, size_t edge_begin,
+                                     size_t edge_end, const uint32_t* edge_idx_dev, size_t m, uint64_t* s1_dev, void* stream);
+/* Stage (b), :163-223: u1_dev = s1^5, 7 m shares. With u = (u1, w_r, w_o, w_4) and sum = u_1 + u_2 + u_3 + u_4: acc_dev[0..28) shares:
+ * poseidon2_internal.r0 .. r3, SEVEN entries each, r_i = the fold of (u_i diag_i + sum - w_i_shift) q_poseidon2_internal scaling. The
+ * library builds in no diagonal values. Reads w_r, w_o, w_4, the four shifts, q_poseidon2_internal; params: mat_internal_diag_m_1. */
+int csh_honk_co_pos_int_finish_dev(csh_curve_t field_of, uint32_t protocol, uint32_t party_id, const uint64_t* const* cols_dev, size_t edge_begin,
+                                   size_t edge_end, const uint32_t* edge_idx_dev, size_t m, const uint64_t* scaling_dev, size_t scaling_stride,
+                                   const uint64_t* params, const uint64_t* u1_dev, uint64_t* acc_dev, void* stream);
+
 /* Rep3 correlated masks generated on the device ("next" row f2): out[i] = from_be_bytes_mod_order(a_i) -
  * from_be_bytes_mod_order(b_i), a_i / b_i = the 32-byte chunks number elem_offset{1,2} + i of the ChaCha12 keystreams
  * of seed1 (own key) and seed2 (previous party's key): byte-compatible with Rep3Rand::masking_field_elements_vec

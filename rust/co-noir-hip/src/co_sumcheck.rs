@@ -12,7 +12,7 @@ use co_groth16_hip::error::check;
 use co_groth16_hip::layout::limbs_of;
 use cosnarks_hip_sys as sys;
 
-use crate::sumcheck::SUMCHECK_COLUMNS;
+use crate::sumcheck::{GATES_COLUMNS, GATES_PARAMS, SUMCHECK_COLUMNS};
 
 /// Batch elements per kept edge (MAX_PARTIAL_RELATION_LENGTH).
 pub const CO_POINTS: usize = 7;
@@ -111,4 +111,96 @@ pub fn hip_co_lookup_mid<F: PrimeField>(b: &CoBatch<F>, write_inverse_dev: *cons
 pub fn hip_co_lookup_finish<F: PrimeField>(b: &CoBatch<F>, mul_dev: *const u64, acc_dev: *mut u64) -> eyre::Result<()> {
     let (scaling, stride) = b.scaling();
     check(unsafe { sys::csh_honk_co_lookup_finish_dev(b.field, b.protocol, b.party_id, b.cols.as_ptr(), b.edge_begin, b.edge_end, b.list(), b.kept(), scaling, stride, limbs_of(&b.params[..]), mul_dev, acc_dev, core::ptr::null_mut()) })
+}
+
+// ---- the five gate relations (csrc/honk_co_gates.hip): elliptic_relation.rs:102-254, memory_relation.rs:166-457,
+// non_native_field_relation.rs:109-215, poseidon2_external_relation.rs:141-228, poseidon2_internal_relation.rs:135-227 ----
+
+/// `CoBatch` over the 19 device columns of `csh_honk_sumcheck_accumulate_gates_dev` (the eight witness and shifted-witness columns as
+/// shares) and its eight parameters (`crate::sumcheck::gate_params`); `edge_idx` = the list of `hip_co_select_edges` on the relation's
+/// own selector (q_elliptic, q_memory, q_nnf, q_poseidon2_external, q_poseidon2_internal).
+pub struct CoGatesBatch<'a, F: PrimeField> {
+    pub field: i32,
+    pub protocol: u32,
+    pub party_id: u32,
+    pub cols: &'a [*const u64; GATES_COLUMNS],
+    pub edge_begin: usize,
+    pub edge_end: usize,
+    pub edge_idx: Option<(*const u32, usize)>,
+    pub gate_separator: Option<(*const u64, usize)>,
+    pub params: &'a [F; GATES_PARAMS],
+}
+
+impl<'a, F: PrimeField> CoGatesBatch<'a, F> {
+    /// m: the kept edges
+    pub fn kept(&self) -> usize {
+        self.edge_idx.map(|(_, m)| m).unwrap_or((self.edge_end - self.edge_begin) / 2)
+    }
+    fn list(&self) -> *const u32 {
+        self.edge_idx.map(|(p, _)| p).unwrap_or(core::ptr::null())
+    }
+    fn scaling(&self) -> (*const u64, usize) {
+        self.gate_separator.unwrap_or((core::ptr::null(), 1))
+    }
+}
+
+/// Elliptic stage (a): `lhs_dev` = [y1 | y2 | y1 | x_diff | y1 + y3 | y_diff | 3 x1], `rhs_dev` = [y1 | y2 | y2 | x_diff | x_diff | x3 - x1 | x1], 7 * 7 m shares each.
+pub fn hip_co_ell_operands<F: PrimeField>(b: &CoGatesBatch<F>, lhs_dev: *mut u64, rhs_dev: *mut u64) -> eyre::Result<()> {
+    check(unsafe { sys::csh_honk_co_ell_operands_dev(b.field, b.protocol, b.party_id, b.cols.as_ptr(), b.edge_begin, b.edge_end, b.list(), b.kept(), lhs_dev, rhs_dev, core::ptr::null_mut()) })
+}
+
+/// Elliptic stage (b): `mul1_dev` = mul_many(lhs, rhs) -> the operands of the second product, 5 * 7 m shares each.
+pub fn hip_co_ell_operands2<F: PrimeField>(b: &CoGatesBatch<F>, mul1_dev: *const u64, lhs_dev: *mut u64, rhs_dev: *mut u64) -> eyre::Result<()> {
+    check(unsafe { sys::csh_honk_co_ell_operands2_dev(b.field, b.protocol, b.party_id, b.cols.as_ptr(), b.edge_begin, b.edge_end, b.list(), b.kept(), limbs_of(&b.params[..]), mul1_dev, lhs_dev, rhs_dev, core::ptr::null_mut()) })
+}
+
+/// Elliptic stage (c): `acc_dev` = elliptic.r0, r1 (6 shares each).
+pub fn hip_co_ell_finish<F: PrimeField>(b: &CoGatesBatch<F>, mul1_dev: *const u64, mul2_dev: *const u64, acc_dev: *mut u64) -> eyre::Result<()> {
+    let (scaling, stride) = b.scaling();
+    check(unsafe { sys::csh_honk_co_ell_finish_dev(b.field, b.protocol, b.party_id, b.cols.as_ptr(), b.edge_begin, b.edge_end, b.list(), b.kept(), scaling, stride, mul1_dev, mul2_dev, acc_dev, core::ptr::null_mut()) })
+}
+
+/// Memory stage (a): `lhs_dev`, `rhs_dev` = 6 * 7 m shares each in the order of memory_relation.rs:272-357, `rhs2_dev` =
+/// neg_next_gate_access_type (+) 1 (7 m shares). The caller runs mul = mul_many(lhs, rhs), then mul2 = mul_many(mul[3], rhs2).
+pub fn hip_co_mem_operands<F: PrimeField>(b: &CoGatesBatch<F>, lhs_dev: *mut u64, rhs_dev: *mut u64, rhs2_dev: *mut u64) -> eyre::Result<()> {
+    check(unsafe { sys::csh_honk_co_mem_operands_dev(b.field, b.protocol, b.party_id, b.cols.as_ptr(), b.edge_begin, b.edge_end, b.list(), b.kept(), limbs_of(&b.params[..]), lhs_dev, rhs_dev, rhs2_dev, core::ptr::null_mut()) })
+}
+
+/// Memory stage (b): `acc_dev` = memory.r0 .. r5 (6 shares each).
+pub fn hip_co_mem_finish<F: PrimeField>(b: &CoGatesBatch<F>, mul_dev: *const u64, mul2_dev: *const u64, acc_dev: *mut u64) -> eyre::Result<()> {
+    let (scaling, stride) = b.scaling();
+    check(unsafe { sys::csh_honk_co_mem_finish_dev(b.field, b.protocol, b.party_id, b.cols.as_ptr(), b.edge_begin, b.edge_end, b.list(), b.kept(), scaling, stride, limbs_of(&b.params[..]), mul_dev, mul2_dev, acc_dev, core::ptr::null_mut()) })
+}
+
+/// Non-native field stage (a): `lhs_dev` = [w1 | w2 | w4 | w3 | w1'], `rhs_dev` = [w2' | w1' | w1 | w2 | w2'], 5 * 7 m shares each.
+pub fn hip_co_nnf_operands<F: PrimeField>(b: &CoGatesBatch<F>, lhs_dev: *mut u64, rhs_dev: *mut u64) -> eyre::Result<()> {
+    check(unsafe { sys::csh_honk_co_nnf_operands_dev(b.field, b.protocol, b.party_id, b.cols.as_ptr(), b.edge_begin, b.edge_end, b.list(), b.kept(), lhs_dev, rhs_dev, core::ptr::null_mut()) })
+}
+
+/// Non-native field stage (b): `acc_dev` = nnf.r0 (6 shares).
+pub fn hip_co_nnf_finish<F: PrimeField>(b: &CoGatesBatch<F>, mul_dev: *const u64, acc_dev: *mut u64) -> eyre::Result<()> {
+    let (scaling, stride) = b.scaling();
+    check(unsafe { sys::csh_honk_co_nnf_finish_dev(b.field, b.protocol, b.party_id, b.cols.as_ptr(), b.edge_begin, b.edge_end, b.list(), b.kept(), scaling, stride, mul_dev, acc_dev, core::ptr::null_mut()) })
+}
+
+/// Poseidon2 external stage (a): `s_dev` = [s1 | s2 | s3 | s4], s_i = w_i (+) q_i, 4 * 7 m shares; the caller runs the s-box's three products.
+pub fn hip_co_pos_ext_operands<F: PrimeField>(b: &CoGatesBatch<F>, s_dev: *mut u64) -> eyre::Result<()> {
+    check(unsafe { sys::csh_honk_co_pos_ext_operands_dev(b.field, b.protocol, b.party_id, b.cols.as_ptr(), b.edge_begin, b.edge_end, b.list(), b.kept(), s_dev, core::ptr::null_mut()) })
+}
+
+/// Poseidon2 external stage (b): `u_dev` = s^5 -> `acc_dev` = poseidon2_external.r0 .. r3 (7 shares each).
+pub fn hip_co_pos_ext_finish<F: PrimeField>(b: &CoGatesBatch<F>, u_dev: *const u64, acc_dev: *mut u64) -> eyre::Result<()> {
+    let (scaling, stride) = b.scaling();
+    check(unsafe { sys::csh_honk_co_pos_ext_finish_dev(b.field, b.protocol, b.party_id, b.cols.as_ptr(), b.edge_begin, b.edge_end, b.list(), b.kept(), scaling, stride, u_dev, acc_dev, core::ptr::null_mut()) })
+}
+
+/// Poseidon2 internal stage (a): `s1_dev` = w_l (+) q_l, 7 m shares.
+pub fn hip_co_pos_int_operands<F: PrimeField>(b: &CoGatesBatch<F>, s1_dev: *mut u64) -> eyre::Result<()> {
+    check(unsafe { sys::csh_honk_co_pos_int_operands_dev(b.field, b.protocol, b.party_id, b.cols.as_ptr(), b.edge_begin, b.edge_end, b.list(), b.kept(), s1_dev, core::ptr::null_mut()) })
+}
+
+/// Poseidon2 internal stage (b): `u1_dev` = s1^5 -> `acc_dev` = poseidon2_internal.r0 .. r3 (7 shares each).
+pub fn hip_co_pos_int_finish<F: PrimeField>(b: &CoGatesBatch<F>, u1_dev: *const u64, acc_dev: *mut u64) -> eyre::Result<()> {
+    let (scaling, stride) = b.scaling();
+    check(unsafe { sys::csh_honk_co_pos_int_finish_dev(b.field, b.protocol, b.party_id, b.cols.as_ptr(), b.edge_begin, b.edge_end, b.list(), b.kept(), scaling, stride, limbs_of(&b.params[..]), u1_dev, acc_dev, core::ptr::null_mut()) })
 }

@@ -16,5 +16,6 @@ pub mod sumcheck;
 pub use sumcheck::{gate_params, hip_compute_univariate, hip_compute_univariate_all, hip_compute_univariate_gates, hip_pow_table, AllAccumulators, GateAccumulators, UltraAccumulators};
 pub mod co_sumcheck;
 pub use co_sumcheck::{hip_co_arith, hip_co_delta_finish, hip_co_delta_operands, hip_co_delta_sub_one, hip_co_lookup_finish, hip_co_lookup_mid, hip_co_lookup_operands, hip_co_perm_finish, hip_co_perm_operands, hip_co_perm_operands2, hip_co_select_edges, CoBatch};
+pub use co_sumcheck::{hip_co_ell_finish, hip_co_ell_operands, hip_co_ell_operands2, hip_co_mem_finish, hip_co_mem_operands, hip_co_nnf_finish, hip_co_nnf_operands, hip_co_pos_ext_finish, hip_co_pos_ext_operands, hip_co_pos_int_finish, hip_co_pos_int_operands, CoGatesBatch};
 pub mod scans;
 pub use scans::{hip_batch_inverse, hip_batched_polys_dev, hip_eval_poly, hip_prefix_product, hip_factor_roots};

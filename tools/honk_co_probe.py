@@ -4,11 +4,15 @@ own, and the party's whole round of the four relations -- the stages with the lo
 (csh_rep3_local_mul_vec_dev; the exchange of the halves is the network's and is not here: the product's output stands in for the
 reshared vector).
 
-    python tools/honk_co_probe.py [--log FILE] [--sizes 12,16,20] [--example EXE]
+    python tools/honk_co_probe.py [--log FILE] [--sizes 12,16,20] [--example EXE] [--gates] [--gates-example EXE]
 
 With --example (the built examples/honk_sumcheck_from_cpp) the mirror's plain C++ loop of the same four relations on one host thread is
 timed at n = 2^12 and 2^16: the plain form (one value per element, no operand vectors, no products between stages), the only host loop of
 these relations the mirror has.
+
+With --gates the stages of the five gate relations (csrc/honk_co_gates.hip) are timed behind them, then those five relations' round and
+the party's whole round of all nine relations; --gates-example (the built examples/honk_gates_from_cpp) adds the mirror's plain C++ loop
+of the five gate relations at the same two sizes. The selectors of the gate relations are five of the non-zero precomputed columns.
 
 Every figure: the call back to back on the calling thread's stream between two HIP events, after bench.py's spin-up rule (untimed batches
 for at least 0.3 s until two consecutive batch means agree within 2 %, 3 s at the most); the median of 7 such batches, with the lowest and
@@ -36,6 +40,8 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--log", default=None, help="also append the lines to this file")
 ap.add_argument("--sizes", default="12,16,20", help="log2 of the round size")
 ap.add_argument("--example", default=None, help="the built examples/honk_sumcheck_from_cpp, for the host loop")
+ap.add_argument("--gates", action="store_true", help="also the five gate relations and the round of all nine")
+ap.add_argument("--gates-example", default=None, help="the built examples/honk_gates_from_cpp, for the host loop of the five gate relations")
 args = ap.parse_args()
 if not hip.have_device():
     raise SystemExit("honk_co_probe: no HIP device (there is no CPU path to time)")
@@ -90,6 +96,8 @@ settings = {k: B.tune_get(k) for k in ("vec_max_blocks",)}
 print(json.dumps({"settings": settings}), flush=True)
 lines.append({"settings": settings})
 params = random_elements(rs, 3).reshape(-1)
+gate_params = random_elements(rs, 8).reshape(-1)
+GATE_COLUMN_OF = [0, 1, 2, 3, 8, 9, 10, 11, 13, 14, 15, 16, 17, 18] + [19, 20, 21, 22, 23]    # the last five stand in for the gate selectors
 betas = random_elements(rs, 28)
 for lg in (int(x) for x in args.sizes.split(",")):
     n = 1 << lg
@@ -154,6 +162,64 @@ for lg in (int(x) for x in args.sizes.split(",")):
         hip.honk_co_lookup_finish(b, lhs8, acc)
 
     emit("whole round: ten stages + seven local products", n, measure(whole_round, max(2, reps // 4)), edges=m)
+    if args.gates:
+        gb = hip.HonkCoGatesBatch(0, 1, 0, [col[c] for c in GATE_COLUMN_OF], 0, n, None, None, table, 2, gate_params)
+        l7, r7, mul7, l5, r5, mul5, one, gacc = vec(7), vec(7), vec(7), vec(5), vec(5), vec(5), vec(1), hip.DeviceBuffer(SH * 36)
+        hip.honk_co_ell_operands(gb, l7, r7)               # every vector canonical before it is a stage's input
+        hip.honk_co_ell_operands(gb, mul7, r7)
+        hip.honk_co_ell_operands2(gb, mul7, l5, r5)
+        hip.honk_co_ell_operands2(gb, mul7, mul5, r5)
+        hip.honk_co_mem_operands(gb, l7, r7, one)
+        part = lambda v, q: C.c_void_p(v.ptr.value + q * SH * n7)
+        gstages = [
+            ("ell operands", lambda: hip.honk_co_ell_operands(gb, l7, r7), 6 * SH * n + PUB * n + 14 * SH * n7),
+            ("ell operands2", lambda: hip.honk_co_ell_operands2(gb, mul7, l5, r5), 5 * SH * n + 13 * SH * n7),
+            ("ell finish", lambda: hip.honk_co_ell_finish(gb, mul7, mul5, gacc), 3 * PUB * n + sc + 10 * SH * n7),
+            ("mem operands", lambda: hip.honk_co_mem_operands(gb, l7, r7, one), 8 * SH * n + PUB * n + 13 * SH * n7),
+            ("mem finish", lambda: hip.honk_co_mem_finish(gb, mul7, one, gacc), 8 * SH * n + 7 * PUB * n + sc + 7 * SH * n7),
+            ("nnf operands", lambda: hip.honk_co_nnf_operands(gb, l5, r5), 6 * SH * n + 10 * SH * n7),
+            ("nnf finish", lambda: hip.honk_co_nnf_finish(gb, mul5, gacc), 8 * SH * n + 5 * PUB * n + sc + 5 * SH * n7),
+            ("pos_ext operands", lambda: hip.honk_co_pos_ext_operands(gb, l5), 4 * SH * n + 4 * PUB * n + 4 * SH * n7),
+            ("pos_ext finish", lambda: hip.honk_co_pos_ext_finish(gb, mul5, gacc), 4 * SH * n + PUB * n + sc + 4 * SH * n7),
+            ("pos_int operands", lambda: hip.honk_co_pos_int_operands(gb, one), SH * n + PUB * n + SH * n7),
+            ("pos_int finish", lambda: hip.honk_co_pos_int_finish(gb, one, gacc), 7 * SH * n + PUB * n + sc + SH * n7),
+        ]
+        for name, fn, must in gstages:
+            emit(name, n, measure(fn, reps), must, edges=m)
+
+        def sbox(s, u, w, count):                          # s^5: three local products
+            local_mul(s.ptr.value, s.ptr.value, u, count)
+            local_mul(u.ptr.value, u.ptr.value, w, count)
+            local_mul(w.ptr.value, s.ptr.value, u, count)
+
+        def gates_round():
+            hip.honk_co_ell_operands(gb, l7, r7)
+            local_mul(l7.ptr.value, r7.ptr.value, mul7, 7 * n7)
+            hip.honk_co_ell_operands2(gb, mul7, l5, r5)
+            local_mul(l5.ptr.value, r5.ptr.value, mul5, 5 * n7)
+            hip.honk_co_ell_finish(gb, mul7, mul5, gacc)
+            hip.honk_co_mem_operands(gb, l7, r7, one)
+            local_mul(l7.ptr.value, r7.ptr.value, mul7, 6 * n7)
+            local_mul(part(mul7, 3).value, one.ptr.value, mul5, n7)
+            hip.honk_co_mem_finish(gb, mul7, mul5, gacc)
+            hip.honk_co_nnf_operands(gb, l5, r5)
+            local_mul(l5.ptr.value, r5.ptr.value, mul5, 5 * n7)
+            hip.honk_co_nnf_finish(gb, mul5, gacc)
+            hip.honk_co_pos_ext_operands(gb, l5)
+            sbox(l5, mul5, r5, 4 * n7)
+            hip.honk_co_pos_ext_finish(gb, mul5, gacc)
+            hip.honk_co_pos_int_operands(gb, one)
+            sbox(one, mul5, r5, n7)
+            hip.honk_co_pos_int_finish(gb, mul5, gacc)
+
+        def nine_relations():
+            whole_round()
+            gates_round()
+
+        emit("gate relations: eleven stages + eleven local products", n, measure(gates_round, max(2, reps // 4)), edges=m)
+        emit("whole round of nine relations: 21 stages + 18 local products", n, measure(nine_relations, max(2, reps // 4)), edges=m)
+        for x in (l7, r7, mul7, l5, r5, mul5, one):
+            x.free()
     for x in (pool, table, mask, half, lhs8, rhs4, mul_out):
         x.free()
 if args.example:
@@ -170,6 +236,23 @@ if args.example:
                 raise SystemExit("honk_co_probe: %s failed: %s" % (args.example, r.stderr))
             us_host = int(np.fromfile(fout, dtype="<u8")[-1])
         line = {"op": "host_loop (plain C++, one thread, the plain form of the four relations)", "n": n, "ms": round(us_host / 1000, 3), "edges": n // 2}
+        lines.append(line)
+        print(json.dumps(line), flush=True)
+if args.gates_example:
+    for lg in (12, 16):
+        n = 1 << lg
+        with tempfile.TemporaryDirectory() as d:
+            head = np.array([0, n, 0, n, lg, 2, 0], dtype=np.uint64)
+            one = np.array([1, 0, 0, 0], dtype=np.uint64)
+            words = [head, params, one, random_elements(rs, lg).reshape(-1), random_elements(rs, 27).reshape(-1), gate_params,
+                     random_elements(rs, (COLS + 5) * n).reshape(-1)]
+            fin, fout = os.path.join(d, "in.bin"), os.path.join(d, "out.bin")
+            np.concatenate(words).astype("<u8").tofile(fin)
+            r = subprocess.run([args.gates_example, fin, fout], capture_output=True, text=True, timeout=600)
+            if r.returncode != 0:
+                raise SystemExit("honk_co_probe: %s failed: %s" % (args.gates_example, r.stderr))
+            us_host = int(np.fromfile(fout, dtype="<u8")[-1])
+        line = {"op": "host_loop (plain C++, one thread, the plain form of the five gate relations)", "n": n, "ms": round(us_host / 1000, 3), "edges": n // 2}
         lines.append(line)
         print(json.dumps(line), flush=True)
 if args.log:
