@@ -984,6 +984,110 @@ def honk_co_pos_int_finish(b: HonkCoGatesBatch, u1, acc=None, stream=None):
     return acc
 
 
+# ---- batched Poseidon2 (csrc/poseidon2.hip): one wrapper per entry of include/cosnarks_hip.h -----------------------------------------
+POSEIDON2_SPONGE, POSEIDON2_COMPRESSION = 0, 1
+
+
+def _poseidon2_tree_rules(what, t, arity, mode, n_leaves=1):
+    if mode not in (POSEIDON2_SPONGE, POSEIDON2_COMPRESSION):
+        raise CoSnarksHipError("%s: mode must be 0 (sponge) or 1 (compression)" % what)
+    if arity < 2 or (t <= arity if mode == POSEIDON2_SPONGE else t < arity):
+        raise CoSnarksHipError("%s: arity must be at least 2, below t in sponge mode and at most t in compression mode" % what)
+    v = n_leaves
+    while v > 1 and v % arity == 0:
+        v //= arity
+    if v != 1:
+        raise CoSnarksHipError("%s: n_leaves must be a power of the arity" % what)
+
+
+class Poseidon2Params:
+    """csh_poseidon2_params_create: one parameter set on the device (the fields of the reference's Poseidon2Params; the library builds in
+    none). rc_external: (rounds_f_beginning + rounds_f_end) * t host elements, rc_internal: rounds_p, diag_m_1: t."""
+
+    def __init__(self, curve: int, t: int, rounds_f_beginning: int, rounds_f_end: int, rounds_p: int, rc_external, rc_internal, diag_m_1):
+        if t not in (2, 3, 4):
+            raise CoSnarksHipError("Poseidon2Params: t must be 2, 3 or 4 (d = 5)")
+        if min(rounds_f_beginning, rounds_f_end, rounds_p) < 0:
+            raise CoSnarksHipError("Poseidon2Params: a negative round count")
+        ext, inn, diag = _u64(rc_external), _u64(rc_internal), _u64(diag_m_1)
+        if ext.size != 4 * (rounds_f_beginning + rounds_f_end) * t or inn.size != 4 * rounds_p or diag.size != 4 * t:
+            raise CoSnarksHipError("Poseidon2Params: rc_external holds (rounds_f_beginning + rounds_f_end) * t elements, rc_internal rounds_p, diag_m_1 t")
+        self.curve, self.t, self.rf_b, self.rf_e, self.rp = curve, t, rounds_f_beginning, rounds_f_end, rounds_p
+        self.h = C.c_void_p()
+        _check(lib().csh_poseidon2_params_create(curve, C.c_uint32(t), C.c_uint32(rounds_f_beginning), C.c_uint32(rounds_f_end), C.c_uint32(rounds_p),
+                                                 _p(ext) if ext.size else None, _p(inn) if inn.size else None, _p(diag), C.byref(self.h)))
+
+    @property
+    def rounds(self):
+        return self.rf_b + self.rp + self.rf_e
+
+    def round_entries(self, r: int, n_perm: int) -> int:
+        """precomputation entries round r consumes: n_perm * t in an external round, n_perm in an internal one"""
+        return n_perm * self.t if (r < self.rf_b or r >= self.rf_b + self.rp) else n_perm
+
+    def free(self):
+        if self.h:
+            lib().csh_poseidon2_params_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def poseidon2_permute(params: Poseidon2Params, state, n_perm: int, out=None, stream=None):
+    """csh_poseidon2_permute_dev: n_perm states of t elements; out (default: in place) is returned."""
+    out = out if out is not None else state
+    _check(lib().csh_poseidon2_permute_dev(params.h, _devptr(state), C.c_size_t(n_perm), _devptr(out), _stream(stream)))
+    return out
+
+
+def poseidon2_merkle(params: Poseidon2Params, arity: int, mode: int, leaves, n_leaves: int, root=None, work=None, stream=None):
+    """csh_poseidon2_merkle_dev: the root (one element, returned as a DeviceBuffer) of n_leaves = arity^k leaves."""
+    _poseidon2_tree_rules("poseidon2_merkle", params.t, arity, mode, n_leaves)
+    root = root if root is not None else DeviceBuffer(32)
+    if work is None and n_leaves > arity:
+        work = DeviceBuffer(32 * 2 * (n_leaves // arity))
+    _check(lib().csh_poseidon2_merkle_dev(params.h, C.c_uint32(arity), C.c_uint32(mode), _devptr(leaves), C.c_size_t(n_leaves), _devptr(root),
+                                          _devptr(work), _stream(stream)))
+    return root
+
+
+def poseidon2_co_round(curve: int, protocol: int, party: int, params: Poseidon2Params, step: int, state, n_perm: int, y, precomp,
+                       precomp_offset: int, open_out=None, ff_out=None, stream=None):
+    """csh_poseidon2_co_round_dev: step `step` of 0 .. params.rounds on n_perm states of shares, in place. y: the opened values of the round
+    before (None at step 0); precomp: the five DeviceBuffers r, r^2, r^3, r^4, r^5; precomp_offset: the offset of round `step`.
+    -> open_out (the shares to open; None at the last step)."""
+    if protocol not in (0, 1) or party not in (0, 1, 2):
+        raise CoSnarksHipError("poseidon2_co_round: protocol must be 0 (plain / Shamir) or 1 (Rep3), party_id 0, 1 or 2")
+    if not 0 <= step <= params.rounds:
+        raise CoSnarksHipError("poseidon2_co_round: step must be 0 .. rounds_f_beginning + rounds_p + rounds_f_end")
+    if len(precomp) != 5:
+        raise CoSnarksHipError("poseidon2_co_round: precomp holds the five vectors r, r^2, r^3, r^4, r^5")
+    if step < params.rounds and open_out is None:
+        open_out = DeviceBuffer(max(32 * (protocol + 1) * params.round_entries(step, n_perm), 32))
+    _check(lib().csh_poseidon2_co_round_dev(curve, C.c_uint32(protocol), C.c_uint32(party), params.h, C.c_uint32(step), _devptr(state),
+                                            C.c_size_t(n_perm), _devptr(y), _devptr_array(precomp), C.c_size_t(precomp_offset), _devptr(open_out),
+                                            _devptr(ff_out), _stream(stream)))
+    return open_out
+
+
+def poseidon2_layer_next(curve: int, ncomp: int, t: int, arity: int, mode: int, state, ff, length: int, next_out=None, stream=None):
+    """csh_poseidon2_layer_next_dev: the length / arity states of the next layer of a collaborative tree (length == 1: the root's share)."""
+    if t not in (2, 3, 4):
+        raise CoSnarksHipError("poseidon2_layer_next: t must be 2, 3 or 4")
+    _poseidon2_tree_rules("poseidon2_layer_next", t, arity, mode)
+    if length < 1 or (length != 1 and length % arity):
+        raise CoSnarksHipError("poseidon2_layer_next: len must be 1 or a multiple of the arity")
+    if next_out is None:
+        next_out = DeviceBuffer(32 * ncomp * (1 if length == 1 else length // arity * t))
+    _check(lib().csh_poseidon2_layer_next_dev(curve, C.c_uint32(ncomp), C.c_uint32(t), C.c_uint32(arity), C.c_uint32(mode), _devptr(state),
+                                              _devptr(ff), _devptr(next_out), C.c_size_t(length), _stream(stream)))
+    return next_out
+
+
 def rep3_local_mul_vec(curve: int, lhs_ab, rhs_ab, mask=None):
     l, r = _u64(lhs_ab), _u64(rhs_ab)
     n = l.size // 8

@@ -21,6 +21,7 @@
 #include "msm_digits.hpp"
 #include "plonk_quot.hpp"
 #include "plonk_rounds.hpp"
+#include "poseidon2.hpp"
 #include "vec_elem.hpp"
 
 using namespace csh;
@@ -771,7 +772,41 @@ static int honk_pow_table_host_t(const uint64_t* betas, size_t m, uint64_t* out)
   return CSH_OK;
 }
 
+// The per-state functions of poseidon2.hpp on host arrays, dealt to no lanes, with the limb-bound checks of field29.hpp on.
+// op 0: the plain kernel's body on n states (arg = take, flags bit 0 = the whole state is written, bit 1 = feed-forward): in -> out.
+// op 1: step `arg` of the collaborative permutation on n states: `in` is copied to `out` (n t ncomp values), which is the state.
+template <class F>
+static int poseidon2_host_t(uint32_t t, uint32_t rf_b, uint32_t rf_e, uint32_t rp, const uint64_t* rc_ext, const uint64_t* rc_int, const uint64_t* diag,
+                            int op, uint32_t protocol, uint32_t party, uint32_t arg, uint32_t flags, const uint64_t* in, size_t n, const uint64_t* y,
+                            const uint64_t* const* pre, size_t pre_off, uint64_t* out, uint64_t* open, uint64_t* ff_out) {
+  std::vector<F> store;
+  P2Table<F> tab;
+  p2_build_table(t, rf_b, rf_e, rp, rc_ext, rc_int, diag, store, tab);
+  p2_point_table(tab, store.data());
+  if (op == 0) {
+    const P2PlainArgs<F> a{tab, (const F*)in, (F*)out, n, arg, flags & 1, (flags >> 1) & 1};
+    for (size_t i = 0; i < n; ++i) t == 2 ? p2_plain_at<F, 2>(a, i) : t == 3 ? p2_plain_at<F, 3>(a, i) : p2_plain_at<F, 4>(a, i);
+    return CSH_OK;
+  }
+  P2CoArgs<F> a;
+  a.tab = tab, a.ncomp = protocol + 1, a.pub_comp = pq_pub_comp(protocol, party), a.step = arg, a.n_perm = n, a.pre_off = pre_off;
+  memcpy(out, in, sizeof(F) * n * t * a.ncomp);
+  a.state = (F*)out, a.y = (const F*)y, a.open = (F*)open, a.ff_out = arg == 0 ? (F*)ff_out : nullptr;
+  for (int k = 0; k < 5; ++k) a.pre[k] = (const F*)pre[k];
+  for (size_t u = 0; u < n * a.ncomp; ++u) t == 2 ? p2_co_step_at<F, 2>(a, u) : t == 3 ? p2_co_step_at<F, 3>(a, u) : p2_co_step_at<F, 4>(a, u);
+  return CSH_OK;
+}
+
 extern "C" {
+
+int csh_selftest_poseidon2_host(int field_of, uint32_t t, uint32_t rf_b, uint32_t rf_e, uint32_t rp, const uint64_t* rc_ext, const uint64_t* rc_int,
+                                const uint64_t* diag, int op, uint32_t protocol, uint32_t party, uint32_t arg, uint32_t flags, const uint64_t* in, size_t n,
+                                const uint64_t* y, const uint64_t* const* pre, size_t pre_off, uint64_t* out, uint64_t* open, uint64_t* ff_out) {
+  if (t < 2 || t > 4 || op < 0 || op > 1 || protocol > 1 || party > 2 || !diag || !in || !out || (op == 1 && !pre)) return CSH_ERR_INVALID;
+  if (op == 0 && (arg < 1 || arg > t)) return CSH_ERR_INVALID;
+  if (op == 1 && (arg > rf_b + rp + rf_e || pre_off < (arg ? ((arg - 1 < rf_b || arg - 1 >= rf_b + rp) ? n * t : n) : 0))) return CSH_ERR_INVALID;
+  return FR_CALL(field_of, poseidon2_host_t<F>(t, rf_b, rf_e, rp, rc_ext, rc_int, diag, op, protocol, party, arg, flags, in, n, y, pre, pre_off, out, open, ff_out));
+}
 
 int csh_selftest_plonk_quot_host(int field_of, int stage, const uint64_t* gen, size_t N, uint32_t protocol, uint32_t party, const uint64_t* const* in,
                                  size_t n_public, const uint64_t* scalars, uint64_t* const* out) {

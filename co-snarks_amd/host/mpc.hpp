@@ -453,4 +453,355 @@ struct ShamirGroth16Driver {
   }
 };
 
+// ================================= Poseidon2 (mpc-core/src/gadgets/poseidon2, gadgets/merkle_tree) =================================
+// One party of a Poseidon2 computation: what arithmetic::rand, arithmetic::mul_vec and arithmetic::open_vec are for it. A share vector is a
+// flat vector of NCOMP field elements per share, the layout of the device entries (Rep3: a, b interleaved, which is Rep3PrimeFieldShare).
+//   PROTOCOL, NCOMP, party()   the protocol, ncomp and party_id of the device entries
+//   rand_vec(n)                n fresh random shares
+//   mul_vec(a, b)              shares of the products: the local multiplication on the device and the party's network round
+//   open_vec(x)                the opened values, one element per share
+// Plain: one party holding the values themselves (the Poseidon2 of poseidon2_permutation.rs run through the same rounds).
+template <class P>
+struct Poseidon2PlainParty {
+  using Fr = typename P::Fr;
+  static constexpr uint32_t PROTOCOL = 0, NCOMP = 1;
+  ChaCha12 rng;  // the caller's key
+  explicit Poseidon2PlainParty(const uint8_t seed[32]) : rng(seed) {}
+  uint32_t party() const { return 0; }
+  std::vector<Fr> rand_vec(size_t n) {
+    std::vector<Fr> r(n);
+    for (auto& x : r) {
+      uint8_t b[32];
+      rng.fill_bytes(b, 32);
+      x = from_be_bytes_mod_order<Fr>(b);
+    }
+    return r;
+  }
+  std::vector<Fr> mul_vec(const std::vector<Fr>& a, const std::vector<Fr>& b) {
+    UnitState st;
+    return PlainGroth16Driver<P>::local_mul_vec(a, b, st);
+  }
+  std::vector<Fr> open_vec(const std::vector<Fr>& x) { return x; }
+};
+
+// Rep3 (rep3/arithmetic.rs): rand :357-360, mul_vec :148-161 (local_mul_vec + reshare), open_vec :249-271
+template <class P>
+struct Poseidon2Rep3Party {
+  using Fr = typename P::Fr;
+  static constexpr uint32_t PROTOCOL = 1, NCOMP = 2;
+  const LocalNetwork& net;
+  Rep3State& st;
+  uint32_t party() const { return (uint32_t)st.id; }
+  std::vector<Fr> rand_vec(size_t n) {
+    std::vector<Fr> r(2 * n);
+    for (size_t i = 0; i < n; ++i) {
+      auto [a, b] = st.rand.template random_fes<Fr>();
+      r[2 * i] = a, r[2 * i + 1] = b;
+    }
+    return r;
+  }
+  std::vector<Fr> exchange(const std::vector<Fr>& mine) {  // reshare_many: to the next party, from the previous one
+    const size_t bytes = sizeof(Fr) * mine.size();
+    Bytes b(bytes);
+    if (bytes) memcpy(b.data(), mine.data(), bytes);
+    net.send((net.id() + 1) % 3, std::move(b));
+    const Bytes r = net.recv((net.id() + 2) % 3);
+    if (r.size() != bytes) throw Error("Poseidon2Rep3Party: invalid number of elements received");
+    std::vector<Fr> prev(mine.size());
+    if (bytes) memcpy((void*)prev.data(), r.data(), bytes);
+    return prev;
+  }
+  std::vector<Fr> mul_vec(const std::vector<Fr>& a, const std::vector<Fr>& b) {
+    const size_t n = a.size() / 2;
+    const UninitBuf<Fr> mask = st.rand.template masking_field_elements_vec<Fr>(n);
+    std::vector<Fr> half(n);
+    check(csh_rep3_local_mul_vec(P::ID, (const uint64_t*)a.data(), (const uint64_t*)b.data(), (const uint64_t*)mask.data(), (uint64_t*)half.data(), n),
+          "csh_rep3_local_mul_vec");
+    const std::vector<Fr> prev = exchange(half);
+    std::vector<Fr> out(2 * n);
+    for (size_t i = 0; i < n; ++i) out[2 * i] = half[i], out[2 * i + 1] = prev[i];
+    return out;
+  }
+  std::vector<Fr> open_vec(const std::vector<Fr>& x) {
+    const size_t n = x.size() / 2;
+    std::vector<Fr> bs(n);
+    for (size_t i = 0; i < n; ++i) bs[i] = x[2 * i + 1];
+    const std::vector<Fr> cs = exchange(bs);
+    std::vector<Fr> y(n);
+    for (size_t i = 0; i < n; ++i) y[i] = Fr::add(Fr::add(x[2 * i], x[2 * i + 1]), cs[i]);
+    return y;
+  }
+};
+
+// Shamir (shamir/arithmetic.rs): rand = the degree-t half of a double sharing, mul_vec :81-94 (local products + degree_reduce_many,
+// shamir/network.rs:150-241, king = party 0), open_vec :233-247 (broadcast_next(n, t + 1), network.rs:96-126, and open_lagrange_t)
+template <class P>
+struct Poseidon2ShamirParty {
+  using Fr = typename P::Fr;
+  static constexpr uint32_t PROTOCOL = 0, NCOMP = 1;
+  const LocalNetwork& net;
+  ShamirState<Fr>& st;
+  uint32_t party() const { return (uint32_t)st.id; }
+  std::vector<Fr> rand_vec(size_t n) {
+    std::vector<Fr> r(n);
+    for (auto& x : r) x = st.get_pair().first;
+    return r;
+  }
+  static Bytes pack(const std::vector<Fr>& v) {
+    Bytes b(sizeof(Fr) * v.size());
+    if (!v.empty()) memcpy(b.data(), v.data(), b.size());
+    return b;
+  }
+  std::vector<Fr> recv_many(int from, size_t len) {
+    const Bytes r = net.recv(from);
+    if (r.size() != sizeof(Fr) * len) throw Error("Poseidon2ShamirParty: invalid number of elements received");
+    std::vector<Fr> v(len);
+    if (len) memcpy((void*)v.data(), r.data(), r.size());
+    return v;
+  }
+  std::vector<Fr> mul_vec(const std::vector<Fr>& a, const std::vector<Fr>& b) {
+    const size_t n = st.num_parties, t = st.threshold, num_non_zero = n - t, len = a.size();
+    std::vector<Fr> in(len), r_ts(len);
+    check(csh_vec_mul(P::ID, (const uint64_t*)a.data(), (const uint64_t*)b.data(), (uint64_t*)in.data(), len), "csh_vec_mul");
+    for (size_t i = 0; i < len; ++i) {
+      auto [r_t, r_2t] = st.get_pair();
+      in[i] = Fr::add(in[i], r_2t);
+      r_ts[i] = r_t;
+    }
+    std::vector<Fr> mine(len, Fr::zero());
+    if (st.id == 0) {
+      std::vector<std::vector<Fr>> got{in};
+      for (size_t other = 1; other < st.mul_lagrange_2t.size(); ++other) got.push_back(recv_many((int)other, len));
+      std::vector<const uint64_t*> parts;
+      for (auto& g : got) parts.push_back((const uint64_t*)g.data());
+      std::vector<Fr> acc(len);
+      check(csh_lincomb(P::ID, parts.data(), (const uint64_t*)st.mul_lagrange_2t.data(), parts.size(), (uint64_t*)acc.data(), len), "csh_lincomb");
+      for (size_t id = 0; id < num_non_zero; ++id) {  // acc * q(X) at X = id + 1: q(0) = 1 and the last t parties' shares are zero
+        Fr x = Fr::from_u64(id + 1), e = Fr::zero();
+        for (size_t k = st.mul_reconstruct_with_zeros.size(); k-- > 0;) e = Fr::add(Fr::mul(e, x), st.mul_reconstruct_with_zeros[k]);
+        std::vector<Fr> vals(len);
+        for (size_t i = 0; i < len; ++i) vals[i] = Fr::mul(acc[i], e);
+        if (id == 0) mine = std::move(vals);
+        else net.send((int)id, pack(vals));
+      }
+    } else {
+      if ((size_t)st.id <= 2 * t) net.send(0, pack(in));
+      if ((size_t)st.id < num_non_zero) mine = recv_many(0, len);
+    }
+    for (size_t i = 0; i < len; ++i) mine[i] = Fr::sub(mine[i], r_ts[i]);
+    return mine;
+  }
+  std::vector<Fr> open_vec(const std::vector<Fr>& x) {
+    const size_t n = st.num_parties, num = st.threshold + 1;
+    for (size_t s = 1; s < num; ++s) net.send((int)((st.id + s) % n), pack(x));
+    std::vector<std::vector<Fr>> got;
+    for (size_t r = 1; r < num; ++r) got.push_back(recv_many((int)((st.id + n - r) % n), x.size()));
+    std::vector<const uint64_t*> parts{(const uint64_t*)x.data()};
+    for (auto& g : got) parts.push_back((const uint64_t*)g.data());
+    std::vector<Fr> y(x.size());
+    check(csh_lincomb(P::ID, parts.data(), (const uint64_t*)st.open_lagrange_t.data(), num, (uint64_t*)y.data(), y.size()), "csh_lincomb");
+    return y;
+  }
+};
+
+// Poseidon2<F, T, 5> over the device entries (csrc/poseidon2.hip): the caller's parameter set (the fields of Poseidon2Params) is uploaded once;
+// the methods carry the reference's names. The collaborative ones take a party (above) and run every stretch of local arithmetic between two
+// openings as one csh_poseidon2_co_round_dev; state and precomputation stay on the device, the shares to open and the opened values cross.
+template <class P>
+struct Poseidon2Hip {
+  using Fr = typename P::Fr;
+  static constexpr uint32_t SPONGE = 0, COMPRESSION = 1;
+  struct Precomputations {  // Poseidon2Precomputations (poseidon2/mod.rs): five share vectors and the offset the next round reads at
+    std::vector<Fr> r, r2, r3, r4, r5;
+    size_t offset = 0;
+  };
+  struct Dev {  // csh_malloc / csh_free
+    void* p = nullptr;
+    explicit Dev(size_t bytes) { check(csh_malloc(&p, bytes ? bytes : 1), "csh_malloc"); }
+    explicit Dev(const std::vector<Fr>& v) : Dev(sizeof(Fr) * v.size()) {
+      if (!v.empty()) check(csh_memcpy_h2d(p, v.data(), sizeof(Fr) * v.size()), "csh_memcpy_h2d");
+    }
+    Dev(const Dev&) = delete;
+    Dev& operator=(const Dev&) = delete;
+    ~Dev() { csh_free(p); }
+    uint64_t* w() const { return (uint64_t*)p; }
+    std::vector<Fr> down(size_t count) const {
+      std::vector<Fr> v(count);
+      if (count) check(csh_memcpy_d2h(v.data(), p, sizeof(Fr) * count), "csh_memcpy_d2h");
+      return v;
+    }
+  };
+
+  const uint32_t t, rounds_f_beginning, rounds_f_end, rounds_p;
+  const std::vector<Fr> rc_external, rc_internal, diag_m_1;  // the host's copy, for permutation_in_place
+  csh_poseidon2_params_t handle = nullptr;
+
+  Poseidon2Hip(uint32_t t_, uint32_t rf_b, uint32_t rf_e, uint32_t rp, const std::vector<Fr>& round_constants_external,
+               const std::vector<Fr>& round_constants_internal, const std::vector<Fr>& mat_internal_diag_m_1)
+      : t(t_), rounds_f_beginning(rf_b), rounds_f_end(rf_e), rounds_p(rp), rc_external(round_constants_external),
+        rc_internal(round_constants_internal), diag_m_1(mat_internal_diag_m_1) {
+    if (round_constants_external.size() != (size_t)(rf_b + rf_e) * t || round_constants_internal.size() != rp || mat_internal_diag_m_1.size() != t)
+      throw Error("Poseidon2Hip: the constants do not have the lengths of the round numbers");
+    check(csh_poseidon2_params_create(P::ID, t, rf_b, rf_e, rp, (const uint64_t*)round_constants_external.data(), (const uint64_t*)round_constants_internal.data(),
+                                      (const uint64_t*)mat_internal_diag_m_1.data(), &handle), "csh_poseidon2_params_create");
+  }
+  Poseidon2Hip(const Poseidon2Hip&) = delete;
+  Poseidon2Hip& operator=(const Poseidon2Hip&) = delete;
+  ~Poseidon2Hip() { csh_poseidon2_params_destroy(handle); }
+
+  size_t rounds() const { return (size_t)rounds_f_beginning + rounds_p + rounds_f_end; }
+  size_t num_sbox() const { return (size_t)(rounds_f_beginning + rounds_f_end) * t + rounds_p; }  // poseidon2_permutation.rs:41-43
+  bool is_external(size_t round) const { return round < rounds_f_beginning || round >= (size_t)rounds_f_beginning + rounds_p; }
+
+  // The plain permutation of one state on the host, as the reference writes it (poseidon2_permutation.rs:67-214): what one thread of the
+  // reference does per state, the baseline the device batch is measured against (tools/poseidon2_probe.py). Not a fall-back of anything.
+  void matmul_external_host(Fr* s) const {
+    if (t == 4) {  // matmul_m4, :67-80
+      const Fr t0 = Fr::add(s[0], s[1]), t1 = Fr::add(s[2], s[3]);
+      const Fr t2 = Fr::add(Fr::add(s[1], s[1]), t1), t3 = Fr::add(Fr::add(s[3], s[3]), t0);
+      Fr t4 = Fr::add(t1, t1), t5 = Fr::add(t0, t0);
+      t4 = Fr::add(Fr::add(t4, t4), t3), t5 = Fr::add(Fr::add(t5, t5), t2);
+      s[0] = Fr::add(t3, t5), s[1] = t5, s[2] = Fr::add(t2, t4), s[3] = t4;
+      return;
+    }
+    Fr sum = s[0];
+    for (uint32_t i = 1; i < t; ++i) sum = Fr::add(sum, s[i]);
+    for (uint32_t i = 0; i < t; ++i) s[i] = Fr::add(s[i], sum);
+  }
+  void matmul_internal_host(Fr* s) const {  // :126-162
+    Fr sum = s[0];
+    for (uint32_t i = 1; i < t; ++i) sum = Fr::add(sum, s[i]);
+    if (t == 4) {
+      for (uint32_t i = 0; i < 4; ++i) s[i] = Fr::add(Fr::mul(s[i], diag_m_1[i]), sum);
+      return;
+    }
+    s[t - 1] = Fr::add(s[t - 1], s[t - 1]);
+    for (uint32_t i = 0; i < t; ++i) s[i] = Fr::add(s[i], sum);
+  }
+  static Fr sbox_host(const Fr& x) {
+    const Fr x2 = Fr::mul(x, x);
+    return Fr::mul(Fr::mul(x2, x2), x);
+  }
+  void permutation_in_place(Fr* s) const {
+    matmul_external_host(s);
+    const size_t R = rounds();
+    for (size_t r = 0; r < R; ++r) {
+      if (is_external(r)) {
+        const Fr* rc = &rc_external[(r < rounds_f_beginning ? r : r - rounds_p) * t];
+        for (uint32_t i = 0; i < t; ++i) s[i] = sbox_host(Fr::add(s[i], rc[i]));
+        matmul_external_host(s);
+      } else {
+        s[0] = sbox_host(Fr::add(s[0], rc_internal[r - rounds_f_beginning]));
+        matmul_internal_host(s);
+      }
+    }
+  }
+
+  // permutation_in_place over chunks_exact_mut(T) of plain states (poseidon2_permutation.rs:194-214), one launch
+  std::vector<Fr> permutation_packed(const std::vector<Fr>& states) const {
+    if (states.size() % t) throw Error("Poseidon2Hip: the state vector is no multiple of t");
+    Dev d(states);
+    check(csh_poseidon2_permute_dev(handle, d.w(), states.size() / t, d.w(), nullptr), "csh_poseidon2_permute_dev");
+    return d.down(states.size());
+  }
+  // merkle_tree_sponge / merkle_tree_compression on plain leaves (merkle_tree/plain.rs:15-50, :113-155)
+  Fr merkle_tree_plain(const std::vector<Fr>& leaves, uint32_t arity, uint32_t mode) const {
+    Dev in(leaves), root(sizeof(Fr)), work(2 * sizeof(Fr) * (leaves.size() / (arity ? arity : 1)));
+    check(csh_poseidon2_merkle_dev(handle, arity, mode, in.w(), leaves.size(), root.w(), work.w(), nullptr), "csh_poseidon2_merkle_dev");
+    return root.down(1)[0];
+  }
+  Fr merkle_tree_sponge(const std::vector<Fr>& leaves, uint32_t arity) const { return merkle_tree_plain(leaves, arity, SPONGE); }
+  Fr merkle_tree_compression(const std::vector<Fr>& leaves, uint32_t arity) const { return merkle_tree_plain(leaves, arity, COMPRESSION); }
+
+  // precompute_rep3 / precompute_shamir (rep3.rs:12-51, shamir.rs:35-73): r, then r^2, r^4 and [r^3 | r^5] = [r | r] [r^2 | r^4] by three
+  // multiplications, each the existing local product on the device and the party's network round
+  template <class Party>
+  Precomputations precompute(Party& party, size_t num_poseidon) const {
+    const size_t n = num_sbox() * num_poseidon, w = Party::NCOMP * n;
+    Precomputations pre;
+    pre.r = party.rand_vec(n);
+    pre.r2 = party.mul_vec(pre.r, pre.r);
+    pre.r4 = party.mul_vec(pre.r2, pre.r2);
+    std::vector<Fr> lhs(pre.r), rhs(pre.r2);
+    lhs.insert(lhs.end(), pre.r.begin(), pre.r.end());
+    rhs.insert(rhs.end(), pre.r4.begin(), pre.r4.end());
+    pre.r3 = party.mul_vec(lhs, rhs);
+    pre.r5.assign(pre.r3.begin() + w, pre.r3.end());
+    pre.r3.resize(w);
+    return pre;
+  }
+
+  // the five vectors of a precomputation on the device, in the order of csh_poseidon2_co_round_dev
+  struct DevicePrecomputations {
+    Dev r, r2, r3, r4, r5;
+    const uint64_t* ptrs[5];
+    explicit DevicePrecomputations(const Precomputations& pre) : r(pre.r), r2(pre.r2), r3(pre.r3), r4(pre.r4), r5(pre.r5), ptrs{r.w(), r2.w(), r3.w(), r4.w(), r5.w()} {}
+  };
+  // {rep3,shamir}_permutation_in_place_with_precomputation_packed (rep3.rs:612-648, shamir.rs:326-365) on n_perm states on the device:
+  // R + 1 steps with an opening between two of them. ff_dev (may be NULL): the feed-forward of the compression tree.
+  template <class Party>
+  void permutation_on_device(Party& party, uint64_t* state_dev, size_t n_perm, const DevicePrecomputations& pre, size_t entries, size_t& offset,
+                             uint64_t* ff_dev) const {
+    if (offset + num_sbox() * n_perm > entries) throw Error("Poseidon2Hip: the precomputation is too short for these permutations");
+    const size_t R = rounds();
+    Dev open_dev(sizeof(Fr) * Party::NCOMP * n_perm * t), y_dev(sizeof(Fr) * n_perm * t);
+    for (size_t s = 0; s <= R; ++s) {
+      check(csh_poseidon2_co_round_dev(P::ID, Party::PROTOCOL, party.party(), handle, (uint32_t)s, state_dev, n_perm, s ? y_dev.w() : nullptr, pre.ptrs, offset,
+                                       s < R ? open_dev.w() : nullptr, s == 0 ? ff_dev : nullptr, nullptr), "csh_poseidon2_co_round_dev");
+      if (s == R) break;
+      const size_t count = is_external(s) ? n_perm * t : n_perm;
+      const std::vector<Fr> y = party.open_vec(open_dev.down(Party::NCOMP * count));
+      if (y.size() != count) throw Error("Poseidon2Hip: open_vec returned a vector of another length");
+      if (count) check(csh_memcpy_h2d(y_dev.p, y.data(), sizeof(Fr) * count), "csh_memcpy_h2d");
+      offset += count;
+    }
+    check(csh_sync(nullptr), "csh_sync");  // the last step still reads y_dev
+  }
+  template <class Party>
+  void permutation_in_place_with_precomputation_packed(Party& party, std::vector<Fr>& state, Precomputations& pre) const {
+    if (state.size() % ((size_t)Party::NCOMP * t)) throw Error("Poseidon2Hip: the state vector is no multiple of t shares");
+    const size_t n_perm = state.size() / Party::NCOMP / t;
+    Dev st(state);
+    const DevicePrecomputations dpre(pre);
+    permutation_on_device(party, st.w(), n_perm, dpre, pre.r.size() / Party::NCOMP, pre.offset, nullptr);
+    state = st.down(state.size());
+  }
+
+  // merkle_tree_sponge_rep3 / merkle_tree_compression_rep3 (merkle_tree/rep3.rs:10-56, :59-115) and their Shamir forms (merkle_tree/shamir.rs):
+  // the precomputation for all (len - 1) / (arity - 1) hashes, then layer after layer; the gather between two layers is
+  // csh_poseidon2_layer_next_dev, so no layer returns to the host. -> the root's share
+  template <class Party>
+  std::vector<Fr> merkle_tree_shared(Party& party, const std::vector<Fr>& leaves, uint32_t arity, uint32_t mode) const {
+    constexpr size_t nc = Party::NCOMP;
+    size_t len = leaves.size() / nc, pw = 1;
+    while (arity >= 2 && pw < len && len % (pw * arity) == 0) pw *= arity;
+    if (arity < 2 || len < arity || pw != len || (mode == SPONGE ? t <= arity : t < arity) || mode > COMPRESSION)
+      throw Error("Poseidon2Hip: the number of leaves must be a power of the arity; sponge mode needs t > arity, compression t >= arity");
+    Precomputations pre = precompute(party, (len - 1) / (arity - 1));
+    const DevicePrecomputations dpre(pre);
+    const size_t entries = pre.r.size() / nc;
+    // the first layer's states: `arity` leaves and zeros after them (:25-33, :74-87; nothing is padded at t == arity)
+    std::vector<Fr> first(nc * (len / arity) * t, Fr::zero());
+    for (size_t i = 0; i < len / arity; ++i)
+      for (size_t j = 0; j < arity * nc; ++j) first[nc * i * t + j] = leaves[nc * i * arity + j];
+    Dev a(first), b(sizeof(Fr) * first.size()), ff(sizeof(Fr) * nc * (len / arity));
+    Dev *cur = &a, *nxt = &b;
+    while (len > 1) {
+      len /= arity;
+      permutation_on_device(party, cur->w(), len, dpre, entries, pre.offset, mode == COMPRESSION ? ff.w() : nullptr);
+      check(csh_poseidon2_layer_next_dev(P::ID, nc, t, arity, mode, cur->w(), mode == COMPRESSION ? ff.w() : nullptr, nxt->w(), len, nullptr),
+            "csh_poseidon2_layer_next_dev");
+      std::swap(cur, nxt);
+    }
+    if (pre.offset != entries) throw Error("Poseidon2Hip: the tree did not use up its precomputation");
+    return cur->down(nc);
+  }
+  template <class Party>
+  std::vector<Fr> merkle_tree_sponge_shared(Party& party, const std::vector<Fr>& leaves, uint32_t arity) const { return merkle_tree_shared(party, leaves, arity, SPONGE); }
+  template <class Party>
+  std::vector<Fr> merkle_tree_compression_shared(Party& party, const std::vector<Fr>& leaves, uint32_t arity) const {
+    return merkle_tree_shared(party, leaves, arity, COMPRESSION);
+  }
+};
+
 }  // namespace cosnarks

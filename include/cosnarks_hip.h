@@ -82,6 +82,7 @@ typedef enum {
 
 typedef struct csh_bases_s* csh_bases_t;   /* proving-key query resident on the device */
 typedef struct csh_domain_s* csh_domain_t; /* radix-2 evaluation domain (twiddles on device) */
+typedef struct csh_poseidon2_params_s* csh_poseidon2_params_t; /* one Poseidon2 parameter set on the device */
 
 /* ---- context ------------------------------------------------------------------------------- */
 int csh_init(int device);            /* select device for the calling thread, create context lazily */
@@ -763,6 +764,56 @@ int csh_honk_co_pos_int_operands_dev(csh_curve_t field_of, uint32_t protocol, ui
 int csh_honk_co_pos_int_finish_dev(csh_curve_t field_of, uint32_t protocol, uint32_t party_id, const uint64_t* const* cols_dev, size_t edge_begin,
                                    size_t edge_end, const uint32_t* edge_idx_dev, size_t m, const uint64_t* scaling_dev, size_t scaling_stride,
                                    const uint64_t* params, const uint64_t* u1_dev, uint64_t* acc_dev, void* stream);
+
+/* ---- batched Poseidon2: plain, Rep3 and Shamir rounds, Merkle trees ------------------------------------------------
+ * The Poseidon2 gadget of mpc-core/src/gadgets/ (paths below are relative to it), d = 5, t = 2, 3 or 4, over a batch of independent
+ * states: state i is elements [i t, (i + 1) t) of a vector (chunks_exact_mut(T)). The library builds in no parameter set: the round
+ * numbers, the round constants and the diagonal are the caller's (the fields of Poseidon2Params, poseidon2/poseidon2_params.rs).
+ * Elements are arkworks Montgomery words, outputs are canonical, the _dev calls are stream-ordered without host synchronisation.
+ * protocol, party_id and x (+) v (a public value goes to component a of party 0 and component b of party 1; with protocol 0 to the
+ * one component of every party) are those of the Oink section; a share is ncomp = protocol + 1 values, interleaved.
+ * CSH_ERR_INVALID before any device work: t outside 2 .. 4, a NULL pointer where one is required, an arity that does not go with the
+ * mode, n_leaves that is no power of the arity, a step above the round count, an output range that overlaps an input range or another
+ * output of the call. */
+/* One parameter set on the device. rc_external: (rounds_f_beginning + rounds_f_end) * t host elements, round after round
+ * (round_constants_external); rc_internal: rounds_p host elements; diag_m_1: t host elements (mat_internal_diag_m_1). At t = 2 and
+ * t = 3 the internal matrix is the fixed one of matmul_internal (poseidon2/poseidon2_permutation.rs:126-147), so diag_m_1 must be
+ * (1, 2) or (1, 1, 2) as the reference asserts there; at t = 4 it is used (:148-160). */
+int csh_poseidon2_params_create(csh_curve_t field_of, uint32_t t, uint32_t rounds_f_beginning, uint32_t rounds_f_end, uint32_t rounds_p,
+                                const uint64_t* rc_external, const uint64_t* rc_internal, const uint64_t* diag_m_1,
+                                csh_poseidon2_params_t* handle);
+int csh_poseidon2_params_destroy(csh_poseidon2_params_t handle);
+/* permutation_in_place (poseidon2/poseidon2_permutation.rs:194-214) on each of n_perm states: the initial linear layer,
+ * rounds_f_beginning external rounds, rounds_p internal rounds, rounds_f_end external rounds whose constants go on at index
+ * rounds_f_beginning (:209-213); one launch. out_dev may be state_dev itself; any other overlap is refused. */
+int csh_poseidon2_permute_dev(csh_poseidon2_params_t handle, const uint64_t* state_dev, size_t n_perm, uint64_t* out_dev, void* stream);
+/* merkle_tree_sponge (mode 0, t > arity; merkle_tree/plain.rs:15-50) and merkle_tree_compression (mode 1, t >= arity; :113-155) of
+ * n_leaves = arity^k leaves, k >= 0: root_dev receives one element. One launch per layer, nothing returns to the host in between.
+ * work_dev: 2 * (n_leaves / arity) elements of scratch (may be NULL when n_leaves <= arity). */
+int csh_poseidon2_merkle_dev(csh_poseidon2_params_t handle, uint32_t arity, uint32_t mode, const uint64_t* leaves_dev, size_t n_leaves,
+                             uint64_t* root_dev, uint64_t* work_dev, void* stream);
+/* The local stretches of rep3_permutation_in_place_with_precomputation_packed (poseidon2/rep3.rs:612-648, round bodies :516-575,
+ * :220-243, :296-310, :358-388) and shamir_permutation_in_place_with_precomputation_packed (poseidon2/shamir.rs:326-365, :75-153,
+ * :258-296), one call per network round. With R = rounds_f_beginning + rounds_p + rounds_f_end: step 0 = the initial linear layer and the
+ * pre-part of round 0; step s in 1 .. R - 1 = the post-part of round s - 1 and the pre-part of round s; step R = the post-part of the
+ * last round. Pre-part: state (+) round constant - r at the s-box positions, written compactly to open_dev (n_perm * t shares in an
+ * external round, n_perm in an internal one); the caller opens them (open_vec) and passes the opened values as y_dev to the next step.
+ * Post-part: r^5 + 5 y r^4 + 10 y^2 r^3 + 10 y^3 r^2 + 5 y^4 r (+) y^5 at the s-box positions (sbox_rep3_precomp_post,
+ * sbox_shamir_precomp_post), then matmul_external or matmul_internal. state_dev (n_perm * t shares, in place) holds the state after
+ * the linear layer. precomp_dev: host array of the five device vectors r, r^2, r^3, r^4, r^5 (Poseidon2Precomputations). precomp_offset:
+ * precomp.offset at the round whose pre-part the step runs (at step R: after the last round) -- the caller advances it by n_perm * t
+ * after an external round and by n_perm after an internal one (rep3.rs:240); an external round reads entry offset + flat state index,
+ * an internal one offset + permutation index. ff_out_dev (step 0 only, may be NULL): n_perm shares, element 0 of every state before
+ * the linear layer, the feed-forward of the compression tree. handle's field must be field_of. */
+int csh_poseidon2_co_round_dev(csh_curve_t field_of, uint32_t protocol, uint32_t party_id, csh_poseidon2_params_t handle, uint32_t step,
+                               uint64_t* state_dev, size_t n_perm, const uint64_t* y_dev, const uint64_t* const* precomp_dev /* 5 */,
+                               size_t precomp_offset, uint64_t* open_dev, uint64_t* ff_out_dev, void* stream);
+/* The next layer of a collaborative tree (merkle_tree/rep3.rs:44-52, :99-111, merkle_tree/shamir.rs the same): state_dev = the len
+ * states of a layer after its permutation, ff_dev = len shares (mode 1; ignored in mode 0). next_dev: len / arity states, state i =
+ * element 0 of states arity i .. arity i + arity - 1 (+ their feed-forward), zeros after them. len == 1: next_dev is one share, the root.
+ * Affine and the same for every party. */
+int csh_poseidon2_layer_next_dev(csh_curve_t field_of, uint32_t ncomp, uint32_t t, uint32_t arity, uint32_t mode, const uint64_t* state_dev,
+                                 const uint64_t* ff_dev, uint64_t* next_dev, size_t len, void* stream);
 
 /* Rep3 correlated masks generated on the device ("next" row f2): out[i] = from_be_bytes_mod_order(a_i) -
  * from_be_bytes_mod_order(b_i), a_i / b_i = the 32-byte chunks number elem_offset{1,2} + i of the ChaCha12 keystreams

@@ -19,3 +19,5 @@ pub use co_sumcheck::{hip_co_arith, hip_co_delta_finish, hip_co_delta_operands, 
 pub use co_sumcheck::{hip_co_ell_finish, hip_co_ell_operands, hip_co_ell_operands2, hip_co_mem_finish, hip_co_mem_operands, hip_co_nnf_finish, hip_co_nnf_operands, hip_co_pos_ext_finish, hip_co_pos_ext_operands, hip_co_pos_int_finish, hip_co_pos_int_operands, CoGatesBatch};
 pub mod scans;
 pub use scans::{hip_batch_inverse, hip_batched_polys_dev, hip_eval_poly, hip_prefix_product, hip_factor_roots};
+pub mod poseidon2;
+pub use poseidon2::Poseidon2Dev;
