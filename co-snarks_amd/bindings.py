@@ -1088,6 +1088,119 @@ def poseidon2_layer_next(curve: int, ncomp: int, t: int, arity: int, mode: int, 
     return next_out
 
 
+# ---- F::rand streams and DN07 double sharings (csrc/field_rand.hip, csrc/shamir_rng.hip) -------------------------------------------
+SHAMIR_MAX_PARTIES = 16
+_FIELD_RAND_MAX_CAND = 1 << 62
+
+
+def _seed32(seed, what):
+    b = bytes(seed)
+    if len(b) != 32:
+        raise CoSnarksHipError("%s: a seed is 32 bytes" % what)
+    return b
+
+
+def field_rand(curve: int, seed, cand_begin: int, n: int, out=None, stream=None):
+    """csh_field_rand_dev: the first n accepted F::rand candidates of ChaCha12Rng::from_seed(seed) at or after candidate cand_begin
+    -> (out DeviceBuffer of n elements, cand_end). Synchronises the stream."""
+    seed = _seed32(seed, "field_rand")
+    if curve not in (BN254, BLS12_381, BLS12_377):
+        raise CoSnarksHipError("field_rand: field_of must be BN254, BLS12-381 or BLS12-377")
+    if n < 0 or n > 1 << 28 or not 0 <= cand_begin <= _FIELD_RAND_MAX_CAND:
+        raise CoSnarksHipError("field_rand: n must be 0 .. 2^28 and cand_begin 0 .. 2^62")
+    if out is None:
+        out = DeviceBuffer(max(32 * n, 32))
+    elif isinstance(out, DeviceBuffer) and out.nbytes < 32 * n:
+        raise CoSnarksHipError("field_rand: out holds fewer than n elements")
+    end = C.c_uint64(0)
+    _check(lib().csh_field_rand_dev(curve, seed, C.c_uint64(cand_begin), C.c_size_t(n), _devptr(out), C.byref(end), _stream(stream)))
+    return out, end.value
+
+
+def field_rand_plan(curve: int, n: int, cand_begin: int = 0):
+    """csh_field_rand_plan -> (candidates of the first window, workgroups, candidates per workgroup, acceptance rate)"""
+    out = (C.c_uint64 * 4)()
+    _check(lib().csh_field_rand_plan(curve, C.c_size_t(n), C.c_uint64(cand_begin), out))
+    return out[0], out[1], out[2], out[3] / 1e9
+
+
+class ShamirRng:
+    """csh_shamir_rng_t: one Shamir party's shared streams (seeds: num_parties - 1 seeds of 32 bytes, stream q shared with party q for
+    q < id and q + 1 otherwise; positions in candidates), public matrices and the device buffers r_t / r_2t."""
+
+    def __init__(self, curve: int, party_id: int, num_parties: int, threshold: int, seeds, positions=None):
+        if curve not in (BN254, BLS12_381, BLS12_377):
+            raise CoSnarksHipError("ShamirRng: field_of must be BN254, BLS12-381 or BLS12-377")
+        if num_parties > SHAMIR_MAX_PARTIES:
+            raise CoSnarksHipError("ShamirRng: num_parties exceeds 16, the limit of this library")
+        if threshold < 1 or 2 * threshold + 1 > num_parties:
+            raise CoSnarksHipError("ShamirRng: threshold must be at least 1 and 2 * threshold + 1 <= num_parties")
+        if not 0 <= party_id < num_parties:
+            raise CoSnarksHipError("ShamirRng: id must be below num_parties")
+        seeds = [_seed32(s, "ShamirRng") for s in seeds]
+        if len(seeds) != num_parties - 1 or (positions is not None and len(positions) != num_parties - 1):
+            raise CoSnarksHipError("ShamirRng: num_parties - 1 seeds (and positions)")
+        if positions is not None and any(not 0 <= int(x) <= _FIELD_RAND_MAX_CAND for x in positions):
+            raise CoSnarksHipError("ShamirRng: a stream position exceeds 2^62")
+        self.curve, self.id, self.n, self.t = curve, party_id, num_parties, threshold
+        self.n_send = (num_parties - threshold - 2) + (num_parties - 2 * threshold - 1)  # wire vectors of one double share, t block then 2t block
+        pos = (C.c_uint64 * (num_parties - 1))(*[int(x) for x in positions]) if positions is not None else None
+        self.h = C.c_void_p()
+        _check(lib().csh_shamir_rng_create(curve, C.c_uint32(party_id), C.c_uint32(num_parties), C.c_uint32(threshold), b"".join(seeds), pos, C.byref(self.h)))
+
+    def positions(self):
+        out = (C.c_uint64 * (self.n - 1))()
+        _check(lib().csh_shamir_rng_positions(self.h, out))
+        return list(out)
+
+    def fork_seeds(self):
+        """csh_shamir_rng_fork_seeds: one 32-byte seed draw from every shared stream (fork_with_pairs); positions advance by one"""
+        out = C.create_string_buffer(32 * (self.n - 1))
+        _check(lib().csh_shamir_rng_fork_seeds(self.h, out))
+        return [out.raw[32 * q:32 * q + 32] for q in range(self.n - 1)]
+
+    def __len__(self):
+        v = C.c_size_t(0)
+        _check(lib().csh_shamir_pairs_len(self.h, C.byref(v)))
+        return v.value
+
+    def double_share_local(self, amount: int, send=None, stream=None):
+        """csh_shamir_double_share_local_dev -> send (DeviceBuffer of n_send * amount elements in wire order; None when nothing is sent)"""
+        if not 1 <= amount <= 1 << 24:
+            raise CoSnarksHipError("ShamirRng.double_share_local: amount must be 1 .. 2^24")
+        if send is None and self.n_send:
+            send = DeviceBuffer(32 * self.n_send * amount)
+        _check(lib().csh_shamir_double_share_local_dev(self.h, C.c_size_t(amount), _devptr(send), _stream(stream)))
+        return send
+
+    def double_share_finish(self, amount: int, recv=None, stream=None):
+        """csh_shamir_double_share_finish_dev: recv = n_send * amount received elements; appends amount * (threshold + 1) pairs"""
+        if recv is None and self.n_send:
+            raise CoSnarksHipError("ShamirRng.double_share_finish: recv is None but this party receives")
+        _check(lib().csh_shamir_double_share_finish_dev(self.h, C.c_size_t(amount), _devptr(recv), _stream(stream)))
+
+    def take(self, count: int, from_front: bool = False, r_t=None, r_2t=None, stream=None):
+        """csh_shamir_pairs_take_dev -> (r_t, r_2t) DeviceBuffers of count elements: pops from the back (element i = the i-th pop) or
+        the drain from the front"""
+        if count < 0:
+            raise CoSnarksHipError("ShamirRng.take: a negative count")
+        r_t = r_t if r_t is not None else DeviceBuffer(max(32 * count, 32))
+        r_2t = r_2t if r_2t is not None else DeviceBuffer(max(32 * count, 32))
+        _check(lib().csh_shamir_pairs_take_dev(self.h, C.c_size_t(count), C.c_int(1 if from_front else 0), _devptr(r_t), _devptr(r_2t), _stream(stream)))
+        return r_t, r_2t
+
+    def free(self):
+        if self.h:
+            lib().csh_shamir_rng_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 def rep3_local_mul_vec(curve: int, lhs_ab, rhs_ab, mask=None):
     l, r = _u64(lhs_ab), _u64(rhs_ab)
     n = l.size // 8

@@ -473,6 +473,7 @@ static const TuneEntry kTune[] = {
     {"scan_tile_lanes", "CSH_SCAN_TILE_LANES", &Tune::scan_tile_lanes},
     {"scan_spine_step", "CSH_SCAN_SPINE_STEP", &Tune::scan_spine_step},
     {"fold_tile_log", "CSH_FOLD_TILE_LOG", &Tune::fold_tile_log},
+    {"field_rand_window", "CSH_FIELD_RAND_WINDOW", &Tune::field_rand_window},
 };
 static bool is_scan_knob(std::atomic<int> Tune::*f) { return f == &Tune::scan_lane_run || f == &Tune::scan_tile_lanes || f == &Tune::scan_spine_step; }
 Tune& tune() {
@@ -756,6 +757,10 @@ int csh_tune_set(const char* key, int value) {
       }
       if (e.field == &Tune::fold_tile_log && !fold_tile_log_ok(value)) {
         set_error("csh_tune_set: '%s' = %d is out of range (fold_tile_log: 3 .. 11)", key, value);
+        return CSH_ERR_INVALID;
+      }
+      if (e.field == &Tune::field_rand_window && !field_rand_window_ok(value)) {
+        set_error("csh_tune_set: '%s' = %d is out of range (field_rand_window: 0 or 256 .. 2^30)", key, value);
         return CSH_ERR_INVALID;
       }
       (tune().*(e.field)).store(value);

@@ -196,6 +196,8 @@ struct Tune {
   std::atomic<int> scan_spine_step{1024}; // tile totals the one-workgroup spine takes per step (= its lanes): a power of two, 64 .. 1024
   // multilinear folds (mle_fold.hip): the decomposition only, never a result
   std::atomic<int> fold_tile_log{10};     // log2 of the elements a workgroup of k_mle_fold_rounds folds on chip (= rounds per launch): 3 .. 11
+  // F::rand streams (field_rand.hip): the decomposition only, never a result
+  std::atomic<int> field_rand_window{0};  // most candidates one window of csh_field_rand_dev looks at: 0 = sized from n, else 256 .. 2^30
 };
 Tune& tune();
 // the values csh_tune_set accepts for the field-scan keys (the launchers fall back to the defaults for anything else)
@@ -207,6 +209,8 @@ inline bool scan_knob_ok(std::atomic<int> Tune::*key, int v) {
 
 constexpr int FOLD_TILE_LOG_MIN = 3, FOLD_TILE_LOG_MAX = 11, FOLD_TILE_LOG_DEFAULT = 10;
 inline bool fold_tile_log_ok(int v) { return v >= FOLD_TILE_LOG_MIN && v <= FOLD_TILE_LOG_MAX; }
+constexpr uint64_t FRD_WINDOW_MIN = 256, FRD_WINDOW_MAX = uint64_t(1) << 30;  // tune "field_rand_window": 0 (sized from n) or this range
+inline bool field_rand_window_ok(int v) { return v == 0 || (v >= (int)FRD_WINDOW_MIN && (uint64_t)v <= FRD_WINDOW_MAX); }
 
 // A Rep3 local multiplication without its correlated mask is not a valid sharing step: once opened, the products leak
 // cross terms (rep3/arithmetic.rs:132-146 always adds masking_field_elements_vec). NULL masks / seeds are therefore an

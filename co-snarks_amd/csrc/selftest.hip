@@ -12,6 +12,7 @@
 #include "curve_lazy.hpp"
 #include "chacha.hpp"
 #include "field29.hpp"
+#include "field_rand.hpp"
 #include "field_scan.hpp"
 #include "fr_entry.hpp"
 #include "honk_oink.hpp"
@@ -22,6 +23,7 @@
 #include "plonk_quot.hpp"
 #include "plonk_rounds.hpp"
 #include "poseidon2.hpp"
+#include "shamir_rng.hpp"
 #include "vec_elem.hpp"
 
 using namespace csh;
@@ -795,6 +797,74 @@ static int poseidon2_host_t(uint32_t t, uint32_t rf_b, uint32_t rf_e, uint32_t r
   for (int k = 0; k < 5; ++k) a.pre[k] = (const F*)pre[k];
   for (size_t u = 0; u < n * a.ncomp; ++u) t == 2 ? p2_co_step_at<F, 2>(a, u) : t == 3 ? p2_co_step_at<F, 3>(a, u) : p2_co_step_at<F, 4>(a, u);
   return CSH_OK;
+}
+
+
+// The stages of shamir_rng.hip on host arrays, dealt to no lanes: the same schedule, matrices, argument builders and per-element function.
+// force: 0 = the draws of the shared streams (field_rand_host, the per-candidate function of the kernels; positions advance), 1 = every
+// draw the limbs 0, 2 = every draw the limbs p - 1 (the matrix stage at the edges). send: the wire vectors (written); with recv given the finish stage runs
+// too and r_t / r_2t receive amount * (t + 1) elements each.
+template <class F>
+static int shamir_rng_host_t(uint32_t id, uint32_t n, uint32_t t, const uint8_t* seeds, uint64_t* positions, size_t amount, int force, uint64_t* send,
+                             const uint64_t* recv, bool finish, uint64_t* r_t, uint64_t* r_2t) {
+  const ShamirSchedule s = shamir_schedule(n, t, id);
+  const ShamirMatrices<F> m = shamir_matrices<F>(s);
+  const ShamirWork w(s, amount);
+  std::vector<F> work(w.total, F::zero());
+  size_t off = 0;
+  for (uint32_t q = 0; q + 1 < n; ++q) {
+    const size_t cnt = s.per_stream[q] * amount;
+    if (force == 0 && cnt) positions[q] = field_rand_host<F>(seeds + 32 * q, positions[q], cnt, work.data() + off);
+    if (force == 2)
+      for (size_t i = 0; i < cnt; ++i) work[off + i] = F::modulus(), work[off + i].l[0] -= 1;  // the limbs of p - 1 (p is odd)
+    off += cnt;
+  }
+  auto run = [](const SmArgs<F>& a) {
+    for (uint32_t tile = 0; tile < (a.R + SM_ROWS - 1) / SM_ROWS; ++tile)
+      for (size_t i = 0; i < a.n; ++i) shamir_matmul_at(a, tile, i);
+  };
+  run(shamir_local_args<F>(s, 0, m.m.data() + m.off_t, m.rows_t, work.data(), amount, (F*)send));
+  run(shamir_local_args<F>(s, 1, m.m.data() + m.off_2t, m.rows_2t, work.data(), amount, (F*)send));
+  if (finish) {
+    run(shamir_finish_args<F>(s, 0, m.m.data() + m.off_v, work.data(), amount, (const F*)recv, (F*)r_t));
+    run(shamir_finish_args<F>(s, 1, m.m.data() + m.off_v, work.data(), amount, (const F*)recv, (F*)r_2t));
+  }
+  return CSH_OK;
+}
+
+extern "C" {
+
+// the host loop over the kernels' per-candidate function (field_rand.hpp)
+int csh_selftest_field_rand_host(int field_of, const uint8_t seed[32], uint64_t cand_begin, size_t n, uint64_t* out, uint64_t* cand_end) {
+  if (!seed || (!out && n) || cand_begin > FRD_MAX_CAND) return CSH_ERR_INVALID;
+  return FR_CALL(field_of, [&]() -> int {
+    const uint64_t end = field_rand_host<F>(seed, cand_begin, n, (F*)out);
+    if (cand_end) *cand_end = end;
+    return CSH_OK;
+  }());
+}
+
+// the per-candidate function on 32 given bytes (one half of a keystream block): *accepted and, if so, the element
+int csh_selftest_field_rand_candidate(int field_of, const uint8_t bytes[32], uint64_t out[4], int* accepted) {
+  if (!bytes || !out || !accepted) return CSH_ERR_INVALID;
+  uint32_t words[16] = {0};
+  memcpy(words + 8, bytes, 32);
+  return FR_CALL(field_of, [&]() -> int {
+    F v;
+    *accepted = field_rand_candidate<F>(words, 1, v) ? 1 : 0;
+    memcpy(out, &v, 32);
+    return CSH_OK;
+  }());
+}
+
+int csh_selftest_shamir_rng_host(int field_of, uint32_t id, uint32_t num_parties, uint32_t threshold, const uint8_t* seeds, uint64_t* positions,
+                                 size_t amount, int force, uint64_t* send, const uint64_t* recv, int finish, uint64_t* r_t, uint64_t* r_2t) {
+  if (shamir_params_refusal(id, num_parties, threshold) || !seeds || !positions || amount < 1 || force < 0 || force > 2) return CSH_ERR_INVALID;
+  const bool wire = num_parties - threshold - 2 + num_parties - 2 * threshold - 1 != 0;
+  if ((wire && (!send || (finish && !recv))) || (finish && (!r_t || !r_2t))) return CSH_ERR_INVALID;
+  return FR_CALL(field_of, shamir_rng_host_t<F>(id, num_parties, threshold, seeds, positions, amount, force, send, recv, finish != 0, r_t, r_2t));
+}
+
 }
 
 extern "C" {

@@ -604,6 +604,150 @@ struct Poseidon2ShamirParty {
   }
 };
 
+// ShamirPreprocessing (shamir.rs:26-64) with ShamirRng (shamir/rngs.rs) on the device: the shared streams, the public matrices and the
+// buffers r_t / r_2t live in a csh_shamir_rng_t; this struct is the network around it -- get_shared_rngs (rngs.rs:98-139: same send /
+// receive split, same seed order), the one exchange of random_double_share (rngs.rs:387-392) and fork_with_pairs (rngs.rs:74-96). The
+// reference seeds the party's own generator from the operating system (RngType::from_entropy, shamir.rs:45); here the caller passes the
+// 32 bytes. Stream positions are counted in 32-byte candidates (csh_field_rand_dev): a seed draw is one of them.
+template <class P>
+struct ShamirPreprocessingHip {
+  using Fr = typename P::Fr;
+  int id = 0;
+  size_t num_parties = 0, threshold = 0;
+  uint8_t rng_seed[32] = {0};  // the party's own generator (only ever draws seeds)
+  uint64_t rng_pos = 0;
+  csh_shamir_rng_t handle = nullptr;
+  std::deque<std::pair<Fr, Fr>> inherited;  // a fork's pairs: the parent's drain(..amount), in front of whatever the fork generates itself
+
+  ShamirPreprocessingHip() = default;
+  ShamirPreprocessingHip(const ShamirPreprocessingHip&) = delete;
+  ShamirPreprocessingHip& operator=(const ShamirPreprocessingHip&) = delete;
+  ShamirPreprocessingHip(ShamirPreprocessingHip&& o) noexcept { *this = std::move(o); }
+  ShamirPreprocessingHip& operator=(ShamirPreprocessingHip&& o) noexcept {
+    if (this != &o) {
+      csh_shamir_rng_destroy(handle);
+      id = o.id, num_parties = o.num_parties, threshold = o.threshold, rng_pos = o.rng_pos, handle = o.handle;
+      memcpy(rng_seed, o.rng_seed, 32);
+      inherited = std::move(o.inherited);
+      o.handle = nullptr;
+    }
+    return *this;
+  }
+  ~ShamirPreprocessingHip() { csh_shamir_rng_destroy(handle); }
+
+  struct Dev {  // csh_malloc / csh_free
+    void* p = nullptr;
+    explicit Dev(size_t bytes) { check(csh_malloc(&p, bytes ? bytes : 1), "csh_malloc"); }
+    Dev(const Dev&) = delete;
+    Dev& operator=(const Dev&) = delete;
+    ~Dev() { csh_free(p); }
+    uint64_t* w() const { return (uint64_t*)p; }
+  };
+  // rng.gen::<[u8; 32]>() at candidate `pos` of ChaCha12Rng::from_seed(seed)
+  static void gen_seed(const uint8_t seed[32], uint64_t& pos, uint8_t out[32]) {
+    ChaCha12 c(seed);
+    c.counter = pos >> 1;
+    uint8_t blk[64];
+    c.fill_bytes(blk, 64);
+    memcpy(out, blk + 32 * (pos & 1), 32);
+    ++pos;
+  }
+  size_t sending() const { return (num_parties - threshold - 2) + (num_parties - 2 * threshold - 1); }
+
+  // ShamirPreprocessing::new: `amount` pairs at least (amount.div_ceil(t + 1) batch items of t + 1 pairs)
+  static ShamirPreprocessingHip create(const LocalNetwork& net, size_t num_parties, size_t threshold, size_t amount, const uint8_t seed[32]) {
+    if (2 * threshold + 1 > num_parties) throw Error("Threshold too large for number of parties");
+    ShamirPreprocessingHip s;
+    s.id = net.id(), s.num_parties = num_parties, s.threshold = threshold;
+    memcpy(s.rng_seed, seed, 32);
+    // get_shared_rngs
+    const size_t n = num_parties, id = (size_t)s.id, interact = n - 1;
+    std::vector<uint8_t> seeds(32 * n, 0);
+    size_t send = interact / 2;
+    if ((interact & 1) == 1 && id < n / 2) send += 1;
+    const size_t receive = interact - send;
+    for (size_t off = 1; off <= send; ++off) {
+      const size_t rcv_id = (id + off) % n;
+      gen_seed(s.rng_seed, s.rng_pos, &seeds[32 * rcv_id]);
+      net.send((int)rcv_id, Bytes(seeds.begin() + 32 * rcv_id, seeds.begin() + 32 * rcv_id + 32));
+    }
+    for (size_t off = 1; off <= receive; ++off) {
+      const size_t send_id = (id + n - off) % n;
+      const Bytes b = net.recv((int)send_id);
+      if (b.size() != 32) throw Error("get_shared_rngs: a seed is 32 bytes");
+      memcpy(&seeds[32 * send_id], b.data(), 32);
+    }
+    seeds.erase(seeds.begin() + 32 * id, seeds.begin() + 32 * id + 32);  // seeds.split_off(id), skip(1)
+    check(csh_shamir_rng_create(P::ID, (uint32_t)id, (uint32_t)n, (uint32_t)threshold, seeds.data(), nullptr, &s.handle), "csh_shamir_rng_create");
+    if (amount) s.buffer_triples(net, (amount + threshold) / (threshold + 1));
+    return s;
+  }
+  // buffer_triples (rngs.rs:401-428): `amount` batch items, (t + 1) pairs each
+  void buffer_triples(const LocalNetwork& net, size_t amount) {
+    const size_t n = num_parties, t = threshold, k = sending();
+    Dev wire(sizeof(Fr) * k * amount);
+    check(csh_shamir_double_share_local_dev(handle, amount, k ? wire.w() : nullptr, nullptr), "csh_shamir_double_share_local_dev");
+    if (k) {
+      std::vector<uint8_t> host(sizeof(Fr) * k * amount);
+      check(csh_memcpy_d2h(host.data(), wire.p, host.size()), "csh_memcpy_d2h");
+      const size_t per = sizeof(Fr) * amount;
+      size_t q = 0;
+      for (size_t i = 1; i <= n - t - 2; ++i, ++q) net.send((int)((id + i + t + 1) % n), Bytes(host.begin() + q * per, host.begin() + (q + 1) * per));
+      for (size_t i = 1; i <= n - 2 * t - 1; ++i, ++q) net.send((int)((id + i + 2 * t) % n), Bytes(host.begin() + q * per, host.begin() + (q + 1) * per));
+      q = 0;
+      auto take = [&](size_t from) {
+        const Bytes b = net.recv((int)from);
+        if (b.size() != per) throw Error("random_double_share: invalid number of elements received");
+        memcpy(host.data() + q++ * per, b.data(), per);
+      };
+      for (size_t i = 1; i <= n - t - 2; ++i) take((id + n - (t + 1) - i) % n);
+      for (size_t i = 1; i <= n - 2 * t - 1; ++i) take((id + n - 2 * t - i) % n);
+      check(csh_memcpy_h2d(wire.p, host.data(), host.size()), "csh_memcpy_h2d");
+    }
+    check(csh_shamir_double_share_finish_dev(handle, amount, k ? wire.w() : nullptr, nullptr), "csh_shamir_double_share_finish_dev");
+  }
+  size_t len() const {
+    size_t l = 0;
+    check(csh_shamir_pairs_len(handle, &l), "csh_shamir_pairs_len");
+    return inherited.size() + l;
+  }
+  // `count` pairs off the front of the device buffers, in buffer order
+  std::deque<std::pair<Fr, Fr>> drain(size_t count) {
+    Dev a(sizeof(Fr) * count), b(sizeof(Fr) * count);
+    check(csh_shamir_pairs_take_dev(handle, count, 1, a.w(), b.w(), nullptr), "csh_shamir_pairs_take_dev");
+    std::vector<Fr> r_t(count), r_2t(count);
+    if (count) {
+      check(csh_memcpy_d2h(r_t.data(), a.p, sizeof(Fr) * count), "csh_memcpy_d2h");
+      check(csh_memcpy_d2h(r_2t.data(), b.p, sizeof(Fr) * count), "csh_memcpy_d2h");
+    }
+    std::deque<std::pair<Fr, Fr>> out;
+    for (size_t i = 0; i < count; ++i) out.push_back({r_t[i], r_2t[i]});
+    return out;
+  }
+  // From<ShamirPreprocessing> for ShamirState (shamir.rs:66-103): every pair, in buffer order, into the host state the drivers consume
+  ShamirState<Fr> into_state() {
+    size_t l = 0;
+    check(csh_shamir_pairs_len(handle, &l), "csh_shamir_pairs_len");
+    std::deque<std::pair<Fr, Fr>> pairs = std::move(inherited);
+    inherited.clear();
+    for (auto& pr : drain(l)) pairs.push_back(pr);
+    return ShamirState<Fr>::create(id, num_parties, threshold, std::move(pairs));
+  }
+  // fork_with_pairs (rngs.rs:74-96): the own generator's seed draw first, then one per shared stream; the first `amount` pairs move
+  ShamirPreprocessingHip fork(size_t amount) {
+    ShamirPreprocessingHip c;
+    c.id = id, c.num_parties = num_parties, c.threshold = threshold;
+    gen_seed(rng_seed, rng_pos, c.rng_seed);
+    std::vector<uint8_t> seeds(32 * (num_parties - 1));
+    check(csh_shamir_rng_fork_seeds(handle, seeds.data()), "csh_shamir_rng_fork_seeds");
+    if (amount > len()) throw Error("not enough corr rand pairs");
+    check(csh_shamir_rng_create(P::ID, (uint32_t)id, (uint32_t)num_parties, (uint32_t)threshold, seeds.data(), nullptr, &c.handle), "csh_shamir_rng_create");
+    while (amount && !inherited.empty()) c.inherited.push_back(inherited.front()), inherited.pop_front(), --amount;
+    for (auto& pr : drain(amount)) c.inherited.push_back(pr);
+    return c;
+  }
+};
+
 // Poseidon2<F, T, 5> over the device entries (csrc/poseidon2.hip): the caller's parameter set (the fields of Poseidon2Params) is uploaded once;
 // the methods carry the reference's names. The collaborative ones take a party (above) and run every stretch of local arithmetic between two
 // openings as one csh_poseidon2_co_round_dev; state and precomputation stay on the device, the shares to open and the opened values cross.

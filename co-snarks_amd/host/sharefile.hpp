@@ -57,6 +57,16 @@ struct SeededShare {
     }
     return out;
   }
+  // the same expansion on the device (csh_field_rand_dev: the candidates in parallel, a stable compaction of the accepted ones): out_dev
+  // receives length() elements, word for word those of expand(). Explicit shares are uploaded. Synchronises `stream` once.
+  void expand_dev(csh_curve_t field_of, uint64_t* out_dev, void* stream) const {
+    static_assert(sizeof(Fr) == 32, "32-byte scalar fields only");
+    if (!is_seed) {
+      if (!shares.empty()) check(csh_memcpy_h2d(out_dev, shares.data(), sizeof(Fr) * shares.size()), "csh_memcpy_h2d");
+      return;
+    }
+    check(csh_field_rand_dev(field_of, seed, 0, (size_t)len, out_dev, nullptr, stream), "csh_field_rand_dev");
+  }
 };
 
 template <class P>

@@ -83,6 +83,7 @@ typedef enum {
 typedef struct csh_bases_s* csh_bases_t;   /* proving-key query resident on the device */
 typedef struct csh_domain_s* csh_domain_t; /* radix-2 evaluation domain (twiddles on device) */
 typedef struct csh_poseidon2_params_s* csh_poseidon2_params_t; /* one Poseidon2 parameter set on the device */
+typedef struct csh_shamir_rng_s* csh_shamir_rng_t; /* one Shamir party's shared streams, public matrices and double-share buffers */
 
 /* ---- context ------------------------------------------------------------------------------- */
 int csh_init(int device);            /* select device for the calling thread, create context lazily */
@@ -824,6 +825,68 @@ int csh_rep3_masks(csh_curve_t field_of, const uint8_t seed1[32], uint64_t elem_
                    uint64_t elem_offset2, uint64_t* out, size_t n);
 int csh_rep3_masks_dev(csh_curve_t field_of, const uint8_t seed1[32], uint64_t elem_offset1, const uint8_t seed2[32],
                        uint64_t elem_offset2, uint64_t* out_dev, size_t n, void* stream);
+
+/* ---- F::rand over a ChaCha12 stream on the device -------------------------------------------------------------------
+ * The draws of `F::rand(&mut rng)` for rng = ChaCha12Rng::from_seed(seed) (RngType, mpc-core/src/lib.rs:13): what SeededType::expand_vec
+ * (mpc-core/src/protocols/rep3.rs:185-196) and every draw of ShamirRng (mpc-core/src/protocols/shamir/rngs.rs:334-428) make. Candidate k
+ * of the stream is keystream bytes [32 k, 32 k + 32) as little-endian limbs with the top limb masked to the modulus bit size; it is
+ * accepted iff it is below p, and the accepted limbs are the element's Montgomery words as they stand. ark-ff is not vendored and no
+ * reference vector exists: PARITY UNPINNED, as for the seeded share files.
+ * out_dev receives the first n accepted candidates at or after candidate cand_begin, in order, canonical by construction. *cand_end (a
+ * HOST pointer, may be NULL) receives the index one past the last candidate consumed, so that a call with cand_begin = *cand_end
+ * continues the stream; a 32-byte seed draw of the reference (rng.gen::<[u8; 32]>()) is one candidate slot. The output words do not
+ * depend on the launch shape (tune "vec_max_blocks", "field_rand_window" change the decomposition only). Unlike the other _dev entries
+ * this one reads two words back per window of candidates, so it SYNCHRONISES the stream: once, unless a window sized for n draws plus
+ * eight standard deviations falls short (or "field_rand_window" shrinks it) and further windows follow for the remainder. Scratch: 8 KiB
+ * of the stream's workspace. CSH_ERR_INVALID: unknown field, NULL seed, NULL out_dev with n > 0, n > 2^28, cand_begin > 2^62. */
+int csh_field_rand_dev(csh_curve_t field_of, const uint8_t seed[32], uint64_t cand_begin, size_t n, uint64_t* out_dev, uint64_t* cand_end,
+                       void* stream);
+/* The decomposition csh_field_rand_dev would give the first window of n > 0 draws at cand_begin under the tune keys in force, without
+ * running it: [candidates of the window, workgroups, candidates per workgroup, the field's acceptance rate p / 2^bits times 10^9].
+ * Host-only: for tests of the window rule and of chunk boundaries. */
+int csh_field_rand_plan(csh_curve_t field_of, size_t n, uint64_t cand_begin, uint64_t out[4]);
+
+/* ---- DN07 double sharings: the preprocessing of a Shamir party -----------------------------------------------------------
+ * ShamirRng of mpc-core/src/protocols/shamir/rngs.rs (paths below are relative to mpc-core/src/protocols/) without its network: the
+ * handle holds the field, id, num_parties, threshold, the num_parties - 1 shared streams of get_shared_rngs (rngs.rs:98-139; stream q
+ * is the one shared with party q for q < id and with party q + 1 otherwise) each as a seed and a position in candidates, the public
+ * matrices on the device -- the interpolation polynomials of precompute_interpolation_polys (shamir.rs:503-525) for degree t and 2t
+ * evaluated at the points the stages need, and create_vandermonde_matrix (rngs.rs:147-158) -- and the two growing device buffers r_t and
+ * r_2t. Exchanging the seeds and the wire vectors is network traffic and stays in the caller. seeds: (num_parties - 1) * 32 host bytes;
+ * positions: num_parties - 1 host words or NULL for zeros. CSH_ERR_INVALID: 2 * threshold + 1 > num_parties (ShamirPreprocessing::new,
+ * shamir.rs:41-43), threshold 0, id >= num_parties, and num_parties > 16, a limit of this library (the matrices go to the kernel as
+ * they are). A handle belongs to the device it was created on and is used by one thread at a time. */
+int csh_shamir_rng_create(csh_curve_t field_of, uint32_t id, uint32_t num_parties, uint32_t threshold, const uint8_t* seeds,
+                          const uint64_t* positions, csh_shamir_rng_t* handle);
+int csh_shamir_rng_destroy(csh_shamir_rng_t handle);
+/* The positions of the num_parties - 1 shared streams, in candidates (see csh_field_rand_dev). */
+int csh_shamir_rng_positions(csh_shamir_rng_t handle, uint64_t* positions);
+/* The shared-stream half of fork_with_pairs (rngs.rs:76-79): one 32-byte seed draw from every shared stream, in stream order, into
+ * seeds_out ((num_parties - 1) * 32 host bytes); every position advances by one candidate. Host work only. The child is a new handle
+ * created from these seeds; its pairs are a take from the front of this one. */
+int csh_shamir_rng_fork_seeds(csh_shamir_rng_t handle, uint8_t* seeds_out);
+/* random_double_share (rngs.rs:334-395) up to and including send_share_of_randomness, for `amount` batch items (1 .. 2^24). Per shared
+ * stream the draws run in the order of rngs.rs:344-384 -- receive_seeded_next, the sender's draws, receive_seeded_prev, for degree
+ * t + 1 and then for 2 t, `amount` draws each -- and advance the handle's positions; polys_t, rands = p[0], polys_2t, the party's own
+ * evaluations and the evaluations for the receivers are public linear maps of those draw vectors. send_dev receives the vectors in
+ * wire order: `amount` elements per receiver, (id + i + t + 1) mod n for i = 1 .. n - t - 2, then (id + i + 2 t) mod n for
+ * i = 1 .. n - 2 t - 1 (rngs.rs:291-311, :387-388). With nothing to send (3 parties, t = 1) it may be NULL. Stream-ordered, but each
+ * shared stream's draws synchronise the stream as csh_field_rand_dev does. */
+int csh_shamir_double_share_local_dev(csh_shamir_rng_t handle, size_t amount, uint64_t* send_dev, void* stream);
+/* The rest of random_double_share and buffer_triples (rngs.rs:390-427): recv_dev holds what receive_share_of_randomness receives, in
+ * its order -- `amount` elements from (id - (t + 1) - i) mod n for i = 1 .. n - t - 2, then from (id - 2 t - i) mod n for
+ * i = 1 .. n - 2 t - 1 (may be NULL when nothing is received). Applies the Vandermonde matrix to every rcv_t[b] and rcv_2t[b] and appends
+ * amount * (threshold + 1) pairs to the handle's buffers, batch item b at [b * (t + 1), (b + 1) * (t + 1)) (chunks_exact_mut). `amount`
+ * must be that of the local stage before it. The buffers grow by reallocation, which synchronises. */
+int csh_shamir_double_share_finish_dev(csh_shamir_rng_t handle, size_t amount, const uint64_t* recv_dev, void* stream);
+/* Hands out `count` pairs, element order. from_front == 0: the pops of get_pair (rngs.rs r_t.pop(); shamir/network.rs:150-167 gives
+ * element i of a vector the i-th pop), output element i = buffer element len - 1 - i. from_front != 0: the drain(..count) of
+ * fork_with_pairs (rngs.rs:93-94), buffer order. The buffers shrink by count. More than present: CSH_ERR_INVALID and nothing changes
+ * (refilling is the caller's decision). With the outputs, csh_vec_mul_dev + csh_vec_add_dev of r_2t is the masked local product of
+ * mul_vec and csh_vec_sub_dev of r_t ends the degree reduction. */
+int csh_shamir_pairs_take_dev(csh_shamir_rng_t handle, size_t count, int from_front, uint64_t* r_t_out_dev, uint64_t* r_2t_out_dev,
+                              void* stream);
+int csh_shamir_pairs_len(csh_shamir_rng_t handle, size_t* len);
 
 int csh_vec_mul_dev(csh_curve_t field_of, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n, void* stream);
 int csh_vec_add_dev(csh_curve_t field_of, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n, uint32_t ncomp, void* stream);

@@ -13,10 +13,12 @@ pub mod error;
 pub mod hip_reduction;
 pub mod layout;
 pub mod matrices;
+pub mod shamir_rng;
 pub mod split;
 
 pub use drivers::{HipPlainGroth16Driver, HipRep3Groth16Driver, HipShamirGroth16Driver};
 pub use hip_reduction::{HipCircomReduction, HipLibSnarkReduction};
+pub use shamir_rng::{hip_expand_seeded_dev, ShamirRngDev};
 
 use co_groth16::CoGroth16;
 
