@@ -5,7 +5,7 @@
 //                workgroup adds its accepted candidates through LDS;
 //   k_frd_scan   one workgroup: the chunks' offsets and the window's total; a window that falls short also gets its end reported here;
 //   k_frd_write  recomputes the candidates (half a ChaCha12 block is a few hundred integer operations, against 64 bytes through HBM per
-//                stored candidate: the rule of HcPoint) and writes the accepted ones behind the chunk's offset with a ballot scan. The
+//                stored candidate: the rule of CoPoint) and writes the accepted ones behind the chunk's offset with a ballot scan. The
 //                lane that writes the last wanted element reports its candidate index: one writer, no atomics.
 // No atomics anywhere and the output words do not depend on the launch shape: tune "vec_max_blocks" (the grid cap) and
 // "field_rand_window" (candidates per window) change the decomposition only. The per-candidate function and the window plan are

@@ -2,20 +2,15 @@
 // stretches of local arithmetic between two network products of co-noir/co-ultrahonk/src/co_decider/relations/ for EllipticRelation
 // (elliptic_relation.rs:102-254), MemoryRelation (memory_relation.rs:166-457), NonNativeFieldRelation
 // (non_native_field_relation.rs:109-215), Poseidon2ExternalRelation (poseidon2_external_relation.rs:141-228) and
-// Poseidon2InternalRelation (poseidon2_internal_relation.rs:135-227), subrelations 11 .. 27, and fold_accumulator!
-// (relations/mod.rs:45-57) at the end of each. What the kernels and the host self-test share: the argument struct, the element rule, every
-// stage's loop body.
+// Poseidon2InternalRelation (poseidon2_internal_relation.rs:135-227), subrelations 11 .. 27. What is this family's own in the stage
+// framework of honk_co_stage.hpp: the stage enum, the stages' descriptors, the constants, and every stage's loop body, which the kernels
+// and the host self-test share.
 //
-// The pattern is honk_co_relations.hpp's: the batch is never built, batch element t = 7 j + k of a column is col[e] + k (col[e + 1] -
-// col[e]) per component (hc_lerp), the only vectors in memory are the operands and results of the network products in the reference's
-// concatenation order, and every value is a canonical element of the exact 32-bit-limb field F between two operations. The columns are
-// the 19 of honk_gates.hpp (HgCol): 0 .. 7 shares, 8 .. 18 public. The parameters are the eight of the plain entry (eta_1..3, curve_b,
-// mat_internal_diag_m_1[0..4)); 2^68 and 2^14 are made on the host per field.
-//
-// The Poseidon2 accumulators keep seven points, the others six: a fold stage states its points and its edge slots (6 x 42 = 7 x 36 = 252
-// lanes of 256), as the plain kernels do (honk_gates.hpp). A lane of a six-point stage never sees the point 6.
+// The columns are the 19 of honk_gates.hpp (HgCol): 0 .. 7 shares, 8 .. 18 public. The parameters are the eight of the plain entry
+// (eta_1..3, curve_b, mat_internal_diag_m_1[0..4)); 2^68 and 2^14 are made on the host per field. Every value is a canonical element of
+// the exact 32-bit-limb field F between two operations.
 #pragma once
-#include "honk_co_relations.hpp"
+#include "honk_co_stage.hpp"
 #include "honk_gates.hpp"
 
 namespace csh {
@@ -29,93 +24,42 @@ enum HgcStage : int {
   HGC_STAGES
 };
 
-// the columns a stage reads, as a mask over HgCol
-inline uint32_t hgc_cols_of(int stage) {
-  auto bit = [](int c) { return uint32_t(1) << c; };
-  const uint32_t wires = bit(HG_W_L) | bit(HG_W_R) | bit(HG_W_O) | bit(HG_W_4);
-  const uint32_t shifts = bit(HG_W_L_SHIFT) | bit(HG_W_R_SHIFT) | bit(HG_W_O_SHIFT) | bit(HG_W_4_SHIFT);
+// The stages as data. Subrelation s of a fold stage is accumulator s of its output, entry k at element s POINTS + k: the Poseidon2
+// accumulators keep seven points, the others six. mem_finish folds its six subrelations in two launches of three -- r1, r2, r4, which
+// need neither the records nor the second product, and r0, r3, r5 -- so that a lane holds three running sums, not six.
+constexpr CoStage hgc_stage(int stage) {
+  constexpr int S = HG_Q_M;  // the columns in front of q_m are shares
+  constexpr auto bit = [](int c) { return uint64_t(1) << c; };
+  constexpr uint64_t wires = bit(HG_W_L) | bit(HG_W_R) | bit(HG_W_O) | bit(HG_W_4);
+  constexpr uint64_t shifts = bit(HG_W_L_SHIFT) | bit(HG_W_R_SHIFT) | bit(HG_W_O_SHIFT) | bit(HG_W_4_SHIFT);
+  constexpr CoPass four_of_seven{4, {0, 7, 14, 21}, {7, 7, 7, 7}};
   switch (stage) {
-    case HGC_ELL_OPS: return bit(HG_W_R) | bit(HG_W_O) | shifts | bit(HG_Q_L);
-    case HGC_ELL_OPS2: return bit(HG_W_R) | bit(HG_W_O) | bit(HG_W_L_SHIFT) | bit(HG_W_R_SHIFT) | bit(HG_W_O_SHIFT);
-    case HGC_ELL_FINISH: return bit(HG_Q_L) | bit(HG_Q_M) | bit(HG_Q_ELLIPTIC);
-    case HGC_MEM_OPS: return wires | shifts | bit(HG_Q_C);
+    case HGC_ELL_OPS: return co_ops(S, bit(HG_W_R) | bit(HG_W_O) | shifts | bit(HG_Q_L), 7, 7, 0, 0, false);
+    case HGC_ELL_OPS2: return co_ops(S, bit(HG_W_R) | bit(HG_W_O) | bit(HG_W_L_SHIFT) | bit(HG_W_R_SHIFT) | bit(HG_W_O_SHIFT), 5, 5, 0, 7, true);
+    case HGC_ELL_FINISH: return co_fold(S, bit(HG_Q_L) | bit(HG_Q_M) | bit(HG_Q_ELLIPTIC), 7, 5, false, 6, CoPass{2, {0, 6}, {6, 6}});
+    case HGC_MEM_OPS: return co_ops(S, wires | shifts | bit(HG_Q_C), 6, 6, 1, 0, true);
     case HGC_MEM_FINISH:
-      return wires | shifts | bit(HG_Q_M) | bit(HG_Q_C) | bit(HG_Q_L) | bit(HG_Q_R) | bit(HG_Q_O) | bit(HG_Q_4) | bit(HG_Q_MEMORY);
-    case HGC_NNF_OPS: return wires | bit(HG_W_L_SHIFT) | bit(HG_W_R_SHIFT);
-    case HGC_NNF_FINISH: return wires | shifts | bit(HG_Q_M) | bit(HG_Q_R) | bit(HG_Q_O) | bit(HG_Q_4) | bit(HG_Q_NNF);
-    case HGC_POS_EXT_OPS: return wires | bit(HG_Q_L) | bit(HG_Q_R) | bit(HG_Q_O) | bit(HG_Q_4);
-    case HGC_POS_EXT_FINISH: return shifts | bit(HG_Q_POSEIDON2_EXTERNAL);
-    case HGC_POS_INT_OPS: return bit(HG_W_L) | bit(HG_Q_L);
-    case HGC_POS_INT_FINISH: return bit(HG_W_R) | bit(HG_W_O) | bit(HG_W_4) | shifts | bit(HG_Q_POSEIDON2_INTERNAL);
-    default: return 0;
+      return co_fold(S, wires | shifts | bit(HG_Q_M) | bit(HG_Q_C) | bit(HG_Q_L) | bit(HG_Q_R) | bit(HG_Q_O) | bit(HG_Q_4) | bit(HG_Q_MEMORY), 6, 1,
+                     true, 6, CoPass{3, {6, 12, 24}, {6, 6, 6}}, CoPass{3, {0, 18, 30}, {6, 6, 6}});
+    case HGC_NNF_OPS: return co_ops(S, wires | bit(HG_W_L_SHIFT) | bit(HG_W_R_SHIFT), 5, 5, 0, 0, false);
+    case HGC_NNF_FINISH:
+      return co_fold(S, wires | shifts | bit(HG_Q_M) | bit(HG_Q_R) | bit(HG_Q_O) | bit(HG_Q_4) | bit(HG_Q_NNF), 5, 0, false, 6, CoPass{1, {0}, {6}});
+    case HGC_POS_EXT_OPS: return co_ops(S, wires | bit(HG_Q_L) | bit(HG_Q_R) | bit(HG_Q_O) | bit(HG_Q_4), 4, 0, 0, 0, false);
+    case HGC_POS_EXT_FINISH: return co_fold(S, shifts | bit(HG_Q_POSEIDON2_EXTERNAL), 4, 0, false, 7, four_of_seven);
+    case HGC_POS_INT_OPS: return co_ops(S, bit(HG_W_L) | bit(HG_Q_L), 1, 0, 0, 0, false);
+    case HGC_POS_INT_FINISH:
+      return co_fold(S, bit(HG_W_R) | bit(HG_W_O) | bit(HG_W_4) | shifts | bit(HG_Q_POSEIDON2_INTERNAL), 1, 0, true, 7, four_of_seven);
+    default: return co_ops(S, 0, 0, 0, 0, 0, false);
   }
 }
 
-// A fold stage: its passes (launches), the subrelations of a pass (all of one length) with their place in the stage's output, its points
-// and the edges a workgroup takes per pass over the list. mem_finish folds its six subrelations in two launches of three -- r1, r2, r4,
-// which need neither the records nor the second product, and r0, r3, r5 -- so that a lane holds three running sums, not six.
-template <int STAGE, int PASS = 0>
-struct HgcFold {
-  static constexpr bool POS = STAGE == HGC_POS_EXT_FINISH || STAGE == HGC_POS_INT_FINISH, MEM = STAGE == HGC_MEM_FINISH;
-  static constexpr int PASSES = MEM ? 2 : 1;
-  static constexpr int NS = STAGE == HGC_ELL_FINISH ? 2 : (MEM ? 3 : (POS ? 4 : 1));
-  static constexpr int POINTS = POS ? 7 : 6;
-  static constexpr int EDGES_WG = POS ? 36 : 42;
-  // subrelation s of the pass is accumulator sub(s) of the stage: entry k at element sub(s) POINTS + k of the output
-  CSH_HD static constexpr int sub(int s) { return !MEM ? s : (PASS == 0 ? (s == 0 ? 1 : (s == 1 ? 2 : 4)) : (s == 0 ? 0 : (s == 1 ? 3 : 5))); }
-  static_assert(PASS < PASSES && POINTS * EDGES_WG <= 256, "one lane per point of an edge slot");
-};
-// operand vectors an operand stage writes per output (0 = the output is not written), and the parts of its inputs
-struct HgcParts {
-  int out[3], in, in2;
-};
-inline HgcParts hgc_parts_of(int stage) {
-  switch (stage) {
-    case HGC_ELL_OPS: return HgcParts{{7, 7, 0}, 0, 0};
-    case HGC_ELL_OPS2: return HgcParts{{5, 5, 0}, 7, 0};
-    case HGC_ELL_FINISH: return HgcParts{{0, 0, 0}, 7, 5};
-    case HGC_MEM_OPS: return HgcParts{{6, 6, 1}, 0, 0};
-    case HGC_MEM_FINISH: return HgcParts{{0, 0, 0}, 6, 1};
-    case HGC_NNF_OPS: return HgcParts{{5, 5, 0}, 0, 0};
-    case HGC_NNF_FINISH: return HgcParts{{0, 0, 0}, 5, 0};
-    case HGC_POS_EXT_OPS: return HgcParts{{4, 0, 0}, 0, 0};
-    case HGC_POS_EXT_FINISH: return HgcParts{{0, 0, 0}, 4, 0};
-    case HGC_POS_INT_OPS: return HgcParts{{1, 0, 0}, 0, 0};
-    case HGC_POS_INT_FINISH: return HgcParts{{0, 0, 0}, 1, 0};
-    default: return HgcParts{{0, 0, 0}, 0, 0};
-  }
-}
-// elements of a fold stage's output (0 for an operand stage)
-inline int hgc_acc_elems_of(int stage) {
-  switch (stage) {
-    case HGC_ELL_FINISH: return 12;
-    case HGC_MEM_FINISH: return 36;
-    case HGC_NNF_FINISH: return 6;
-    case HGC_POS_EXT_FINISH:
-    case HGC_POS_INT_FINISH: return 28;
-    default: return 0;
-  }
-}
-
-// What one call is told.
 template <class F>
-struct HgcArgs {
-  const F* col[HG_COLS];     // shares (0 .. 7, ncomp values per element) and public columns (8 .. 18)
-  const uint32_t* edge_idx;  // the kept e >> 1, ascending; NULL = every edge of the range
-  const F* scaling;          // NULL = one
-  size_t scaling_stride;
-  size_t edge_begin, m;      // m = kept edges
-  uint32_t ncomp;
-  int pub_comp;              // -1 = none
-  F eta[3], neg_curve_b, diag[4], limb, sublimb, one;  // arkworks-Montgomery
-  const F* in;               // the result of the network product in front of the stage
-  const F* in2;              // and of the second one (ell_finish, mem_finish)
-  F* out[3];
-  CSH_HD size_t n7() const { return HC_POINTS * m; }
+struct HgcArgs : CoArgs<F, HG_COLS> {
+  F eta[3], neg_curve_b, diag[4], limb, sublimb;  // arkworks-Montgomery
 };
 template <class F>
-inline void hgc_consts(HgcArgs<F>& a, const uint64_t* params) {
-  a.one = F::one();
+inline void hgc_consts(HgcArgs<F>& a, const CoCall& c) {
+  const uint64_t* params = c.params;
   F pw = F::add(a.one, a.one);  // 2^14 and 2^68 by square and multiply on 2
   a.sublimb = a.limb = a.one;
   for (int bit = 0; bit < 7; ++bit, pw = F::mul(pw, pw)) {
@@ -127,25 +71,9 @@ inline void hgc_consts(HgcArgs<F>& a, const uint64_t* params) {
   for (int i = 0; i < 4; ++i) a.diag[i] = params ? fr_load<F>(params + 16 + 4 * i) : F::zero();
 }
 
-// Batch element t = 7 j + k of the columns, on the component `comp` (HcPoint over the 19 columns).
-template <class F>
-struct HgcPoint {
-  const HgcArgs<F>& a;
-  size_t e;  // the edge's first element
-  int k;
-  unsigned comp;
-  CSH_HD HgcPoint(const HgcArgs<F>& a_, size_t j, int k_, unsigned comp_)
-      : a(a_), e(a_.edge_idx ? 2 * (size_t)a_.edge_idx[j] : a_.edge_begin + 2 * j), k(k_), comp(comp_) {}
-  CSH_HD F pub(int c) const { return hc_lerp(a.col[c][e], a.col[c][e + 1], k); }
-  CSH_HD F sh(int c) const { return hc_lerp(a.col[c][e * a.ncomp + comp], a.col[c][(e + 1) * a.ncomp + comp], k); }
-  CSH_HD bool is_pub() const { return (int)comp == a.pub_comp; }
-  CSH_HD F plus(const F& x, const F& v) const { return is_pub() ? F::add(x, v) : x; }  // x (+) v
-  CSH_HD F sc() const { return a.scaling ? a.scaling[(e >> 1) * a.scaling_stride] : a.one; }
-};
-
 // w_3 eta_three + w_2 eta_two + w_1 eta of the four columns from `first` on (memory_relation.rs:241-243, :328-336)
 template <class F>
-CSH_HD F hgc_record(const HgcPoint<F>& p, int first) {
+CSH_HD F hgc_record(const CoPoint<HgcArgs<F>>& p, int first) {
   const HgcArgs<F>& a = p.a;
   F r = F::mul(p.sh(first + 2), a.eta[2]);
   r = F::add(r, F::mul(p.sh(first + 1), a.eta[1]));
@@ -153,7 +81,7 @@ CSH_HD F hgc_record(const HgcPoint<F>& p, int first) {
 }
 // (((x0 2^14 + x1) 2^14 + x2) 2^14 + x3) 2^14 of four columns (non_native_field_relation.rs:183-189, :195-201)
 template <class F>
-CSH_HD F hgc_limbs(const HgcPoint<F>& p, int c0, int c1, int c2, int c3) {
+CSH_HD F hgc_limbs(const CoPoint<HgcArgs<F>>& p, int c0, int c1, int c2, int c3) {
   const F& s = p.a.sublimb;
   F r = F::mul(p.sh(c0), s);
   r = F::mul(F::add(r, p.sh(c1)), s);
@@ -165,7 +93,7 @@ CSH_HD F hgc_limbs(const HgcPoint<F>& p, int c0, int c1, int c2, int c3) {
 template <int STAGE, class F>
 CSH_HD void hgc_ops_at(const HgcArgs<F>& a, size_t u) {
   const size_t t = a.ncomp == 1 ? u : u >> 1, seg = a.n7() * a.ncomp;
-  const HgcPoint<F> p(a, t / HC_POINTS, (int)(t % HC_POINTS), (unsigned)(u & (size_t)(a.ncomp - 1)));
+  const CoPoint<HgcArgs<F>> p(a, t / HC_POINTS, (int)(t % HC_POINTS), (unsigned)(u & (size_t)(a.ncomp - 1)));
   F* lhs = a.out[0];
   F* rhs = a.out[1];
   if constexpr (STAGE == HGC_ELL_OPS) {
@@ -234,7 +162,7 @@ CSH_HD void hgc_ops_at(const HgcArgs<F>& a, size_t u) {
 // ---- fold stages: what batch element 7 j + k adds to the stage's accumulators on the component `comp` -------------------------------------
 template <int STAGE, int PASS, class F>
 CSH_HD void hgc_terms_at(const HgcArgs<F>& a, size_t j, int k, unsigned comp, F* term) {
-  const HgcPoint<F> p(a, j, k, comp);
+  const CoPoint<HgcArgs<F>> p(a, j, k, comp);
   const size_t t = HC_POINTS * j + k, seg = a.n7() * a.ncomp, u = t * a.ncomp + comp;
   if constexpr (STAGE == HGC_ELL_FINISH) {
     // elliptic_relation.rs:199-252; in2 = mul2 = [(x3 + x2 + x1) x_diff^2 | (y1^2 - b) 3 x1 | (x3 + 2 x1) 4 y1^2 | 3 x1^2 (x1 - x3) |
@@ -316,5 +244,18 @@ CSH_HD void hgc_terms_at(const HgcArgs<F>& a, size_t j, int k, unsigned comp, F*
     term[3] = F::mul(F::sub(F::add(F::mul(u_4, a.diag[3]), sum), p.sh(HG_W_4_SHIFT)), qs);
   }
 }
+
+struct HgcFamily {
+  template <class F>
+  using Args = HgcArgs<F>;
+  static constexpr int COLS = HG_COLS, STAGES = HGC_STAGES;
+  static constexpr CoStage stage(int s) { return hgc_stage(s); }
+  template <class F>
+  static void consts(HgcArgs<F>& a, const CoCall& c) { hgc_consts(a, c); }
+  template <int STAGE, class F>
+  CSH_HD static void ops_at(const HgcArgs<F>& a, size_t u) { hgc_ops_at<STAGE>(a, u); }
+  template <int STAGE, int PASS, class F>
+  CSH_HD static void terms_at(const HgcArgs<F>& a, size_t j, int k, unsigned comp, F* term) { hgc_terms_at<STAGE, PASS>(a, j, k, comp, term); }
+};
 
 }  // namespace csh

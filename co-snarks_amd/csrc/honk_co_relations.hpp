@@ -1,32 +1,19 @@
-// The sumcheck round of co-noir's collaborative UltraHonk prover on shares (honk_co_relations.hip): the stretches
-// of local arithmetic between two network rounds of the four relations of subrelations 0 .. 10, in
+// The four relations of the collaborative UltraHonk sumcheck round on shares (honk_co_relations.hip): the
+// stretches of local arithmetic between two network rounds of the relations of subrelations 0 .. 10, in
 // co-noir/co-ultrahonk/src/co_decider/relations/: UltraArithmeticRelation (ultra_arithmetic_relation.rs:88-239), UltraPermutationRelation
 // (permutation_relation.rs:70-150, :202-249), DeltaRangeConstraintRelation (delta_range_constraint_relation.rs:126-216) and
-// LogDerivLookupRelation (logderiv_lookup_relation.rs:77-168, :255-312), the `can_skip` selection of the edges, and the reduction that ends
-// every relation, fold_accumulator! (relations/mod.rs:45-57). What the kernels and the host self-test share: the argument struct, the
-// element rule, every stage's loop body.
-//
-// The batch is never built. The reference's batch element t of a column (extend_edges + fold_and_filter + add_entities,
-// co_sumcheck/co_sumcheck_round.rs:54-73, types_batch.rs:105-130, relations/mod.rs:69-80) belongs to kept edge j = t / 7 and point
-// k = t % 7 and is col[e] + k (col[e + 1] - col[e]) per component, e = 2 edge_idx[j] with an edge list and edge_begin + 2 j without; its
-// scaling element is scaling[(e >> 1) stride]. Every stage computes its elements from the columns through this rule (HcPoint); the only
-// vectors in memory are the operands and results of the network products, in the reference's concatenation order.
+// LogDerivLookupRelation (logderiv_lookup_relation.rs:77-168, :255-312), and the `can_skip` rule of the edge selection. What is this
+// family's own in the stage framework of honk_co_stage.hpp: the stage enum, the stages' descriptors, the constants, and every stage's loop
+// body, which the kernels and the host self-test share. The columns are the 36 of honk_relations.hpp (HrCol): 0 .. 12 shares, 13 .. 35
+// public.
 //
 // Arithmetic. Unlike the plain kernels (honk_relations.hpp) the stages work in the exact 32-bit-limb field F: every value is canonical
 // between two operations, so there are no limb bounds to derive and none that could depend on the data, the range or the stride. The
 // longest chain of a lane is a dozen products; the stages stream operand vectors and are bound by them. Outputs are canonical.
-//
-// Shares. ncomp = 1 for protocol 0 (plain / Shamir), 2 for Rep3 ({a, b} interleaved); value (i, c) of a share vector is v[i ncomp + c].
-// x (+) v adds the public v on the component pub_comp (a for protocol 0 and Rep3 party 0, b for Rep3 party 1, none for party 2).
 #pragma once
-#include "honk_relations.hpp"
-#include "plonk_quot.hpp"
+#include "honk_co_stage.hpp"
 
 namespace csh {
-
-constexpr int HC_POINTS = 7;        // MAX_PARTIAL_RELATION_LENGTH: points per kept edge in an operand vector
-constexpr int HC_FOLD_POINTS = 6;   // the longest accumulator: fold_accumulator! drops the point 6
-constexpr int HC_MAX_SUB = 4;       // subrelations a fold stage reduces at once
 
 enum HcStage : int {
   HC_SELECT = 0,
@@ -36,68 +23,48 @@ enum HcStage : int {
   HC_LOOKUP_OPS, HC_LOOKUP_MID_R0, HC_LOOKUP_MID_OPS, HC_LOOKUP_FINISH
 };
 
-// the columns a stage reads, as a mask over HrCol
-CSH_HD uint64_t hc_bit(int c) { return uint64_t(1) << c; }
-inline uint64_t hc_cols_of(int stage) {
-  const uint64_t wires = hc_bit(HR_W_L) | hc_bit(HR_W_R) | hc_bit(HR_W_O) | hc_bit(HR_W_4);
-  const uint64_t tables = hc_bit(HR_TABLE_1) | hc_bit(HR_TABLE_2) | hc_bit(HR_TABLE_3) | hc_bit(HR_TABLE_4);
+// The stages as data; the accumulator lengths are the reference's (6, 5, 6, 3, 5, 5, 3, 6, 6, 6, 6). HC_SELECT and HC_DELTA_SUB_ONE read no
+// column and are neither an operand nor a fold stage. arith_r0 is a half share: one component per element, both components read.
+constexpr uint64_t hc_bit(int c) { return uint64_t(1) << c; }
+constexpr CoStage hc_stage(int stage) {
+  constexpr int S = HR_Q_M;  // the columns in front of q_m are shares
+  constexpr uint64_t wires = hc_bit(HR_W_L) | hc_bit(HR_W_R) | hc_bit(HR_W_O) | hc_bit(HR_W_4);
+  constexpr uint64_t tables = hc_bit(HR_TABLE_1) | hc_bit(HR_TABLE_2) | hc_bit(HR_TABLE_3) | hc_bit(HR_TABLE_4);
   switch (stage) {
     case HC_ARITH_R0:
-      return wires | hc_bit(HR_W_4_SHIFT) | hc_bit(HR_Q_M) | hc_bit(HR_Q_C) | hc_bit(HR_Q_L) | hc_bit(HR_Q_R) | hc_bit(HR_Q_O) | hc_bit(HR_Q_4) |
-             hc_bit(HR_Q_ARITH);
-    case HC_ARITH_R1: return hc_bit(HR_W_L) | hc_bit(HR_W_4) | hc_bit(HR_W_L_SHIFT) | hc_bit(HR_Q_M) | hc_bit(HR_Q_ARITH);
+      return co_fold(S, wires | hc_bit(HR_W_4_SHIFT) | hc_bit(HR_Q_M) | hc_bit(HR_Q_C) | hc_bit(HR_Q_L) | hc_bit(HR_Q_R) | hc_bit(HR_Q_O) |
+                            hc_bit(HR_Q_4) | hc_bit(HR_Q_ARITH),
+                     0, 0, false, 6, CoPass{1, {0}, {6}}, CoPass{}, true);
+    case HC_ARITH_R1:
+      return co_fold(S, hc_bit(HR_W_L) | hc_bit(HR_W_4) | hc_bit(HR_W_L_SHIFT) | hc_bit(HR_Q_M) | hc_bit(HR_Q_ARITH), 0, 0, false, 6,
+                     CoPass{1, {0}, {5}});
     case HC_PERM_OPS:
-      return wires | hc_bit(HR_SIGMA_1) | hc_bit(HR_SIGMA_2) | hc_bit(HR_SIGMA_3) | hc_bit(HR_SIGMA_4) | hc_bit(HR_ID_1) | hc_bit(HR_ID_2) |
-             hc_bit(HR_ID_3) | hc_bit(HR_ID_4);
-    case HC_PERM_OPS2: return hc_bit(HR_Z_PERM) | hc_bit(HR_Z_PERM_SHIFT) | hc_bit(HR_LAGRANGE_FIRST) | hc_bit(HR_LAGRANGE_LAST);
-    case HC_PERM_FINISH: return hc_bit(HR_Z_PERM_SHIFT) | hc_bit(HR_LAGRANGE_LAST);
-    case HC_DELTA_OPS: return wires | hc_bit(HR_W_L_SHIFT);
-    case HC_DELTA_FINISH: return hc_bit(HR_Q_DELTA_RANGE);
+      return co_ops(S, wires | hc_bit(HR_SIGMA_1) | hc_bit(HR_SIGMA_2) | hc_bit(HR_SIGMA_3) | hc_bit(HR_SIGMA_4) | hc_bit(HR_ID_1) |
+                           hc_bit(HR_ID_2) | hc_bit(HR_ID_3) | hc_bit(HR_ID_4),
+                    4, 4, 0, 0, true);
+    case HC_PERM_OPS2:
+      return co_ops(S, hc_bit(HR_Z_PERM) | hc_bit(HR_Z_PERM_SHIFT) | hc_bit(HR_LAGRANGE_FIRST) | hc_bit(HR_LAGRANGE_LAST), 2, 0, 0, 0, true);
+    case HC_PERM_FINISH: return co_fold(S, hc_bit(HR_Z_PERM_SHIFT) | hc_bit(HR_LAGRANGE_LAST), 2, 0, false, 6, CoPass{2, {0, 6}, {6, 3}});
+    case HC_DELTA_OPS: return co_ops(S, wires | hc_bit(HR_W_L_SHIFT), 8, 0, 0, 0, false);
+    case HC_DELTA_FINISH: return co_fold(S, hc_bit(HR_Q_DELTA_RANGE), 4, 0, false, 6, CoPass{4, {0, 6, 12, 18}, {6, 6, 6, 6}});
     case HC_LOOKUP_OPS:
-      return hc_bit(HR_W_L) | hc_bit(HR_W_R) | hc_bit(HR_W_O) | hc_bit(HR_W_L_SHIFT) | hc_bit(HR_W_R_SHIFT) | hc_bit(HR_W_O_SHIFT) | hc_bit(HR_Q_R) |
-             hc_bit(HR_Q_M) | hc_bit(HR_Q_C) | hc_bit(HR_Q_O) | hc_bit(HR_LOOKUP_INVERSES);
-    case HC_LOOKUP_MID_R0: return tables | hc_bit(HR_LOOKUP_READ_TAGS) | hc_bit(HR_Q_LOOKUP);
-    case HC_LOOKUP_MID_OPS: return hc_bit(HR_LOOKUP_READ_TAGS) | hc_bit(HR_LOOKUP_READ_COUNTS);
-    case HC_LOOKUP_FINISH: return tables | hc_bit(HR_Q_LOOKUP) | hc_bit(HR_LOOKUP_INVERSES) | hc_bit(HR_LOOKUP_READ_TAGS);
-    default: return 0;
+      return co_ops(S, hc_bit(HR_W_L) | hc_bit(HR_W_R) | hc_bit(HR_W_O) | hc_bit(HR_W_L_SHIFT) | hc_bit(HR_W_R_SHIFT) | hc_bit(HR_W_O_SHIFT) |
+                           hc_bit(HR_Q_R) | hc_bit(HR_Q_M) | hc_bit(HR_Q_C) | hc_bit(HR_Q_O) | hc_bit(HR_LOOKUP_INVERSES),
+                    1, 1, 0, 0, true);
+    case HC_LOOKUP_MID_R0: return co_fold(S, tables | hc_bit(HR_LOOKUP_READ_TAGS) | hc_bit(HR_Q_LOOKUP), 1, 0, true, 6, CoPass{1, {0}, {5}});
+    case HC_LOOKUP_MID_OPS: return co_ops(S, hc_bit(HR_LOOKUP_READ_TAGS) | hc_bit(HR_LOOKUP_READ_COUNTS), 0, 2, 2, 1, false);
+    case HC_LOOKUP_FINISH:
+      return co_fold(S, tables | hc_bit(HR_Q_LOOKUP) | hc_bit(HR_LOOKUP_INVERSES) | hc_bit(HR_LOOKUP_READ_TAGS), 2, 0, true, 6,
+                     CoPass{2, {0, 5}, {5, 3}});
+    default: return co_ops(S, 0, 0, 0, 0, 0, false);
   }
 }
-// subrelations of a fold stage and their accumulator lengths (the reference's: 6, 5, 6, 3, 5, 5, 3, 6, 6, 6, 6)
-struct HcFold {
-  int ns;
-  int len[HC_MAX_SUB];
-};
-inline HcFold hc_fold_of(int stage) {
-  switch (stage) {
-    case HC_ARITH_R0: return HcFold{1, {6, 0, 0, 0}};
-    case HC_ARITH_R1: return HcFold{1, {5, 0, 0, 0}};
-    case HC_PERM_FINISH: return HcFold{2, {6, 3, 0, 0}};
-    case HC_DELTA_FINISH: return HcFold{4, {6, 6, 6, 6}};
-    case HC_LOOKUP_MID_R0: return HcFold{1, {5, 0, 0, 0}};
-    case HC_LOOKUP_FINISH: return HcFold{2, {5, 3, 0, 0}};
-    default: return HcFold{0, {0, 0, 0, 0}};
-  }
-}
-template <int STAGE>
-struct HcNs {
-  static constexpr int value = STAGE == HC_DELTA_FINISH ? 4 : ((STAGE == HC_PERM_FINISH || STAGE == HC_LOOKUP_FINISH) ? 2 : 1);
-};
 
-// What one call is told.
 template <class F>
-struct HcArgs {
-  const F* col[HR_COLS];     // shares (0 .. 12, ncomp values per element) and public columns (13 .. 35)
-  const uint32_t* edge_idx;  // the kept e >> 1, ascending; NULL = every edge of the range
-  const F* scaling;          // NULL = one
-  size_t scaling_stride;
-  size_t edge_begin, m;      // m = kept edges
-  uint32_t ncomp, protocol, party;
-  int pub_comp;              // -1 = none
-  F beta, gamma, pid, beta2, beta3, one, two, three, neg_half, neg_one, neg_two;  // arkworks-Montgomery
-  const F* in;               // the result of the network product in front of the stage
+struct HcArgs : CoArgs<F, HR_COLS> {
+  uint32_t protocol, party;
+  F beta, gamma, pid, beta2, beta3, two, three, neg_half, neg_one, neg_two;  // arkworks-Montgomery
   const F* mask;             // HC_ARITH_R0, Rep3: 7 m elements
-  F* out[3];
-  CSH_HD size_t n7() const { return HC_POINTS * m; }
 };
 // -1/2, the one constant that costs a field inversion: made once per field, not once per call
 template <class F>
@@ -106,46 +73,19 @@ inline const F& hc_neg_half() {
   return v;
 }
 template <class F>
-inline void hc_consts(HcArgs<F>& a, const uint64_t* params) {
-  a.one = F::one();
+inline void hc_consts(HcArgs<F>& a, const CoCall& c) {
+  a.protocol = c.protocol, a.party = c.party, a.mask = nullptr;
   a.two = F::add(a.one, a.one);
   a.three = F::add(a.two, a.one);
   a.neg_one = F::neg(a.one);
   a.neg_two = F::neg(a.two);
   a.neg_half = hc_neg_half<F>();
   a.beta = a.gamma = a.pid = a.beta2 = a.beta3 = F::zero();
-  if (params) {
-    a.beta = fr_load<F>(params), a.gamma = fr_load<F>(params + 4), a.pid = fr_load<F>(params + 8);
+  if (c.params) {
+    a.beta = fr_load<F>(c.params), a.gamma = fr_load<F>(c.params + 4), a.pid = fr_load<F>(c.params + 8);
     a.beta2 = F::mul(a.beta, a.beta), a.beta3 = F::mul(a.beta2, a.beta);
   }
 }
-
-// v0 + k (v1 - v0), 0 <= k <= 6: Univariate::extend_from of a pair (univariate.rs:57-178), by the reference's running sum
-template <class F>
-CSH_HD F hc_lerp(const F& v0, const F& v1, int k) {
-  const F d = F::sub(v1, v0);
-  F r = v0;
-#pragma unroll 1
-  for (int i = 0; i < k; ++i) r = F::add(r, d);
-  return r;
-}
-
-// Batch element t = 7 j + k of the columns, on the component `comp`.
-template <class F>
-struct HcPoint {
-  const HcArgs<F>& a;
-  size_t e;  // the edge's first element
-  int k;
-  unsigned comp;
-  CSH_HD HcPoint(const HcArgs<F>& a_, size_t j, int k_, unsigned comp_)
-      : a(a_), e(a_.edge_idx ? 2 * (size_t)a_.edge_idx[j] : a_.edge_begin + 2 * j), k(k_), comp(comp_) {}
-  CSH_HD F pub(int c) const { return hc_lerp(a.col[c][e], a.col[c][e + 1], k); }
-  CSH_HD F sh(int c, unsigned cc) const { return hc_lerp(a.col[c][e * a.ncomp + cc], a.col[c][(e + 1) * a.ncomp + cc], k); }
-  CSH_HD F sh(int c) const { return sh(c, comp); }
-  CSH_HD bool is_pub() const { return (int)comp == a.pub_comp; }
-  CSH_HD F plus(const F& x, const F& v) const { return is_pub() ? F::add(x, v) : x; }  // x (+) v
-  CSH_HD F sc() const { return a.scaling ? a.scaling[(e >> 1) * a.scaling_stride] : a.one; }
-};
 
 // can_skip of the arithmetic and the delta-range relation (ultra_arithmetic_relation.rs:247-249, delta_range_constraint_relation.rs:94-96):
 // the extended selector is zero at all seven points exactly when it is zero at both ends
@@ -156,7 +96,7 @@ CSH_HD bool hc_keep(const F* q, size_t e) {
 
 // write_term, logderiv_lookup_relation.rs:142-168 (public)
 template <class F>
-CSH_HD F hc_write_term(const HcPoint<F>& p) {
+CSH_HD F hc_write_term(const CoPoint<HcArgs<F>>& p) {
   const HcArgs<F>& a = p.a;
   F w = F::add(p.pub(HR_TABLE_1), a.gamma);
   w = F::add(w, F::mul(p.pub(HR_TABLE_2), a.beta));
@@ -168,7 +108,7 @@ CSH_HD F hc_write_term(const HcPoint<F>& p) {
 template <int STAGE, class F>
 CSH_HD void hc_ops_at(const HcArgs<F>& a, size_t u) {
   const size_t t = a.ncomp == 1 ? u : u >> 1, seg = a.n7() * a.ncomp;
-  const HcPoint<F> p(a, t / HC_POINTS, (int)(t % HC_POINTS), (unsigned)(u & (size_t)(a.ncomp - 1)));
+  const CoPoint<HcArgs<F>> p(a, t / HC_POINTS, (int)(t % HC_POINTS), (unsigned)(u & (size_t)(a.ncomp - 1)));
   if constexpr (STAGE == HC_PERM_OPS) {
     // permutation_relation.rs:94-146: lhs = [wid1 | wsigma1 | wid3 | wsigma3], rhs = [wid2 | wsigma2 | wid4 | wsigma4]
 #pragma unroll
@@ -222,9 +162,9 @@ CSH_HD void hc_sub_one_at(const HcArgs<F>& a, size_t u) {
 }
 
 // ---- fold stages: what batch element 7 j + k adds to the stage's accumulators on the component `comp` -------------------------------------
-template <int STAGE, class F>
+template <int STAGE, int PASS, class F>
 CSH_HD void hc_terms_at(const HcArgs<F>& a, size_t j, int k, unsigned comp, F* term) {
-  const HcPoint<F> p(a, j, k, comp);
+  const CoPoint<HcArgs<F>> p(a, j, k, comp);
   const size_t t = HC_POINTS * j + k, seg = a.n7() * a.ncomp, u = t * a.ncomp + comp;
   if constexpr (STAGE == HC_ARITH_R0) {
     // ultra_arithmetic_relation.rs:88-189: a half share, one component per element
@@ -275,5 +215,18 @@ CSH_HD void hc_terms_at(const HcArgs<F>& a, size_t j, int k, unsigned comp, F* t
     term[1] = F::mul(F::sub(a.in[seg + u], p.sh(HR_LOOKUP_READ_TAGS)), p.sc());
   }
 }
+
+struct HcFamily {
+  template <class F>
+  using Args = HcArgs<F>;
+  static constexpr int COLS = HR_COLS, STAGES = HC_LOOKUP_FINISH + 1;
+  static constexpr CoStage stage(int s) { return hc_stage(s); }
+  template <class F>
+  static void consts(HcArgs<F>& a, const CoCall& c) { hc_consts(a, c); }
+  template <int STAGE, class F>
+  CSH_HD static void ops_at(const HcArgs<F>& a, size_t u) { hc_ops_at<STAGE>(a, u); }
+  template <int STAGE, int PASS, class F>
+  CSH_HD static void terms_at(const HcArgs<F>& a, size_t j, int k, unsigned comp, F* term) { hc_terms_at<STAGE, PASS>(a, j, k, comp, term); }
+};
 
 }  // namespace csh

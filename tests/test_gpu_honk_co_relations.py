@@ -169,9 +169,10 @@ def run_case(hip, curve, kind, c, b, e, stride=1, scaled=True, device_net=False,
     return got, CO.plain_accumulate(p, c["polys"], b, e, table, stride, c["params"]), dev
 
 
-# 1, 2, 3 edges; 36 and 37: across the 42 edge slots of a workgroup's pass with the 7 m values of a vector across 256; 257: several passes
+# 1, 2, 3 edges; 36 and 37: the 7 m values of a plain operand vector across the 256 lanes of a workgroup (252, 259); 41 .. 43: across the
+# 42 edge slots of a workgroup's pass of the fold; 257: several passes
 @pytest.mark.parametrize("kind", ["rep3", "plain"])
-@pytest.mark.parametrize("edges", [1, 2, 3, 36, 37, 257])
+@pytest.mark.parametrize("edges", [1, 2, 3, 36, 37, 41, 42, 43, 257])
 def test_stage_parity_on_bn254(gpu, kind, edges):
     got, want, _ = run_case(gpu, "bn254", kind, case("bn254", edges), 0, 2 * edges)
     assert got == want
