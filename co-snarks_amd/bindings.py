@@ -680,33 +680,39 @@ def honk_z_perm_place(curve: int, protocol: int, party: int, mul, z, n: int, dom
 
 
 HONK_SUMCHECK_COLUMNS = 36        # witness (8), shifted witness (5), precomputed (23): the order of include/cosnarks_hip.h
+HONK_SUMCHECK_PARAMS = 3          # beta, gamma, public_input_delta
 HONK_SUMCHECK_ACC_ELEMS = 57      # 6 + 5 + 6 + 3 + 5 + 5 + 3 + 6 + 6 + 6 + 6
+HONK_GATES_COLUMNS = 19           # w (4), shifted w (4), q_m .. q_4 (6), the five gate selectors: the order of include/cosnarks_hip.h
+HONK_GATES_PARAMS = 8             # eta_1..3, curve_b, mat_internal_diag_m_1[0..4)
+HONK_GATES_ACC_ELEMS = 110        # 2 * 6 + 6 * 6 + 6 + 4 * 7 + 4 * 7
 HONK_MAX_EDGE_END = 1 << 28
+
+
+def _honk_accumulate(what, ncols, nparams, acc_elems, curve, cols, edge_begin, edge_end, params, acc, scaling, scaling_stride, stream):
+    """The plain round's two entries: csh_<what>_dev after the column count, the parameter count and the range rules."""
+    if len(cols) != ncols:
+        raise CoSnarksHipError("%s: %d columns, not %d" % (what, len(cols), ncols))
+    if edge_begin < 0 or edge_begin % 2 or edge_end % 2 or not edge_begin < edge_end <= HONK_MAX_EDGE_END:
+        raise CoSnarksHipError("%s: edge_begin and edge_end must be even, edge_begin < edge_end <= 2^28" % what)
+    if scaling is not None and not 1 <= scaling_stride <= HONK_MAX_EDGE_END:
+        raise CoSnarksHipError("%s: scaling_stride must be 1 .. 2^28" % what)
+    pr = _u64(params)
+    if pr.size != 4 * nparams:
+        raise CoSnarksHipError("%s: %d parameter words, not %d elements of 4" % (what, pr.size, nparams))
+    if acc is None:
+        acc = DeviceBuffer(32 * acc_elems)
+    _check(getattr(lib(), "csh_%s_dev" % what)(curve, _devptr_array(cols), C.c_size_t(edge_begin), C.c_size_t(edge_end), _devptr(scaling),
+                                               C.c_size_t(scaling_stride), _p(pr), _devptr(acc), _stream(stream)))
+    return acc
 
 
 def honk_sumcheck_accumulate(curve: int, cols, edge_begin: int, edge_end: int, params, acc=None, scaling=None, scaling_stride: int = 1, stream=None):
     """csh_honk_sumcheck_accumulate_dev: cols = the 36 DeviceBuffers (or device addresses) in the header's order; elements
     [edge_begin, edge_end) of each are read; params = beta, gamma, public_input_delta on the host; scaling = the DeviceBuffer of the
     gate-separator products (honk_pow_table) read at (e >> 1) * scaling_stride, or None for the factor one. acc (57 elements, made here
-    unless given) is returned. The column count and the range rules are checked here, before the call."""
-    if len(cols) != HONK_SUMCHECK_COLUMNS:
-        raise CoSnarksHipError("honk_sumcheck_accumulate: %d columns, not %d" % (len(cols), HONK_SUMCHECK_COLUMNS))
-    if edge_begin < 0 or edge_begin % 2 or edge_end % 2 or not edge_begin < edge_end <= HONK_MAX_EDGE_END:
-        raise CoSnarksHipError("honk_sumcheck_accumulate: edge_begin and edge_end must be even, edge_begin < edge_end <= 2^28")
-    if scaling is not None and not 1 <= scaling_stride <= HONK_MAX_EDGE_END:
-        raise CoSnarksHipError("honk_sumcheck_accumulate: scaling_stride must be 1 .. 2^28")
-    pr = _u64(params)
-    assert pr.size == 12
-    if acc is None:
-        acc = DeviceBuffer(32 * HONK_SUMCHECK_ACC_ELEMS)
-    _check(lib().csh_honk_sumcheck_accumulate_dev(curve, _devptr_array(cols), C.c_size_t(edge_begin), C.c_size_t(edge_end), _devptr(scaling),
-                                                  C.c_size_t(scaling_stride), _p(pr), _devptr(acc), _stream(stream)))
-    return acc
-
-
-HONK_GATES_COLUMNS = 19           # w (4), shifted w (4), q_m .. q_4 (6), the five gate selectors: the order of include/cosnarks_hip.h
-HONK_GATES_PARAMS = 8             # eta_1..3, curve_b, mat_internal_diag_m_1[0..4)
-HONK_GATES_ACC_ELEMS = 110        # 2 * 6 + 6 * 6 + 6 + 4 * 7 + 4 * 7
+    unless given) is returned. The column count, the parameter count and the range rules are checked here, before the call."""
+    return _honk_accumulate("honk_sumcheck_accumulate", HONK_SUMCHECK_COLUMNS, HONK_SUMCHECK_PARAMS, HONK_SUMCHECK_ACC_ELEMS, curve, cols,
+                            edge_begin, edge_end, params, acc, scaling, scaling_stride, stream)
 
 
 def honk_sumcheck_accumulate_gates(curve: int, cols, edge_begin: int, edge_end: int, params, acc=None, scaling=None, scaling_stride: int = 1,
@@ -715,20 +721,8 @@ def honk_sumcheck_accumulate_gates(curve: int, cols, edge_begin: int, edge_end: 
     eta_2, eta_3, curve_b and the four internal diagonal values on the host (8 elements); range and scaling as honk_sumcheck_accumulate.
     acc (110 elements, made here unless given) is returned. The column count, the parameter count and the range rules are checked here,
     before the call."""
-    if len(cols) != HONK_GATES_COLUMNS:
-        raise CoSnarksHipError("honk_sumcheck_accumulate_gates: %d columns, not %d" % (len(cols), HONK_GATES_COLUMNS))
-    if edge_begin < 0 or edge_begin % 2 or edge_end % 2 or not edge_begin < edge_end <= HONK_MAX_EDGE_END:
-        raise CoSnarksHipError("honk_sumcheck_accumulate_gates: edge_begin and edge_end must be even, edge_begin < edge_end <= 2^28")
-    if scaling is not None and not 1 <= scaling_stride <= HONK_MAX_EDGE_END:
-        raise CoSnarksHipError("honk_sumcheck_accumulate_gates: scaling_stride must be 1 .. 2^28")
-    pr = _u64(params)
-    if pr.size != 4 * HONK_GATES_PARAMS:
-        raise CoSnarksHipError("honk_sumcheck_accumulate_gates: %d parameter words, not %d elements of 4" % (pr.size, HONK_GATES_PARAMS))
-    if acc is None:
-        acc = DeviceBuffer(32 * HONK_GATES_ACC_ELEMS)
-    _check(lib().csh_honk_sumcheck_accumulate_gates_dev(curve, _devptr_array(cols), C.c_size_t(edge_begin), C.c_size_t(edge_end), _devptr(scaling),
-                                                        C.c_size_t(scaling_stride), _p(pr), _devptr(acc), _stream(stream)))
-    return acc
+    return _honk_accumulate("honk_sumcheck_accumulate_gates", HONK_GATES_COLUMNS, HONK_GATES_PARAMS, HONK_GATES_ACC_ELEMS, curve, cols,
+                            edge_begin, edge_end, params, acc, scaling, scaling_stride, stream)
 
 
 def honk_pow_table(curve: int, betas, out=None, stream=None):

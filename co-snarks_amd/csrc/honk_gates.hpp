@@ -16,7 +16,7 @@
 // poseidon2_internal.r0 .. r3 (7 each); entry i of an accumulator is its evaluation at the point i.
 //
 // Groups. Seventeen running sums and the S-boxes do not fit under 256 VGPRs, so the relations are dealt to three launches of one kernel
-// template (HgGroup): EN = elliptic + nnf (3 sums, 6 points, 42 edges per pass), MEM = memory (6 sums, 6 points, 42 edges per pass), POS =
+// template (hg_group): EN = elliptic + nnf (3 sums, 6 points, 42 edges per pass), MEM = memory (6 sums, 6 points, 42 edges per pass), POS =
 // Poseidon2 external + internal (8 sums, 7 points, 36 edges per pass). A lane takes ONE point of one edge, as in honk_relations.hpp.
 //
 // Skips. Each relation is left out of an edge when its own selector is zero at both ends (Relation::skip of the five files: the selector's
@@ -46,10 +46,6 @@
 namespace csh {
 
 constexpr int HG_COLS = 19;
-constexpr int HG_SUBRELATIONS = 17;
-constexpr int HG_ACC_ELEMS = 110;
-constexpr int HG_PARAMS = 8;
-constexpr int HG_GROUPS = 3;
 
 enum HgCol : int {
   HG_W_L = 0, HG_W_R, HG_W_O, HG_W_4, HG_W_L_SHIFT, HG_W_R_SHIFT, HG_W_O_SHIFT, HG_W_4_SHIFT,
@@ -57,34 +53,18 @@ enum HgCol : int {
   HG_Q_ELLIPTIC, HG_Q_MEMORY, HG_Q_NNF, HG_Q_POSEIDON2_EXTERNAL, HG_Q_POSEIDON2_INTERNAL
 };
 
-// A group of relations that one launch takes: its running sums, its points, its edges per pass of a workgroup, and where its sums lie in
-// acc[110]. 6 x 42 = 7 x 36 = 252 lanes of 256 at work.
+// The groups, as honk_stage.hpp reads them: running sums, points, edges per pass of a workgroup (6 x 42 = 7 x 36 = 252 lanes of 256 at
+// work), two waves per SIMD asked of the launch bound, then where each sum lies in acc[110] and its length.
 enum HgGroupId : int { HG_EN = 0, HG_MEM = 1, HG_POS = 2 };
-template <int G>
-struct HgGroup;
-template <>
-struct HgGroup<HG_EN> {
-  static constexpr int SUMS = 3, POINTS = 6, EDGES_WG = 42;
-  CSH_HD static int off(int s) { return s < 2 ? 6 * s : 48; }  // elliptic.r0, r1, nnf.r0
-};
-template <>
-struct HgGroup<HG_MEM> {
-  static constexpr int SUMS = 6, POINTS = 6, EDGES_WG = 42;
-  CSH_HD static int off(int s) { return 12 + 6 * s; }
-};
-template <>
-struct HgGroup<HG_POS> {
-  static constexpr int SUMS = 8, POINTS = 7, EDGES_WG = 36;
-  CSH_HD static int off(int s) { return 54 + 7 * s; }
-};
+constexpr HsGroup hg_group(int g) {
+  return g == HG_EN    ? HsGroup{3, 6, 42, 2, {0, 6, 48}, {6, 6, 6}}  // elliptic.r0, r1, nnf.r0
+         : g == HG_MEM ? HsGroup{6, 6, 42, 2, {12, 18, 24, 30, 36, 42}, {6, 6, 6, 6, 6, 6}}
+                       : HsGroup{8, 7, 36, 2, {54, 61, 68, 75, 82, 89, 96, 103}, {7, 7, 7, 7, 7, 7, 7, 7}};
+}
 
-// What one call is told. Edge j (0 <= j < n_edges) is the pair of elements edge_begin + 2 j, edge_begin + 2 j + 1 of every column.
+// The constants of a call beside HsArgs's; hg_consts finds a.one set (hs_args)
 template <class F>
-struct HgArgs {
-  const F* col[HG_COLS];
-  const F* scaling;       // factor of edge j = scaling[((edge_begin >> 1) + j) * scaling_stride]; NULL = one
-  size_t scaling_stride;
-  size_t edge_begin, n_edges;
+struct HgArgs : HsArgs<F, HG_COLS> {
   F etad[3], diagd[4], limbd, sublimbd;  // eta_1..3 R', mat_internal_diag_m_1[0..4) R', 2^68 R', 2^14 R'
   F curve_b, one;                        // arkworks-Montgomery
 };
@@ -93,7 +73,6 @@ inline void hg_consts(HgArgs<F>& a, const uint64_t* params) {
   for (int i = 0; i < 3; ++i) a.etad[i] = fr_to_rprime(fr_load<F>(params + 4 * i));
   a.curve_b = fr_load<F>(params + 12);
   for (int i = 0; i < 4; ++i) a.diagd[i] = fr_to_rprime(fr_load<F>(params + 16 + 4 * i));
-  a.one = F::one();
   F pw = F::add(a.one, a.one), sub = a.one, limb = a.one;  // 2^14 and 2^68 by square and multiply on 2
   for (int bit = 0; bit < 7; ++bit, pw = F::mul(pw, pw)) {
     if ((14 >> bit) & 1) sub = F::mul(sub, pw);
@@ -103,18 +82,8 @@ inline void hg_consts(HgArgs<F>& a, const uint64_t* params) {
   a.limbd = fr_to_rprime(limb);
 }
 
-// The per-point view of one edge
 template <class F>
-struct HgPoint {
-  using LZ = typename LazyOf<F>::type;
-  const HgArgs<F>& a;
-  size_t e;  // the edge's first element
-  int k;     // the point, 0 .. 6
-  CSH_HD LZ at(int c) const { return hr_extend(LZ::unpack(a.col[c][e]), LZ::unpack(a.col[c][e + 1]), k); }
-  CSH_HD LZ one() const { return LZ::unpack(a.one); }
-  CSH_HD bool zero_at_both_ends(int c) const { return a.col[c][e].is_zero() && a.col[c][e + 1].is_zero(); }
-  CSH_HD LZ scaling(size_t j) const { return LZ::unpack(a.scaling ? a.scaling[((a.edge_begin >> 1) + j) * a.scaling_stride] : a.one); }
-};
+using HgPoint = HsPoint<HgArgs<F>>;  // the per-point view of one edge (honk_stage.hpp)
 
 // folded sums: F from at most three terms of F
 template <class LZ>
@@ -286,34 +255,47 @@ CSH_HD void hg_poseidon2_internal_at(const HgPoint<F>& p, const LZ& sc, LZ& r0, 
 // of elliptic_relation.rs:63-69, memory_relation.rs:114-117, non_native_field_relation.rs:59-62, poseidon2_external_relation.rs:92-95
 // and poseidon2_internal_relation.rs:94-97.
 template <int G, class F, class LZ>
-CSH_HD void hg_accumulate_edge(const HgArgs<F>& a, size_t j, int k, LZ (&acc)[HgGroup<G>::SUMS]) {
-  const HgPoint<F> p{a, a.edge_begin + 2 * j, k};
+CSH_HD void hg_accumulate_edge(const HgArgs<F>& a, size_t j, int k, LZ (&acc)[hg_group(G).sums]) {
+  const HgPoint<F> p(a, j, k);
   auto sum = [&](int s, const LZ& term) CSH_LAMBDA_INLINE { acc[s] = LZ::add(acc[s], term).fold_top(); };
   if (G == HG_EN) {
     if (!p.zero_at_both_ends(HG_Q_ELLIPTIC)) {
       LZ r0, r1;
-      hg_elliptic_at(p, p.scaling(j), r0, r1);
+      hg_elliptic_at(p, p.scaling(), r0, r1);
       sum(0, r0), sum(1, r1);
     }
     if (!p.zero_at_both_ends(HG_Q_NNF)) {
       LZ r0;
-      hg_nnf_at(p, p.scaling(j), r0);
+      hg_nnf_at(p, p.scaling(), r0);
       sum(2, r0);
     }
   } else if (G == HG_MEM) {
-    if (!p.zero_at_both_ends(HG_Q_MEMORY)) hg_memory_at(p, p.scaling(j), sum);
+    if (!p.zero_at_both_ends(HG_Q_MEMORY)) hg_memory_at(p, p.scaling(), sum);
   } else {
     if (!p.zero_at_both_ends(HG_Q_POSEIDON2_EXTERNAL)) {
       LZ r0, r1, r2, r3;
-      hg_poseidon2_external_at(p, p.scaling(j), r0, r1, r2, r3);
+      hg_poseidon2_external_at(p, p.scaling(), r0, r1, r2, r3);
       sum(0, r0), sum(1, r1), sum(2, r2), sum(3, r3);
     }
     if (!p.zero_at_both_ends(HG_Q_POSEIDON2_INTERNAL)) {
       LZ r0, r1, r2, r3;
-      hg_poseidon2_internal_at(p, p.scaling(j), r0, r1, r2, r3);
+      hg_poseidon2_internal_at(p, p.scaling(), r0, r1, r2, r3);
       sum(4, r0), sum(5, r1), sum(6, r2), sum(7, r3);
     }
   }
 }
+
+// The family, as honk_stage.hpp reads it
+struct HgFam {
+  template <class F>
+  using Args = HgArgs<F>;
+  static constexpr int COLS = HG_COLS, PARAMS = 8, ACC_ELEMS = 110, GROUPS = 3;  // params: eta_1..3, curve_b, the four diagonal values
+  static constexpr HsGroup group(int g) { return hg_group(g); }
+  template <class F>
+  static void consts(HgArgs<F>& a, const uint64_t* params) { hg_consts(a, params); }
+  template <int G, class F, class LZ>
+  CSH_HD static void accumulate_edge(const HgArgs<F>& a, size_t j, int k, LZ (&acc)[hg_group(G).sums]) { hg_accumulate_edge<G>(a, j, k, acc); }
+};
+static_assert(hs_family_ok<HgFam>(), "the accumulators tile acc[110], none is longer than its group's points, every (point, edge slot) has a lane");
 
 }  // namespace csh

@@ -51,28 +51,14 @@
 // Field addition is exact and every output is canonical, so the 57 words do not depend on how edges are dealt to lanes, workgroups or
 // passes. No bound depends on the range, the stride or the data. The only floating point is fold_top()'s quotient estimate.
 #pragma once
-#include "common.hpp"
-#include "field.hpp"
-#include "field29.hpp"
-#include "fr_entry.hpp"
+#include "honk_stage.hpp"
 
 namespace csh {
 
 constexpr int HR_COLS = 36;
 constexpr int HR_SUBRELATIONS = 11;
-constexpr int HR_POINTS = 6;       // the longest accumulator
-constexpr int HR_ACC_ELEMS = 57;
 constexpr int HR_MAX_BETAS = 28;
-constexpr size_t HR_MAX_EDGE_END = size_t(1) << 28;
-// lengths and offsets of the eleven accumulators in acc[57]
-CSH_HD int hr_acc_len(int s) {
-  constexpr int len[HR_SUBRELATIONS] = {6, 5, 6, 3, 5, 5, 3, 6, 6, 6, 6};
-  return len[s];
-}
-CSH_HD int hr_acc_off(int s) {
-  constexpr int off[HR_SUBRELATIONS] = {0, 6, 11, 17, 20, 25, 30, 33, 39, 45, 51};
-  return off[s];
-}
+constexpr int HR_ALL = 15;  // all four relations in one launch
 
 enum HrCol : int {
   HR_W_L = 0, HR_W_R, HR_W_O, HR_W_4, HR_Z_PERM, HR_LOOKUP_INVERSES, HR_LOOKUP_READ_COUNTS, HR_LOOKUP_READ_TAGS,
@@ -83,13 +69,9 @@ enum HrCol : int {
 };
 enum HrSub : int { HR_ARITH_0 = 0, HR_ARITH_1, HR_PERM_0, HR_PERM_1, HR_LOOKUP_0, HR_LOOKUP_1, HR_LOOKUP_2, HR_DELTA_0, HR_DELTA_1, HR_DELTA_2, HR_DELTA_3 };
 
-// What one call is told. Edge j (0 <= j < n_edges) is the pair of elements edge_begin + 2 j, edge_begin + 2 j + 1 of every column.
+// The constants of a call beside HsArgs's; hr_consts finds a.one set (hs_args)
 template <class F>
-struct HrArgs {
-  const F* col[HR_COLS];
-  const F* scaling;       // factor of edge j = scaling[((edge_begin >> 1) + j) * scaling_stride]; NULL = one
-  size_t scaling_stride;
-  size_t edge_begin, n_edges;
+struct HrArgs : HsArgs<F, HR_COLS> {
   F betad, pidd, neg_halfd;  // beta R', public_input_delta R', (-1/2) R'
   F gamma, one, two, three;  // arkworks-Montgomery
 };
@@ -98,7 +80,6 @@ inline void hr_consts(HrArgs<F>& a, const uint64_t* params) {
   a.betad = fr_to_rprime(fr_load<F>(params));
   a.gamma = fr_load<F>(params + 4);
   a.pidd = fr_to_rprime(fr_load<F>(params + 8));
-  a.one = F::one();
   a.two = F::add(a.one, a.one);
   a.three = F::add(a.two, a.one);
   a.neg_halfd = fr_to_rprime(F::neg(F::inv(a.two)));
@@ -129,20 +110,8 @@ CSH_HD LZ hr_mulc(const LZ& x, const LZ& cd) {
   return LZ::mul(x, cd);
 }
 
-// The per-point view of one edge: what a lane (or the self-test's loop) hands to the relations. at(c) is the column's value at the point.
 template <class F>
-struct HrPoint {
-  using LZ = typename LazyOf<F>::type;
-  const HrArgs<F>& a;
-  size_t e;  // the edge's first element
-  int k;     // the point
-  CSH_HD LZ at(int c) const { return hr_extend(LZ::unpack(a.col[c][e]), LZ::unpack(a.col[c][e + 1]), k); }
-  CSH_HD LZ gamma() const { return LZ::unpack(a.gamma); }
-  CSH_HD LZ one() const { return LZ::unpack(a.one); }
-  // the edge's two elements are zero / equal to another column's (inputs are canonical: equal residues are equal words)
-  CSH_HD bool zero_at_both_ends(int c) const { return a.col[c][e].is_zero() && a.col[c][e + 1].is_zero(); }
-  CSH_HD bool same_at_both_ends(int c, int d) const { return a.col[c][e] == a.col[d][e] && a.col[c][e + 1] == a.col[d][e + 1]; }
-};
+using HrPoint = HsPoint<HrArgs<F>>;  // the per-point view of one edge (honk_stage.hpp)
 
 // ---- the four relations at one point, in the shape of the reference's verify_accumulate; `sc` = the edge's scaling factor (U) ---------
 // ultra_arithmetic_relation.rs:177-223
@@ -166,7 +135,7 @@ CSH_HD void hr_arith_at(const HrPoint<F>& p, const LZ& sc, LZ& r0, LZ& r1) {
 // permutation_relation.rs:169-237
 template <class F, class LZ>
 CSH_HD void hr_perm_at(const HrPoint<F>& p, const LZ& sc, LZ& r0, LZ& r1) {
-  const LZ betad = LZ::unpack(p.a.betad), gamma = p.gamma();
+  const LZ betad = LZ::unpack(p.a.betad), gamma = LZ::unpack(p.a.gamma);
   LZ num = sc, den = sc;
   for (int j = 0; j < 4; ++j) {
     const LZ wg = LZ::add(p.at(HR_W_L + j), gamma);
@@ -182,7 +151,7 @@ CSH_HD void hr_perm_at(const HrPoint<F>& p, const LZ& sc, LZ& r0, LZ& r1) {
 // reference's sums of powers, and beta is the only power a lane holds.
 template <class F, class LZ>
 CSH_HD void hr_lookup_at(const HrPoint<F>& p, const LZ& sc, LZ& r0, LZ& r1, LZ& r2) {
-  const LZ betad = LZ::unpack(p.a.betad), gamma = p.gamma();
+  const LZ betad = LZ::unpack(p.a.betad), gamma = LZ::unpack(p.a.gamma);
   LZ read, write;
   {
     const LZ d3 = LZ::add(hr_mul(p.at(HR_Q_C), p.at(HR_W_O_SHIFT)), p.at(HR_W_O));
@@ -227,8 +196,8 @@ CSH_HD void hr_delta_at(const HrPoint<F>& p, const LZ& sc, LZ& r0, LZ& r1, LZ& r
 // (bit 0 arith, 1 perm, 2 lookup, 3 delta): the kernel is instantiated with all four.
 template <int REL, class F, class LZ>
 CSH_HD void hr_accumulate_edge(const HrArgs<F>& a, size_t j, int k, LZ (&acc)[HR_SUBRELATIONS]) {
-  const HrPoint<F> p{a, a.edge_begin + 2 * j, k};
-  const LZ sc = LZ::unpack(a.scaling ? a.scaling[((a.edge_begin >> 1) + j) * a.scaling_stride] : a.one);
+  const HrPoint<F> p(a, j, k);
+  const LZ sc = p.scaling();
   auto sum = [&](int s, const LZ& term) CSH_LAMBDA_INLINE { acc[s] = LZ::add(acc[s], term).fold_top(); };
   if ((REL & 1) && !p.zero_at_both_ends(HR_Q_ARITH)) {
     LZ r0, r1;
@@ -251,6 +220,23 @@ CSH_HD void hr_accumulate_edge(const HrArgs<F>& a, size_t j, int k, LZ (&acc)[HR
     sum(HR_DELTA_0, r0), sum(HR_DELTA_1, r1), sum(HR_DELTA_2, r2), sum(HR_DELTA_3, r3);
   }
 }
+
+// The family, as honk_stage.hpp reads it
+struct HrFam {
+  template <class F>
+  using Args = HrArgs<F>;
+  static constexpr int COLS = HR_COLS, PARAMS = 3, ACC_ELEMS = 57, GROUPS = 1;  // params: beta, gamma, public_input_delta
+  // one group: eleven running sums at six points (the longest accumulator), 42 edges per pass, no occupancy asked of the launch bound;
+  // then the places and the lengths of the eleven accumulators in acc[57]
+  static constexpr HsGroup group(int) {
+    return HsGroup{HR_SUBRELATIONS, 6, 42, 0, {0, 6, 11, 17, 20, 25, 30, 33, 39, 45, 51}, {6, 5, 6, 3, 5, 5, 3, 6, 6, 6, 6}};
+  }
+  template <class F>
+  static void consts(HrArgs<F>& a, const uint64_t* params) { hr_consts(a, params); }
+  template <int G, class F, class LZ>
+  CSH_HD static void accumulate_edge(const HrArgs<F>& a, size_t j, int k, LZ (&acc)[HR_SUBRELATIONS]) { hr_accumulate_edge<HR_ALL>(a, j, k, acc); }
+};
+static_assert(hs_family_ok<HrFam>(), "the accumulators tile acc[57], none is longer than its group's points, every (point, edge slot) has a lane");
 
 // ---- the gate-separator table, decider/types.rs:53-67 -----------------------------------------------------------------------------------
 template <class F>

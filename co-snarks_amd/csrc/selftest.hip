@@ -714,55 +714,9 @@ static int honk_oink_host_t(int entry, size_t n, size_t domain_size, uint32_t pr
   return CSH_ERR_INVALID;
 }
 
-// Host run of the sumcheck round (honk_relations.hip) with the limb-bound checks on: the argument struct is filled in by the function the
-// launcher uses, and for each of the six points one set of eleven running sums takes every edge of the range through
-// hr_accumulate_edge(), the function a lane of k_hr_accumulate calls -- one lane's grid-stride loop with as many passes as the range has
-// edges. acc = 57 elements, written as k_hr_finish writes them.
-template <class F>
-static int honk_relations_host_t(const uint64_t* const* cols, size_t edge_begin, size_t edge_end, const uint64_t* scaling, size_t scaling_stride,
-                                 const uint64_t* params, uint64_t* acc_out) {
-  using LZ = typename LazyOf<F>::type;
-  HrArgs<F> a;
-  for (int c = 0; c < HR_COLS; ++c) a.col[c] = (const F*)cols[c];
-  a.scaling = (const F*)scaling, a.scaling_stride = scaling_stride;
-  a.edge_begin = edge_begin, a.n_edges = (edge_end - edge_begin) / 2;
-  hr_consts(a, params);
-  for (int k = 0; k < HR_POINTS; ++k) {
-    LZ acc[HR_SUBRELATIONS];
-    for (int s = 0; s < HR_SUBRELATIONS; ++s) acc[s] = LZ::zero();
-    for (size_t j = 0; j < a.n_edges; ++j) hr_accumulate_edge<15>(a, j, k, acc);
-    for (int s = 0; s < HR_SUBRELATIONS; ++s)
-      if (k < hr_acc_len(s)) ((F*)acc_out)[hr_acc_off(s) + k] = acc[s].canonical_narrow().pack();
-  }
-  return CSH_OK;
-}
-// Host run of the sumcheck round's other five relations (honk_gates.hip) with the limb-bound checks on: the argument struct is filled in by
-// the function the launcher uses, and for each group and each of its points one set of running sums takes every edge of the range through
-// hg_accumulate_edge(), the function a lane of k_hg_accumulate calls. acc = 110 elements, written where k_hg_finish writes them.
-template <int G, class F>
-static void honk_gates_group_host(const HgArgs<F>& a, F* acc_out) {
-  using LZ = typename LazyOf<F>::type;
-  using GR = HgGroup<G>;
-  for (int k = 0; k < GR::POINTS; ++k) {
-    LZ acc[GR::SUMS];
-    for (int s = 0; s < GR::SUMS; ++s) acc[s] = LZ::zero();
-    for (size_t j = 0; j < a.n_edges; ++j) hg_accumulate_edge<G>(a, j, k, acc);
-    for (int s = 0; s < GR::SUMS; ++s) acc_out[GR::off(s) + k] = acc[s].canonical_narrow().pack();
-  }
-}
-template <class F>
-static int honk_gates_host_t(const uint64_t* const* cols, size_t edge_begin, size_t edge_end, const uint64_t* scaling, size_t scaling_stride,
-                             const uint64_t* params, uint64_t* acc_out) {
-  HgArgs<F> a;
-  for (int c = 0; c < HG_COLS; ++c) a.col[c] = (const F*)cols[c];
-  a.scaling = (const F*)scaling, a.scaling_stride = scaling_stride;
-  a.edge_begin = edge_begin, a.n_edges = (edge_end - edge_begin) / 2;
-  hg_consts(a, params);
-  honk_gates_group_host<HG_EN>(a, (F*)acc_out);
-  honk_gates_group_host<HG_MEM>(a, (F*)acc_out);
-  honk_gates_group_host<HG_POS>(a, (F*)acc_out);
-  return CSH_OK;
-}
+// The host runs of the sumcheck round's two entries (honk_relations.hip, honk_gates.hip) with the limb-bound checks on are
+// honk_stage.hpp's hs_host_run: the argument struct is filled in by the function the launcher uses, and every edge of the range goes through
+// the function a lane of k_hs_accumulate calls. acc = 57 and 110 elements.
 template <class F>
 static int honk_pow_table_host_t(const uint64_t* betas, size_t m, uint64_t* out) {
   HrPowArgs<F> a;
@@ -900,12 +854,12 @@ int csh_selftest_honk_oink_host(int field_of, int entry, size_t n, size_t domain
 int csh_selftest_honk_relations_host(int field_of, const uint64_t* const* cols, size_t edge_begin, size_t edge_end, const uint64_t* scaling,
                                      size_t scaling_stride, const uint64_t* params, uint64_t* acc_out) {
   if (!cols || !params || !acc_out || (edge_begin & 1) || (edge_end & 1) || edge_begin >= edge_end || (scaling && !scaling_stride)) return CSH_ERR_INVALID;
-  return FR_CALL(field_of, honk_relations_host_t<F>(cols, edge_begin, edge_end, scaling, scaling_stride, params, acc_out));
+  return FR_CALL(field_of, (hs_host_run<HrFam, F>(HsCall{cols, edge_begin, edge_end, scaling, scaling_stride, params, acc_out})));
 }
 int csh_selftest_honk_gates_host(int field_of, const uint64_t* const* cols, size_t edge_begin, size_t edge_end, const uint64_t* scaling,
                                  size_t scaling_stride, const uint64_t* params, uint64_t* acc_out) {
   if (!cols || !params || !acc_out || (edge_begin & 1) || (edge_end & 1) || edge_begin >= edge_end || (scaling && !scaling_stride)) return CSH_ERR_INVALID;
-  return FR_CALL(field_of, honk_gates_host_t<F>(cols, edge_begin, edge_end, scaling, scaling_stride, params, acc_out));
+  return FR_CALL(field_of, (hs_host_run<HgFam, F>(HsCall{cols, edge_begin, edge_end, scaling, scaling_stride, params, acc_out})));
 }
 int csh_selftest_honk_pow_table_host(int field_of, const uint64_t* betas, size_t m, uint64_t* out) {
   if (!out || (m && !betas) || m > 20) return CSH_ERR_INVALID;

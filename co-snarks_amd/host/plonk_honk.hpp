@@ -831,38 +831,47 @@ template <class Fr>
 using HonkGateAccumulators = std::array<Fr, HONK_GATES_ACC_ELEMS>;  // the seventeen accumulators back to back, HONK_GATES_ACC_LENGTHS
 
 namespace detail {
+// what both entries of the round ask of their columns, range and gate separator; `who` = the caller's name, `ncols` = 36 or 19
 template <class Fr>
-inline void honk_check_round(const std::vector<std::vector<Fr>>& cols, size_t edge_begin, size_t edge_end, const HonkGateSeparator<Fr>* gs) {
-  if (cols.size() != HONK_SUMCHECK_COLUMNS) throw Error("compute_round_accumulators: 36 columns");
-  if ((edge_begin & 1) || (edge_end & 1) || edge_begin >= edge_end) throw Error("compute_round_accumulators: an even, non-empty range");
+inline void honk_check_round(const char* who, size_t ncols, const std::vector<std::vector<Fr>>& cols, size_t edge_begin, size_t edge_end,
+                             const HonkGateSeparator<Fr>* gs) {
+  const std::string w = std::string(who) + ": ";
+  if (cols.size() != ncols) throw Error(w + std::to_string(ncols) + " columns");
+  if ((edge_begin & 1) || (edge_end & 1) || edge_begin >= edge_end) throw Error(w + "an even, non-empty range");
   for (const auto& c : cols)
-    if (c.size() < edge_end) throw Error("compute_round_accumulators: a column is shorter than the range");
+    if (c.size() < edge_end) throw Error(w + "a column is shorter than the range");
   if (gs && (gs->log_num_monomials > 28 || gs->betas.size() < gs->log_num_monomials || ((edge_end >> 1) - 1) * gs->periodicity >= (size_t(1) << gs->log_num_monomials)))
-    throw Error("compute_round_accumulators: the gate separator's table is shorter than the range reads");
+    throw Error(w + "the gate separator's table is shorter than the range reads");
 }
-// The loop of compute_univariate_inner (:239-252) on the device: the columns go up, beta_products is made there
-// (csh_honk_pow_table_dev), csh_honk_sumcheck_accumulate_dev, 57 elements come back. gs == nullptr: the factor one
+// The loop of compute_univariate_inner (:239-252) on the device, for either entry of the round (`entry`, `entry_name`): the columns go up,
+// beta_products is made there (csh_honk_pow_table_dev), the entry runs, its ACC elements come back. gs == nullptr: the factor one
 // (compute_virtual_contribution, :388-421).
-template <class P>
-inline HonkAccumulators<typename P::Fr> plain_round_accumulators(const std::vector<std::vector<typename P::Fr>>& cols, size_t edge_begin, size_t edge_end,
-                                                                 const HonkGateSeparator<typename P::Fr>* gs, const HonkRelationParameters<typename P::Fr>& params) {
+template <class P, size_t ACC, class Entry, size_t NP>
+inline std::array<typename P::Fr, ACC> plain_round_device(const char* who, Entry entry, const char* entry_name, size_t ncols,
+                                                          const std::vector<std::vector<typename P::Fr>>& cols, size_t edge_begin, size_t edge_end,
+                                                          const HonkGateSeparator<typename P::Fr>* gs, const typename P::Fr (&pr)[NP]) {
   using Fr = typename P::Fr;
-  honk_check_round(cols, edge_begin, edge_end, gs);
+  honk_check_round(who, ncols, cols, edge_begin, edge_end, gs);
   DevicePool pool;
-  const uint64_t* dc[HONK_SUMCHECK_COLUMNS];
-  for (size_t c = 0; c < HONK_SUMCHECK_COLUMNS; ++c) dc[c] = pool.up(cols[c]);
+  std::vector<const uint64_t*> dc(ncols);
+  for (size_t c = 0; c < ncols; ++c) dc[c] = pool.up(cols[c]);
   uint64_t* table = nullptr;
   if (gs) {
     table = pool.fresh(sizeof(Fr) << gs->log_num_monomials);
     check(csh_honk_pow_table_dev(P::ID, (const uint64_t*)gs->betas.data(), gs->log_num_monomials, table, nullptr), "csh_honk_pow_table_dev");
   }
-  uint64_t* acc = pool.fresh(sizeof(Fr) * HONK_ACC_ELEMS);
-  const Fr pr[3] = {params.beta, params.gamma, params.public_input_delta};
-  check(csh_honk_sumcheck_accumulate_dev(P::ID, dc, edge_begin, edge_end, table, gs ? gs->periodicity : 1, (const uint64_t*)pr, acc, nullptr),
-        "csh_honk_sumcheck_accumulate_dev");
-  HonkAccumulators<Fr> out;
-  check(csh_memcpy_d2h(out.data(), acc, sizeof(Fr) * HONK_ACC_ELEMS), "csh_memcpy_d2h");
+  uint64_t* acc = pool.fresh(sizeof(Fr) * ACC);
+  check(entry(P::ID, dc.data(), edge_begin, edge_end, table, gs ? gs->periodicity : 1, (const uint64_t*)pr, acc, nullptr), entry_name);
+  std::array<Fr, ACC> out;
+  check(csh_memcpy_d2h(out.data(), acc, sizeof(Fr) * ACC), "csh_memcpy_d2h");
   return out;
+}
+template <class P>
+inline HonkAccumulators<typename P::Fr> plain_round_accumulators(const std::vector<std::vector<typename P::Fr>>& cols, size_t edge_begin, size_t edge_end,
+                                                                 const HonkGateSeparator<typename P::Fr>* gs, const HonkRelationParameters<typename P::Fr>& params) {
+  const typename P::Fr pr[3] = {params.beta, params.gamma, params.public_input_delta};
+  return plain_round_device<P, HONK_ACC_ELEMS>("compute_round_accumulators", csh_honk_sumcheck_accumulate_dev, "csh_honk_sumcheck_accumulate_dev",
+                                               HONK_SUMCHECK_COLUMNS, cols, edge_begin, edge_end, gs, pr);
 }
 template <class Fr>
 inline std::vector<Fr> honk_beta_products(const std::vector<Fr>& betas, size_t log_num_monomials) {  // types.rs:53-67
@@ -875,11 +884,11 @@ inline std::vector<Fr> honk_beta_products(const std::vector<Fr>& betas, size_t l
   return out;
 }
 // The same loop in plain C++ on one host thread, the relations in the scalar shape of verify_accumulate at each of the points 0 .. 5: what
-// the mirror test holds the device against, and the host column of tools/honk_relations_probe.py.
+// the mirror test holds the device against, and the host column of tools/honk_sumcheck_probe.py.
 template <class Fr>
 inline HonkAccumulators<Fr> host_round_accumulators(const std::vector<std::vector<Fr>>& cols, size_t edge_begin, size_t edge_end, const HonkGateSeparator<Fr>* gs,
                                                     const HonkRelationParameters<Fr>& params) {
-  honk_check_round(cols, edge_begin, edge_end, gs);
+  honk_check_round("compute_round_accumulators", HONK_SUMCHECK_COLUMNS, cols, edge_begin, edge_end, gs);
   const std::vector<Fr> table = gs ? honk_beta_products(gs->betas, gs->log_num_monomials) : std::vector<Fr>();
   const Fr one = Fr::one(), two = Fr::add(one, one), three = Fr::add(two, one), neg_half = Fr::sub(Fr::zero(), Fr::inv(two));
   const Fr beta = params.beta, gamma = params.gamma;
@@ -988,47 +997,24 @@ inline std::array<Fr, HONK_BATCHED_RELATION_PARTIAL_LENGTH> honk_batch_over_rela
   }
   return result;
 }
-template <class Fr>
-inline void honk_check_round_gates(const std::vector<std::vector<Fr>>& cols, size_t edge_begin, size_t edge_end, const HonkGateSeparator<Fr>* gs) {
-  if (cols.size() != HONK_GATES_COLUMNS) throw Error("compute_round_accumulators_gates: 19 columns");
-  if ((edge_begin & 1) || (edge_end & 1) || edge_begin >= edge_end) throw Error("compute_round_accumulators_gates: an even, non-empty range");
-  for (const auto& c : cols)
-    if (c.size() < edge_end) throw Error("compute_round_accumulators_gates: a column is shorter than the range");
-  if (gs && (gs->log_num_monomials > 28 || gs->betas.size() < gs->log_num_monomials || ((edge_end >> 1) - 1) * gs->periodicity >= (size_t(1) << gs->log_num_monomials)))
-    throw Error("compute_round_accumulators_gates: the gate separator's table is shorter than the range reads");
-}
 // The same loop for subrelations 11 .. 27 on the device: csh_honk_sumcheck_accumulate_gates_dev, 110 elements come back
 template <class P>
 inline HonkGateAccumulators<typename P::Fr> plain_round_accumulators_gates(const std::vector<std::vector<typename P::Fr>>& cols, size_t edge_begin, size_t edge_end,
                                                                            const HonkGateSeparator<typename P::Fr>* gs,
                                                                            const HonkGateParameters<typename P::Fr>& params) {
-  using Fr = typename P::Fr;
-  honk_check_round_gates(cols, edge_begin, edge_end, gs);
-  DevicePool pool;
-  const uint64_t* dc[HONK_GATES_COLUMNS];
-  for (size_t c = 0; c < HONK_GATES_COLUMNS; ++c) dc[c] = pool.up(cols[c]);
-  uint64_t* table = nullptr;
-  if (gs) {
-    table = pool.fresh(sizeof(Fr) << gs->log_num_monomials);
-    check(csh_honk_pow_table_dev(P::ID, (const uint64_t*)gs->betas.data(), gs->log_num_monomials, table, nullptr), "csh_honk_pow_table_dev");
-  }
-  uint64_t* acc = pool.fresh(sizeof(Fr) * HONK_GATES_ACC_ELEMS);
-  const Fr pr[8] = {params.eta_1, params.eta_2, params.eta_3, params.curve_b, params.mat_internal_diag_m_1[0], params.mat_internal_diag_m_1[1],
-                    params.mat_internal_diag_m_1[2], params.mat_internal_diag_m_1[3]};
-  check(csh_honk_sumcheck_accumulate_gates_dev(P::ID, dc, edge_begin, edge_end, table, gs ? gs->periodicity : 1, (const uint64_t*)pr, acc, nullptr),
-        "csh_honk_sumcheck_accumulate_gates_dev");
-  HonkGateAccumulators<Fr> out;
-  check(csh_memcpy_d2h(out.data(), acc, sizeof(Fr) * HONK_GATES_ACC_ELEMS), "csh_memcpy_d2h");
-  return out;
+  const typename P::Fr pr[8] = {params.eta_1, params.eta_2, params.eta_3, params.curve_b, params.mat_internal_diag_m_1[0], params.mat_internal_diag_m_1[1],
+                                params.mat_internal_diag_m_1[2], params.mat_internal_diag_m_1[3]};
+  return plain_round_device<P, HONK_GATES_ACC_ELEMS>("compute_round_accumulators_gates", csh_honk_sumcheck_accumulate_gates_dev,
+                                                     "csh_honk_sumcheck_accumulate_gates_dev", HONK_GATES_COLUMNS, cols, edge_begin, edge_end, gs, pr);
 }
 // The same loop in plain C++ on one host thread, the five relations in the scalar shape of each file's verify_accumulate at each of the
 // points 0 .. 6 (elliptic_relation.rs:163-240, memory_relation.rs:360-561, non_native_field_relation.rs:179-269,
 // poseidon2_external_relation.rs:207-281, poseidon2_internal_relation.rs:202-270): what the mirror test holds the device against, and
-// the host column of tools/honk_gates_probe.py
+// the host column of tools/honk_sumcheck_probe.py
 template <class Fr>
 inline HonkGateAccumulators<Fr> host_round_accumulators_gates(const std::vector<std::vector<Fr>>& cols, size_t edge_begin, size_t edge_end,
                                                               const HonkGateSeparator<Fr>* gs, const HonkGateParameters<Fr>& params) {
-  honk_check_round_gates(cols, edge_begin, edge_end, gs);
+  honk_check_round("compute_round_accumulators_gates", HONK_GATES_COLUMNS, cols, edge_begin, edge_end, gs);
   const std::vector<Fr> table = gs ? honk_beta_products(gs->betas, gs->log_num_monomials) : std::vector<Fr>();
   auto mul = [](const Fr& x, const Fr& y) { return Fr::mul(x, y); };
   auto add = [](const Fr& x, const Fr& y) { return Fr::add(x, y); };

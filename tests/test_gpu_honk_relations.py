@@ -94,8 +94,8 @@ def check_range(hip, curve, n, b, e, stride=1, scaled=True, what=None):
 
 
 # the smallest shapes at which the kernel can go wrong: one edge; 2 and 3 edges; the disabled-rows call [12, 16) of 16; 65 and 66 edges,
-# across a wave; 257 edges, across a workgroup's 42 edges per pass several times over and across 256
-SHAPES = [(2, 0, 2), (4, 0, 4), (6, 0, 6), (16, 12, 16), (130, 0, 130), (132, 0, 132), (514, 0, 514)]
+# across a wave; 257 edges, across a workgroup's 42 edges per pass several times over and across 256; 41, 42 and 43 edges, around one pass
+SHAPES = [(2, 0, 2), (4, 0, 4), (6, 0, 6), (16, 12, 16), (130, 0, 130), (132, 0, 132), (514, 0, 514), (82, 0, 82), (84, 0, 84), (86, 0, 86)]
 
 
 @pytest.mark.parametrize("n,b,e", SHAPES)

@@ -154,6 +154,26 @@ def test_host_kernels_at_the_edges_of_the_field(hip, curve, fill):
 
 
 @pytest.mark.parametrize("curve", CURVES)
+def test_both_host_runs_place_every_element_where_the_restatement_has_it(hip, curve):
+    """[4, 90): 43 edges, one more than a pass of 42, behind a begin offset, through both self-test entries. Random data without planted
+    skips, so every one of the 57 and of the 110 elements is non-zero in the restatement: an element written to another's place cannot hide
+    behind a zero. The words are compared, not the residues."""
+    from tests import honk_gates_ref as G
+    F = H.FR[curve]
+    p, n, b, e = F.p, 90, 4, 90
+    table = R.beta_products(p, [H.rng(21).randrange(1, p) for _ in range(6)], 6)
+    for ref, entry, elems, seed in ((R, "csh_selftest_honk_relations_host", 57, 901), (G, "csh_selftest_honk_gates_host", 110, 902)):
+        c = ref.random_case(p, n, seed, plants=False)
+        flat = [v for acc in ref.accumulate_range(p, c["polys"], b, e, table, 1, c["params"]) for v in acc]
+        assert len(flat) == elems and all(flat), entry
+        out = np.full(4 * elems + 8, FILL, dtype=np.uint64)
+        cols, sc, pr = [H.pack(F, c["polys"][name]) for name in ref.COLS], H.pack(F, table), H.pack(F, list(c["params"]))
+        rc = getattr(hip.lib(), entry)(H.CURVE_IDS[curve], _ptrs(cols), sz(b), sz(e), _p(sc), sz(1), _p(pr), _p(out))
+        assert rc == 0 and (out[4 * elems:] == FILL).all(), entry
+        assert (out[:4 * elems] == H.pack(F, flat)).all(), entry
+
+
+@pytest.mark.parametrize("curve", CURVES)
 def test_pow_table_on_the_host(hip, curve):
     F = H.FR[curve]
     r = H.rng(13)

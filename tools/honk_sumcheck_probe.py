@@ -1,23 +1,25 @@
 #!/usr/bin/env python3
-"""Device times of csh_honk_sumcheck_accumulate_gates_dev (csrc/honk_gates.hip: the elliptic, memory, non-native field and Poseidon2
-relations of the sumcheck round) on BN254 Fr:
+"""Device times of the plain sumcheck round's entries (csrc/honk_relations.hip, csrc/honk_gates.hip over csrc/honk_stage.hpp) on BN254 Fr:
 
-  gates worst   the entry over [0, n) with the gate-separator table at stride 2 (round 0), all five selectors non-zero on every row, so
-                that no edge of any of the three launches is skipped
+  vec_mul       csh_vec_mul_dev on as many values as one column has, in the same process: the HBM yardstick (one multiplication per 96 B)
+  pow_table     csh_honk_pow_table_dev for the table round 0 reads (log2 n betas)
+  gates worst   csh_honk_sumcheck_accumulate_gates_dev over [0, n) with the gate-separator table at stride 2 (round 0), all five
+                selectors non-zero on every row, so that no edge of any of the three launches is skipped
   gates mixed   the same call with each selector non-zero on a contiguous eighth of the rows of its own and zero elsewhere, as a circuit's
                 mutually exclusive, sparse gate blocks are: most edges of each launch read two selector words and leave
-  accumulate    csh_honk_sumcheck_accumulate_dev (subrelations 0 .. 10, 36 columns) on the same size in the same process, for scale
+  accumulate    csh_honk_sumcheck_accumulate_dev (subrelations 0 .. 10, 36 columns) on the same size, no edge skipped
   chain         rounds 0 .. log2 n - 1 of both entries + csh_mle_fold_dev of the 41 distinct columns (n = 2^20 only; worst-case columns)
-  host_loop     the mirror's plain C++ loop of the five relations on one host thread, through examples/honk_gates_from_cpp (--example EXE;
-                n = 2^12, 2^16)
+  host_loop     the mirror's plain C++ loops on one host thread, through examples/honk_sumcheck_from_cpp (--example EXE) and
+                examples/honk_gates_from_cpp (--gates-example EXE); n = 2^12, 2^16
 
-    python tools/honk_gates_probe.py [--log FILE] [--sizes 12,16,20,22] [--example EXE]
+    python tools/honk_sumcheck_probe.py [--log FILE] [--sizes 12,16,20,22] [--example EXE] [--gates-example EXE]
 
 Every device figure: the call back to back on the calling thread's stream between two HIP events, after bench.py's spin-up rule (untimed
 batches for at least 0.3 s until two consecutive batch means agree within 2 %, 3 s at the most); the median of 7 such batches, with the
-lowest and the highest of the 7 beside it. One JSON line per (stage, n), one process. `bytes` is what the worst case MUST read -- 19
-columns x 32 B x n plus the n / 2 scaling elements. One random column goes up and the others are running products of it made on the
-device (distinct, canonical, non-zero). Needs a device."""
+lowest and the highest of the 7 beside it. One JSON line per (stage, n), one process. `bytes` is what the worst case MUST read -- the
+entry's 19 or 36 columns x 32 B x n plus the n / 2 scaling elements. One random column goes up and the others are running products of it
+made on the device (distinct, canonical, non-zero). Only the C ABI is called, so COSNARKS_HIP_LIB may name another build of the library
+to time beside this one. Needs a device."""
 import argparse
 import ctypes as C
 import json
@@ -37,10 +39,11 @@ from cosnarks_amd import bindings as B
 ap = argparse.ArgumentParser()
 ap.add_argument("--log", default=None, help="also append the lines to this file")
 ap.add_argument("--sizes", default="12,16,20,22", help="log2 of the round size")
-ap.add_argument("--example", default=None, help="the built examples/honk_gates_from_cpp, for the host loop")
+ap.add_argument("--example", default=None, help="the built examples/honk_sumcheck_from_cpp, for the host loop of subrelations 0 .. 10")
+ap.add_argument("--gates-example", default=None, help="the built examples/honk_gates_from_cpp, for the host loop of the five gate relations")
 args = ap.parse_args()
 if not hip.have_device():
-    raise SystemExit("honk_gates_probe: no HIP device (there is no CPU path to time)")
+    raise SystemExit("honk_sumcheck_probe: no HIP device (there is no CPU path to time)")
 L = hip.lib()
 e0, e1 = B.Event(), B.Event()
 lines = []
@@ -119,7 +122,9 @@ for lg in sizes:
     mixed_col = gate_col[:14] + [sparse.ptr.value + s * 32 * n for s in range(5)]
     table, acc, gacc = hip.DeviceBuffer(32 * n), hip.DeviceBuffer(32 * 57), hip.DeviceBuffer(32 * 110)
     bp, pp, gp = (x.ctypes.data_as(C.c_void_p) for x in (betas, params, gate_params))
-    B._check(L.csh_honk_pow_table_dev(0, bp, sz(lg), table.ptr, None))
+    emit("vec_mul", n, measure(lambda: B._check(L.csh_vec_mul_dev(0, C.c_void_p(col[0]), C.c_void_p(col[1]), C.c_void_p(col[2]), sz(n), None)), reps), 96 * n)
+    B._check(L.csh_vec_mul_dev(0, C.c_void_p(col[1]), C.c_void_p(col[0]), C.c_void_p(col[2]), sz(n), None))   # col 2 as it was
+    emit("pow_table", n, measure(lambda: B._check(L.csh_honk_pow_table_dev(0, bp, sz(lg), table.ptr, None)), reps), 32 * n)
     cp, gcp, mcp = ptrs(col[:BASE_COLS]), ptrs(gate_col), ptrs(mixed_col)
     must = GATE_COLS * 32 * n + 32 * (n // 2)
     emit("gates worst: no edge skipped", n, measure(lambda: B._check(L.csh_honk_sumcheck_accumulate_gates_dev(0, gcp, sz(0), sz(n), table.ptr, sz(2), gp, gacc.ptr, None)), reps),
@@ -149,21 +154,23 @@ for lg in sizes:
     pool.free()
     sparse.free()
     table.free()
-if args.example:
-    for lg in (12, 16):
+# the examples' input: head, params, partial_evaluation_result, log2 n betas, the alphas, (the gate parameters,) the columns
+for exe, op, alphas, tail, cols in ((args.example, "host_loop (plain C++, one thread)", 10, [], BASE_COLS),
+                                    (args.gates_example, "host_loop (plain C++, one thread, five relations)", 27, [gate_params.reshape(-1)], ALL_COLS)):
+    for lg in (12, 16) if exe else ():
         n = 1 << lg
         with tempfile.TemporaryDirectory() as d:
             head = np.array([0, n, 0, n, lg, 2, 0], dtype=np.uint64)
             one = np.array([1, 0, 0, 0], dtype=np.uint64)   # partial_evaluation_result: any canonical element does for a timing
-            words = [head, params.reshape(-1), one, random_elements(rs, lg).reshape(-1), random_elements(rs, 27).reshape(-1), gate_params.reshape(-1),
-                     random_elements(rs, ALL_COLS * n).reshape(-1)]
+            words = [head, params.reshape(-1), one, random_elements(rs, lg).reshape(-1), random_elements(rs, alphas).reshape(-1)] + tail + \
+                    [random_elements(rs, cols * n).reshape(-1)]
             fin, fout = os.path.join(d, "in.bin"), os.path.join(d, "out.bin")
             np.concatenate(words).astype("<u8").tofile(fin)
-            r = subprocess.run([args.example, fin, fout], capture_output=True, text=True, timeout=600)
+            r = subprocess.run([exe, fin, fout], capture_output=True, text=True, timeout=600)
             if r.returncode != 0:
-                raise SystemExit("honk_gates_probe: %s failed: %s" % (args.example, r.stderr))
+                raise SystemExit("honk_sumcheck_probe: %s failed: %s" % (exe, r.stderr))
             us_host = int(np.fromfile(fout, dtype="<u8")[-1])
-        line = {"op": "host_loop (plain C++, one thread, five relations)", "n": n, "ms": round(us_host / 1000, 3), "edges": n // 2}
+        line = {"op": op, "n": n, "ms": round(us_host / 1000, 3), "edges": n // 2}
         lines.append(line)
         print(json.dumps(line), flush=True)
 if args.log:
